@@ -8,7 +8,14 @@ summarizer, then 100 Adam updates of minibatch 100 (fresh optimizer) and 6
 held-out evaluations.  Inputs are resident in HBM before the timed region.
 value = pairs processed by all ranks / wall time (max over ranks).
 
-    python bench.py --gpus 1 --steps 3 --warmup 1
+A plain run sets up, warms up, times --steps fits and prints the headline line.  --full adds
+everything else the benchmark measures (rooflines, NLL match against the oracle, scaled-batch
+mode, the other configs, the 1M-pair size, the CPU baseline; with several ranks the exchange
+timings); the --no-* options trim it.  --dump-outputs DIR writes what the last timed fit
+returned (loss logs, trained parameters) as DIR/<name>.npy.
+
+    python bench.py --gpus 1 --steps 3 --warmup 1 [--dump-outputs DIR]
+    python bench.py --full
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -56,6 +63,33 @@ CONFIGS = {
 }
 PEAK_HBM_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 PEAK_F32_TFLOPS = 157.3    # fp32 MFMA (= vector) peak
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 20      # elements kept of a parameter tensor larger than DUMP_MAX_BYTES / 4
+
+
+def dump_outputs(path, logs, model):
+    """--dump-outputs: what a caller of BayesSim.fit holds after the last timed step -- the per-chunk
+    loss logs fit returned (train_loss.npy, test_loss.npy: [chunks, logging points], float64) and the
+    trained estimator's parameters (param.<state_dict key>.npy, float32 / float64).  A tensor of
+    more than DUMP_MAX_BYTES / 4 bytes is written as a fixed, seeded sample of DUMP_SAMPLE of its
+    elements (flattened, in index order), so that two builds can be compared file for file."""
+    arrays = {'train_loss': np.asarray([lg['train_loss'] for lg in logs], dtype=np.float64),
+              'test_loss': np.asarray([lg['test_loss'] for lg in logs], dtype=np.float64)}
+    for key, t in model.state_dict().items():
+        if not torch.is_floating_point(t):
+            continue
+        a = t.detach().to('cpu', torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+        if a.nbytes > DUMP_MAX_BYTES // 4:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a.reshape(-1)[idx]
+        arrays['param.' + key] = a
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError('--dump-outputs: %d bytes, more than the %d allowed' % (total, DUMP_MAX_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a))
+    return sorted(arrays)
 
 
 def synth_pairs(cfg, n, seed, device):
@@ -932,28 +966,41 @@ def launch_ranks(n):
     return subprocess.run(rank_launch_command(n, sys.argv[1:], port), env=env).returncode
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=3)
-    ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--steps', type=int, default=3, help='timed fits')
+    ap.add_argument('--warmup', type=int, default=1, help='untimed fits before them')
     ap.add_argument('--config', default='cfg5', choices=sorted(CONFIGS))
     ap.add_argument('--pairs', type=int, default=0, help='pairs per GPU (default: config)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline also the rooflines, the NLL match against the oracle, the '
+                         'scaled-batch mode, the other configs, the 1M-pair size and the CPU baseline '
+                         '(several ranks: the exchange timings); the --no-* options trim it')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed fit returned as DIR/<name>.npy (dump_outputs)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
     ap.add_argument('--no-graph', action='store_true')
-    ap.add_argument('--no-scaled-batch', action='store_true')
+    ap.add_argument('--no-scaled-batch', action='store_true', help='--full without the scaled-batch mode')
     ap.add_argument('--only-scaled-batch', action='store_true',
                     help='run the scaled-batch mode alone (for profiling) and print its JSON')
     ap.add_argument('--no-largest-size', action='store_true',
-                    help='skip the 1M-pair fit (BASELINE config 5 size) of the default 1-GPU line')
+                    help='--full without the 1M-pair fit (BASELINE config 5 size) of the 1-GPU line')
     ap.add_argument('--no-per-config', action='store_true',
-                    help='skip the short fits of the other BASELINE-shaped configs')
+                    help='--full without the short fits of the other BASELINE-shaped configs')
     ap.add_argument('--variants', action='store_true',
-                    help='also time the fit with the persistent kernel / feature cache / RFF hoist off')
+                    help='with --full, also time the fit with the persistent kernel / feature cache / RFF hoist off')
     ap.add_argument('--watchdog', type=int, default=int(os.environ.get('BENCH_WATCHDOG', 1700)),
                     help='dump tracebacks and exit after this many seconds')
     ap.add_argument('--verbose', action='store_true')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
+
+
+def main():
+    args = parse_args()
     import faulthandler
     faulthandler.enable()
     faulthandler.dump_traceback_later(args.watchdog, exit=True)
@@ -1030,15 +1077,19 @@ def main():
     total_pairs = n * world * args.steps
     value = total_pairs / dt
     final_test = float(np.mean([lg['test_loss'][-1] for lg in logs]))
+    if args.dump_outputs and rank == 0:
+        # (before --full's legs: the roofline's launches run on the plan and move its weights)
+        dump_outputs(args.dump_outputs, logs, bsim.model)
+        note('outputs written to %s' % args.dump_outputs)
 
     out = None
-    if dist is not None and int(pkg._lib.load().bsig_fit_is_persistent(bsim.model._plan)):
+    if args.full and dist is not None and int(pkg._lib.load().bsig_fit_is_persistent(bsim.model._plan)):
         time_dp_loop(pkg, bsim)
     scaled_dp = None
-    if dist is not None and not args.no_scaled_batch:
+    if args.full and dist is not None and not args.no_scaled_batch:
         scaled_dp = scaled_batch_dp(pkg, cfg, theta, states, actions, device, dist, world)
     nll_dp = None
-    if dist is not None:
+    if args.full and dist is not None:
         nll_dp = nll_check_dp(pkg, cfg, theta, states, actions, device, dist, rank, world)
     if rank == 0:
         out = {
@@ -1067,6 +1118,7 @@ def main():
             'heldout_nll_last_step_mean': final_test,
         }
         note('timed region done: %.3f s' % dt)
+    if rank == 0 and args.full:
         out['roofline'] = time_dominant_kernel(pkg, cfg, bsim, device)
         out['roofline_summarizer'] = summarizer_roofline(pkg, cfg, bsim, min(n, 50000), device)
         if cfg['model'] == 'MDRFF':

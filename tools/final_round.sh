@@ -23,7 +23,7 @@ python3 tools/summarizer_bench.py 2>&1 | grep -v "amdgpu.ids" > "$OUT/${TAG}_sum
 python3 tools/gemm_scaled_sweep.py heldout 2>&1 | grep -v "amdgpu.ids" > "$OUT/${TAG}_gemm_heldout_sweep.txt"
 BSIG_PROF_T0=50 python3 tools/persist_prof.py 2>&1 | grep -v "amdgpu.ids" > "$OUT/${TAG}_cfg5_update_timeline_warm.txt"
 # a data-parallel rank on a 1-rank RCCL group: resident across the exchange (the default there) and one launch per update
-DPQ="--steps 3 --warmup 1 --no-per-config --no-largest-size --no-cpu-baseline --no-scaled-batch"
+DPQ="--full --steps 3 --warmup 1 --no-per-config --no-largest-size --no-cpu-baseline --no-scaled-batch"
 { echo "BSIG_DP_RESIDENT=1 BENCH_FORCE_DP=1 python bench.py $DPQ  (rank resident across the exchange: opt-in since round 6)"
   BSIG_DP_RESIDENT=1 BSIG_DP_XR_TRACE=1 BENCH_FORCE_DP=1 python3 bench.py $DPQ 2> "$OUT/${TAG}_dp_resident_stderr.log"
   grep "comm_xr:" "$OUT/${TAG}_dp_resident_stderr.log" | head -2
@@ -46,4 +46,4 @@ done
 bash tools/round_profiles.sh "$TAG" "$HEADSHA"
 # The bench line is NOT taken here: bench.pmc_traffic wants this pass's counters in profiles/ first (and
 # a line taken right behind the counter passes once read a scaled-batch fit at 0.49 of the peak).  Copy the files into profiles/, then, in a call of its own:
-#   python bench.py > gpurun_out/<tag>_bench_line.json
+#   python bench.py --full > "$OUT/<tag>_bench_line.json"   (OUT as above)

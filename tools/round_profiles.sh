@@ -41,7 +41,7 @@ run_pmc() {     # name, counter, program, args...
     "rocprofv3 --pmc $ctr --kernel-trace -- python $prog $*"
   sed -i "1i # head: $HEADSHA\n# csrc: $CSRC" $OUT/${TAG}_${name}_pmc_$ctr.txt
 }
-B5="--steps 1 --warmup 1 --no-cpu-baseline --no-scaled-batch --no-per-config --no-largest-size"
+B5="--full --steps 1 --warmup 1 --no-cpu-baseline --no-scaled-batch --no-per-config --no-largest-size"
 run_stats cfg5 bench.py $B5
 run_stats cfg3 bench.py --config cfg3 --pairs 20000 $B5
 run_stats scaled bench.py --only-scaled-batch
@@ -50,13 +50,13 @@ run_stats summarizers tools/summarizer_bench.py
 run_stats anymal bench.py --config anymal_yaml --pairs 5000 $B5
 run_stats shadow_more bench.py --config shadow_more --pairs 5000 $B5
 for c in FETCH_SIZE WRITE_SIZE; do
-  run_pmc anymal $c bench.py --config anymal_yaml --pairs 2000 --steps 1 --warmup 0 --no-cpu-baseline --no-scaled-batch --no-per-config --no-largest-size
-  run_pmc shadow_more $c bench.py --config shadow_more --pairs 2000 --steps 1 --warmup 0 --no-cpu-baseline --no-scaled-batch --no-per-config --no-largest-size
-  run_pmc cfg5 $c bench.py --pairs 5000 --steps 1 --warmup 0 --no-cpu-baseline --no-scaled-batch --no-per-config --no-largest-size
-  run_pmc cfg3 $c bench.py --config cfg3 --pairs 5000 --steps 1 --warmup 0 --no-cpu-baseline --no-scaled-batch --no-per-config --no-largest-size
+  run_pmc anymal $c bench.py --config anymal_yaml --pairs 2000 --full --steps 1 --warmup 0 --no-cpu-baseline --no-scaled-batch --no-per-config --no-largest-size
+  run_pmc shadow_more $c bench.py --config shadow_more --pairs 2000 --full --steps 1 --warmup 0 --no-cpu-baseline --no-scaled-batch --no-per-config --no-largest-size
+  run_pmc cfg5 $c bench.py --pairs 5000 --full --steps 1 --warmup 0 --no-cpu-baseline --no-scaled-batch --no-per-config --no-largest-size
+  run_pmc cfg3 $c bench.py --config cfg3 --pairs 5000 --full --steps 1 --warmup 0 --no-cpu-baseline --no-scaled-batch --no-per-config --no-largest-size
   run_pmc summarizers $c tools/summarizer_bench.py
 done
-BQ="--steps 1 --warmup 0 --no-cpu-baseline --no-scaled-batch --no-per-config --no-largest-size"
+BQ="--full --steps 1 --warmup 0 --no-cpu-baseline --no-scaled-batch --no-per-config --no-largest-size"
 for c in SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE; do
   run_pmc cfg5 $c bench.py --pairs 5000 $BQ
   run_pmc cfg3 $c bench.py --config cfg3 --pairs 5000 $BQ
