@@ -373,6 +373,7 @@ struct bsig_fit_plan {
   Layout L;
   int64_t batch, max_test, n_updates, n_evals;
   bool hoist;                  // RFF projection once per run_training call
+  bool feat_cache;             // ... may keep one feature row per training row (feat_cache_applies; BSIG_NO_FEAT_CACHE)
   bool feat_unique;            // ... of the distinct training rows (else of every gathered minibatch row)
   bool feats_preloaded;        // ... already handed over by the caller (bsig_fit_set_features)
   const float* ext_feats;      // ... and read where they lie (this call only) instead of copied
@@ -384,15 +385,14 @@ struct bsig_fit_plan {
   size_t train_ws_bytes, test_ws_bytes, feats_bytes, big_gemm_ws_bytes, iota_bytes;
   bool use_graph, split_adam;
 
-  bool persistent;             // updates run in the persistent kernel (persist.h)
-  bool persistent_mdnn;        // single-rank MDNN [128, 128] updates: fit_persistent_mdnn.hip
-  bool persistent_mdnn_cap;    // ... the plan's shape is covered (persistent_mdnn: this binding is)
-  bool mdnn_streams;           // ... with a streamed first layer (cross-correlation factor rows only)
+  PersistEngine eng;           // the persistent update engine resolved at creation (persist.h) ...
+  UGeom ug; MdnnGeom mg;       // ... its geometry (linear heads / two-layer MDNN)
+  bool eng_off;                // ... does not run this binding's updates (a streamed first layer bound
+                               // to rows it does not take): the per-phase kernels do -- engine()
   int dp_evals_done;           // data-parallel + in-launch evaluations: bsig_fit_eval calls so far
   bool resident_ran;           // a resident data-parallel call ran since bsig_fit_begin (its workgroup count word is used up)
   bool adam_pending;           // ... data-parallel: the Adam step on the reduced gradients is
                                // taken by the next launch (or flushed before an evaluation)
-  size_t persist_bytes;
   hipStream_t cap_stream;
   hipGraphExec_t g_step, g_grad, g_apply, g_eval;
   bool graphs_ready;           // ensure_graphs has run for this binding (g_eval may legitimately be absent)
@@ -408,7 +408,24 @@ namespace bsig {
 
 static size_t plan_ws_bytes(const bsig_fit_plan* p) {
   return p->train_ws_bytes + p->test_ws_bytes + p->feats_bytes + p->big_gemm_ws_bytes +
-         p->iota_bytes + p->persist_bytes;
+         p->iota_bytes + p->eng.workspace_bytes;
+}
+
+// the persistent engine that runs the bound plan's updates: 0 none (per-phase kernels), 1 linear heads, 2 MDNN
+static int engine(const bsig_fit_plan* p) { return p->eng_off ? 0 : p->eng.kind; }
+
+// Do a call's held-out evaluations run inside the persistent launches?  dp: a data-parallel rank's
+// launches (one per update), else a single rank's call (or a resident data-parallel one).  A streamed
+// first layer evaluates only from the held-out pairs' factor rows (test_factors).  (The plan's engine;
+// whether it runs the bound updates and whether the binding holds held-out rows, the callers ask.)
+static bool evals_in_launch(const bsig_fit_plan* p, bool dp, bool test_factors) {
+  return (dp ? p->eng.eval_dp : p->eng.eval_single) && (!p->eng.streams || test_factors);
+}
+
+// Does a call over n_train training rows keep one projected feature row per training row (the
+// feature cache: the call visits its rows more than once)?
+static bool feat_cache_applies(const bsig_fit_plan* p, int64_t n_train) {
+  return p->hoist && p->feat_cache && n_train <= p->n_updates * p->batch;
 }
 
 struct PlanMem { Scratch tr, te; float* feats; float* big_ws; int32_t* iota; void* persist_ws; };
@@ -417,7 +434,7 @@ struct PlanMem { Scratch tr, te; float* feats; float* big_ws; int32_t* iota; voi
 // moments (2; not where a single-rank persistent plan starts them in registers) -- and, where that
 // leaves room, the combine tickets of the two scratch areas (gemm_wide.h; else: no combine)
 static int begin_regions(const bsig_fit_plan* p) {
-  const bool pers = p->persistent || p->persistent_mdnn;
+  const bool pers = engine(p) != 0;
   return (pers ? 2 : 0) + (!(pers && !p->split_adam) ? 2 : 0);
 }
 static bool tickets_zeroed(const bsig_fit_plan* p) { return begin_regions(p) + 2 <= 4; }
@@ -441,45 +458,6 @@ static PersistShape persist_shape(const bsig_fit_plan* p) {
                       (int)std::min<int64_t>(p->max_test, 1 << 20)};
 }
 
-// n consecutive updates in the persistent kernel.  Data-parallel plans
-// (split_adam): ONE update whose gradients go to the flat gradient buffer, after
-// the pending Adam step of the previous one; n = 0 flushes that step.
-// eval_total > 0: the launch belongs to a call of eval_total updates whose held-out
-// evaluations run inside the launches.
-static int enqueue_persistent(bsig_fit_plan* p, int n, hipStream_t st, int eval_total = 0,
-                              const CommXr* xr = nullptr) {
-  PlanMem m; plan_mem(p, &m);
-  const bsig_fit_buffers& b = p->buf;
-  PersistBuffers pb;
-  pb.feats = m.feats; pb.ld_feats = p->cfg.rff_feats;
-  pb.feat_ids = p->feat_unique ? b.ids_table : nullptr;
-  pb.y = b.y_train; pb.ldy = b.ldy_train; pb.ids = b.ids_table;
-  pb.params = b.params; pb.exp_avg = b.exp_avg; pb.exp_avg_sq = b.exp_avg_sq;
-  pb.w_off = p->L.head_w_off; pb.b_off = p->L.head_b_off;
-  pb.state = b.state; pb.train_loss = b.train_loss;
-  pb.workspace = m.persist_ws; pb.workspace_bytes = p->persist_bytes;
-  if (p->split_adam) {
-    pb.grads = b.grads; pb.adam_pending = p->adam_pending ? 1 : 0;
-    p->adam_pending = false;
-  }
-  if (xr) {      // the whole call in one launch, resident across the exchange (persist.h)
-    pb.xr_ready = xr->ready; pb.xr_done = xr->done; pb.xr_base = xr->base;
-    pb.n_total = n;
-  }
-  if (eval_total > 0) {
-    pb.do_eval = 1; pb.n_total = eval_total; pb.eval_every = std::max(eval_total / 5, 1);   // mdnn.py:235
-    pb.n_test = (int)b.n_test;
-    pb.eval_row0 = p->feat_unique ? b.n_train : p->n_updates * p->batch;  // as eval_inputs()
-    pb.y_test = b.y_test; pb.ldy_test = b.ldy_test; pb.test_loss = b.test_loss;
-  }
-  PersistHyper hy;
-  hy.lr = p->cfg.lr; hy.beta1 = p->cfg.beta1; hy.beta2 = p->cfg.beta2;
-  hy.adam_eps = p->cfg.adam_eps; hy.eps_noise = p->cfg.head.eps_noise;
-  hy.min_weight = p->cfg.head.min_weight; hy.ll_limit = p->cfg.head.ll_limit;
-  hy.norm_batch = p->norm_batch;
-  return persist_run(persist_shape(p), pb, hy, n, st);
-}
-
 static PersistMdnnShape persist_mdnn_shape(const bsig_fit_plan* p) {
   const bsig_mdn_cfg& c = p->cfg;
   return PersistMdnnShape{(int)p->batch, c.input_dim, c.n_hidden > 0 ? c.hidden[0] : 0,
@@ -488,42 +466,53 @@ static PersistMdnnShape persist_mdnn_shape(const bsig_fit_plan* p) {
                           (int)std::min<int64_t>(p->max_test, 1 << 20)};
 }
 
-// n consecutive updates of the two-layer MDNN in its persistent kernel (with_eval: a whole
-// bsig_fit_run call, its held-out evaluations inside the launch)
-static int enqueue_persistent_mdnn(bsig_fit_plan* p, int n, hipStream_t st, int eval_total = 0,
-                                   const CommXr* xr = nullptr) {
+// n consecutive updates in the plan's persistent kernel.  Data-parallel plans (split_adam): ONE
+// update whose gradients go to the flat gradient buffer, after the pending Adam step of the previous
+// one; n = 0 flushes that step.  eval_total > 0: the launch belongs to a call of eval_total updates
+// whose held-out evaluations run inside the launches.  xr: the whole call in one launch, resident
+// across the exchange (persist.h).
+static int enqueue_persistent(bsig_fit_plan* p, int n, hipStream_t st, int eval_total = 0,
+                              const CommXr* xr = nullptr) {
   PlanMem m; plan_mem(p, &m);
   const bsig_fit_buffers& b = p->buf;
+  PersistCommon c;
+  c.y = b.y_train; c.ldy = b.ldy_train; c.ids = b.ids_table;
+  c.params = b.params; c.exp_avg = b.exp_avg; c.exp_avg_sq = b.exp_avg_sq;
+  c.state = b.state; c.train_loss = b.train_loss;
+  c.workspace = m.persist_ws; c.workspace_bytes = p->eng.workspace_bytes;
+  if (p->split_adam) {
+    c.grads = b.grads; c.adam_pending = p->adam_pending ? 1 : 0;
+    p->adam_pending = false;
+  }
+  if (xr) { c.xr_ready = xr->ready; c.xr_done = xr->done; c.xr_base = xr->base; c.n_total = n; }
+  if (eval_total > 0) {
+    c.do_eval = 1; c.n_total = eval_total; c.eval_every = std::max(eval_total / 5, 1);   // mdnn.py:235
+    c.n_test = (int)b.n_test;
+    c.y_test = b.y_test; c.ldy_test = b.ldy_test; c.test_loss = b.test_loss;
+  }
+  c.hy.lr = p->cfg.lr; c.hy.beta1 = p->cfg.beta1; c.hy.beta2 = p->cfg.beta2;
+  c.hy.adam_eps = p->cfg.adam_eps; c.hy.eps_noise = p->cfg.head.eps_noise;
+  c.hy.min_weight = p->cfg.head.min_weight; c.hy.ll_limit = p->cfg.head.ll_limit;
+  c.hy.norm_batch = p->norm_batch;
+  if (engine(p) == 1) {
+    PersistBuffers pb;
+    static_cast<PersistCommon&>(pb) = c;
+    pb.feats = m.feats; pb.ld_feats = p->cfg.rff_feats;
+    pb.feat_ids = p->feat_unique ? b.ids_table : nullptr;
+    pb.w_off = p->L.head_w_off; pb.b_off = p->L.head_b_off;
+    pb.eval_row0 = p->feat_unique ? b.n_train : p->n_updates * p->batch;  // as eval_inputs()
+    return persist_run(persist_shape(p), p->ug, pb, n, st);
+  }
   PersistMdnnBuffers pb;
-  pb.x = b.x_train; pb.ldx = b.ldx_train; pb.ids = b.ids_table;
+  static_cast<PersistCommon&>(pb) = c;
+  pb.x = b.x_train; pb.ldx = b.ldx_train;
   pb.x_kind = b.x_kind; pb.x_s = b.x_s; pb.x_a = b.x_a;
-  pb.y = b.y_train; pb.ldy = b.ldy_train;
-  pb.params = b.params; pb.exp_avg = b.exp_avg; pb.exp_avg_sq = b.exp_avg_sq;
   pb.w1_off = p->L.w_off[0]; pb.b1_off = p->L.b_off[0];
   pb.w2_off = p->L.w_off[1]; pb.b2_off = p->L.b_off[1];
   pb.wh_off = p->L.head_w_off; pb.bh_off = p->L.head_b_off;
-  pb.state = b.state; pb.train_loss = b.train_loss;
-  pb.workspace = m.persist_ws; pb.workspace_bytes = p->persist_bytes;
-  if (p->split_adam) {
-    pb.grads = b.grads; pb.adam_pending = p->adam_pending ? 1 : 0;
-    p->adam_pending = false;
-  }
-  if (xr) {      // the whole call in one launch, resident across the exchange (persist_mdnn.h)
-    pb.xr_ready = xr->ready; pb.xr_done = xr->done; pb.xr_base = xr->base;
-  }
-  if (eval_total > 0) {
-    pb.do_eval = 1; pb.n_total = eval_total; pb.eval_every = std::max(eval_total / 5, 1);   // mdnn.py:235
-    pb.n_test = (int)b.n_test;
-    pb.x_test = b.x_test; pb.ldx_test = b.ldx_test; pb.y_test = b.y_test; pb.ldy_test = b.ldy_test;
-    pb.test_loss = b.test_loss;
-    pb.x_test_fac = b.x_test_factors; pb.ldx_test_fac = b.ldx_test_factors;
-  }
-  PersistHyper hy;
-  hy.lr = p->cfg.lr; hy.beta1 = p->cfg.beta1; hy.beta2 = p->cfg.beta2;
-  hy.adam_eps = p->cfg.adam_eps; hy.eps_noise = p->cfg.head.eps_noise;
-  hy.min_weight = p->cfg.head.min_weight; hy.ll_limit = p->cfg.head.ll_limit;
-  hy.norm_batch = p->norm_batch;
-  return persist_mdnn_run(persist_mdnn_shape(p), pb, hy, n, st);
+  pb.x_test = b.x_test; pb.ldx_test = b.ldx_test;
+  pb.x_test_fac = b.x_test_factors; pb.ldx_test_fac = b.ldx_test_factors;
+  return persist_mdnn_run(persist_mdnn_shape(p), p->mg, pb, n, st);
 }
 
 static Inputs train_inputs(const bsig_fit_plan* p, const PlanMem& m) {
@@ -628,7 +617,7 @@ static int enqueue_hoisted_rff(bsig_fit_plan* p, hipStream_t st) {
   // the chunk): ONE projection over all of them -- a 1000-pair chunk is 16 x 32 tiles of 64 x 64 =
   // 512 workgroups, two per CU, where 800 + 200 rows were 416 + 128 in two launches
   if (p->feat_unique && b.n_test > 0 && b.ldx_test == b.ldx_train &&
-      b.x_test == b.x_train + (size_t)b.n_train * b.ldx_train && getenv("BSIG_RFF_SPLIT_LAUNCH") == nullptr)
+      b.x_test == b.x_train + (size_t)b.n_train * b.ldx_train)
     return rff_project(&p->cfg, in, train_rows + b.n_test, m.feats, m.big_ws, p->big_gemm_ws_bytes, st);
   BSIG_TRY(rff_project(&p->cfg, in, train_rows, m.feats, m.big_ws, p->big_gemm_ws_bytes, st));
   if (b.n_test > 0) {
@@ -669,11 +658,11 @@ static int ensure_graphs(bsig_fit_plan* p) {
   if (!p->use_graph || p->graphs_ready) return BSIG_OK;
   p->graph_feats = fm.feats;
   if (p->split_adam) {
-    if (!p->persistent && !p->persistent_mdnn) {
+    if (!engine(p)) {
       BSIG_TRY(capture(p, &p->g_grad, [&](hipStream_t s) { return enqueue_grad(p, s, false); }));
       BSIG_TRY(capture(p, &p->g_apply, [&](hipStream_t s) { return enqueue_apply(p, s); }));
     }
-  } else if (p->persistent || p->persistent_mdnn) {
+  } else if (engine(p)) {
     // updates are single launches of a persistent kernel: no update graph
   } else {
     BSIG_TRY(capture(p, &p->g_step, [&](hipStream_t s) { return enqueue_grad(p, s, true); }));
@@ -803,27 +792,23 @@ extern "C" int bsig_fit_create_ex(const bsig_mdn_cfg* cfg, int64_t batch,
   // MDRFF feature block: one row per gathered minibatch row, or -- when the caller bounds the
   // training rows and they are fewer -- one per distinct training row (feature cache)
   p->max_train = max_train_rows;
-  const char* no_cache_env = getenv("BSIG_NO_FEAT_CACHE");   // diagnostics: every gathered row projected
-  if (no_cache_env && no_cache_env[0] == '1') max_train_rows = 0;
+  // the plan's switches (diagnostics, A/B runs), read here once
+  const auto set = [](const char* name) { const char* e = getenv(name); return e && e[0] == '1'; };
+  p->feat_cache = !set("BSIG_NO_FEAT_CACHE");   // (set: every gathered row projected)
+  if (!p->feat_cache) max_train_rows = 0;
   p->feat_rows = (max_train_rows > 0 ? std::min(n_updates * batch, max_train_rows)
                                      : n_updates * batch) + max_test_rows;
   const size_t feats = (size_t)p->feat_rows * (size_t)std::max(cfg->rff_feats, 0) * sizeof(float);
-  const char* no_hoist = getenv("BSIG_NO_RFF_HOIST");
-  p->hoist = cfg->rff_feats > 0 && n_updates > 0 && feats <= ((size_t)4 << 30) &&
-             !(no_hoist && no_hoist[0] == '1');
-  const char* no_persist_env = getenv("BSIG_NO_PERSISTENT");
-  const char* no_persist = (plan_flags & BSIG_PLAN_NO_PERSISTENT) ? "1" : no_persist_env;
-  p->persistent = p->hoist && p->L.n_layers == 0 && cfg->head.full_cov == 0 &&
-                  !(no_persist && no_persist[0] == '1') && persist_supported(persist_shape(p));
-  if (p->persistent)
-    p->persist_bytes = round_up<size_t>(persist_workspace_bytes(persist_shape(p)), 256);
-  p->persistent_mdnn = cfg->rff_feats == 0 && p->L.n_layers == 2 && n_updates > 0 &&
-                       !(no_persist && no_persist[0] == '1') &&
-                       persist_mdnn_supported(persist_mdnn_shape(p));
-  p->persistent_mdnn_cap = p->persistent_mdnn;
-  p->mdnn_streams = p->persistent_mdnn && persist_mdnn_streams(persist_mdnn_shape(p)) != 0;
-  if (p->persistent_mdnn)
-    p->persist_bytes = round_up<size_t>(persist_mdnn_workspace_bytes(persist_mdnn_shape(p)), 256);
+  p->hoist = cfg->rff_feats > 0 && n_updates > 0 && feats <= ((size_t)4 << 30) && !set("BSIG_NO_RFF_HOIST");
+  // the persistent update engine: resolved once, here (a streamed first layer: completed at bind)
+  if (!((plan_flags & BSIG_PLAN_NO_PERSISTENT) || set("BSIG_NO_PERSISTENT"))) {
+    if (p->hoist && p->L.n_layers == 0 && cfg->head.full_cov == 0)
+      persist_resolve(persist_shape(p), &p->ug, &p->eng);
+    else if (cfg->rff_feats == 0 && p->L.n_layers == 2 && n_updates > 0)
+      persist_mdnn_resolve(persist_mdnn_shape(p), &p->mg, &p->eng);
+  }
+  if (set("BSIG_NO_INKERNEL_EVAL")) p->eng.eval_single = p->eng.eval_dp = false;
+  p->eng.workspace_bytes = round_up<size_t>(p->eng.workspace_bytes, 256);
   if (p->hoist) {
     p->feats_bytes = round_up<size_t>(feats, 256);
     const int64_t mf = cfg->rff_cos_only ? cfg->rff_feats : cfg->rff_feats / 2;
@@ -862,11 +847,15 @@ extern "C" int bsig_fit_bind(bsig_fit_plan* p, const bsig_fit_buffers* b, int fl
                (long long)b->n_test, (long long)p->max_test);
   const bool fac = b->x_kind == BSIG_X_CROSSCORR_FACTORS;
   BSIG_REQUIRE(b->x_kind == BSIG_X_ROWS || fac, "fit_bind: unknown x_kind %d", b->x_kind);
+  const bool graph = (flags & BSIG_FIT_GRAPH) != 0, split = (flags & BSIG_FIT_SPLIT_ADAM) != 0;
   // a streamed first layer exists for factor rows only: summary rows of that width go through
   // the per-phase kernels
-  const bool mdnn_now = p->persistent_mdnn_cap &&
-                        (!p->mdnn_streams || (fac && persist_mdnn_accepts_factors(persist_mdnn_shape(p), b->x_s, b->x_a)));
-  if (mdnn_now != p->persistent_mdnn) { drop_graphs(p); p->persistent_mdnn = mdnn_now; p->bound = false; }
+  const bool eng_off = p->eng.streams && !(fac && bsig_fit_accepts_factor_rows(p, b->x_s, b->x_a));
+  if (eng_off != p->eng_off) { drop_graphs(p); p->eng_off = eng_off; p->bound = false; }
+  // ... and the launch of the streamed tile workgroups takes these factor dimensions
+  const MdnnGeom& g = p->mg;
+  if (engine(p) == 2 && p->eng.streams && !(g.s_S == b->x_s && g.s_A == b->x_a && g.s_dp == (split ? 1 : 0)))
+    BSIG_TRY(persist_mdnn_resolve_stream(&p->mg, p->cfg.input_dim, p->cfg.head.full_cov != 0, b->x_s, b->x_a, split));
   if (fac) {
     BSIG_REQUIRE(b->x_s >= 1 && b->x_a >= 1 && (int64_t)b->x_s * b->x_a + 2 == p->cfg.input_dim,
                  "fit_bind: factor rows S=%d A=%d do not give the %d inputs of the first layer",
@@ -888,15 +877,12 @@ extern "C" int bsig_fit_bind(bsig_fit_plan* p, const bsig_fit_buffers* b, int fl
   BSIG_REQUIRE(!(b->n_test > 0 && !b->x_test &&
                  !(fac && b->x_test_factors && bsig_fit_evaluates_from_factors(p, b->x_s, b->x_a, flags))),
                "fit_bind: null test buffers");
-  const bool graph = (flags & BSIG_FIT_GRAPH) != 0, split = (flags & BSIG_FIT_SPLIT_ADAM) != 0;
   const bool same = p->bound && std::memcmp(&p->buf, b, sizeof(*b)) == 0 &&
                     p->use_graph == graph && p->split_adam == split;
   if (!same) {
     drop_graphs(p);
     p->buf = *b;
-    const char* no_cache = getenv("BSIG_NO_FEAT_CACHE");
-    p->feat_unique = p->hoist && b->n_train <= p->n_updates * p->batch &&
-                     !(no_cache && no_cache[0] == '1');
+    p->feat_unique = feat_cache_applies(p, b->n_train);
     if (p->hoist && !p->feat_unique && p->feat_rows - p->max_test < p->n_updates * p->batch) {
       p->bound = false;
       set_error("fit_bind: %lld training rows exceed the %lld the plan was sized for",
@@ -916,10 +902,9 @@ extern "C" int bsig_fit_bind(bsig_fit_plan* p, const bsig_fit_buffers* b, int fl
 // at the workspace address the graphs were captured with: a caller's block is copied there.)
 static bool graphs_read_feats(const bsig_fit_plan* p) {
   if (!p->use_graph) return false;       // direct launches take the pointer of the call
-  if (!p->persistent) return true;       // update and evaluation graphs
-  if (p->buf.n_test < 1 || p->n_updates < 1) return false;
-  const char* no_ike = getenv("BSIG_NO_INKERNEL_EVAL");
-  return (no_ike && no_ike[0] == '1') || !persist_eval_supported(persist_shape(p));
+  if (engine(p) != 1) return true;       // update and evaluation graphs
+  if (p->buf.n_test < 1) return false;
+  return !evals_in_launch(p, p->split_adam, false);
 }
 
 extern "C" int bsig_fit_set_features(bsig_fit_plan* p, const float* feats, int64_t ld_feats,
@@ -963,11 +948,11 @@ extern "C" int bsig_fit_begin(bsig_fit_plan* p, uint64_t seed, int64_t norm_batc
     total4 += bz.n4[nz];
     ++nz;
   };
-  if (p->persistent || p->persistent_mdnn) {
+  if (engine(p)) {
     PlanMem m; plan_mem(p, &m);
     ZeroRegion zr[2];
-    if (p->persistent) BSIG_TRY(persist_reset_regions(persist_shape(p), m.persist_ws, p->persist_bytes, zr));
-    else BSIG_TRY(persist_mdnn_reset_regions(persist_mdnn_shape(p), m.persist_ws, p->persist_bytes, zr));
+    if (engine(p) == 1) BSIG_TRY(persist_reset_regions(p->ug, m.persist_ws, p->eng.workspace_bytes, zr));
+    else BSIG_TRY(persist_mdnn_reset_regions(p->mg, m.persist_ws, p->eng.workspace_bytes, zr));
     BSIG_REQUIRE(aligned(zr[0].ptr, 16) && aligned(zr[1].ptr, 16) && zr[0].bytes % 16 == 0 &&
                  zr[1].bytes % 16 == 0, "fit_begin: persistent workspace regions must be 16-byte multiples");
     add_zero(zr[0].ptr, zr[0].bytes);
@@ -975,7 +960,7 @@ extern "C" int bsig_fit_begin(bsig_fit_plan* p, uint64_t seed, int64_t norm_batc
   }
   // fresh optimizer state for every run_training call (mdnn.py:203); a single-rank plan in a
   // persistent kernel starts the moments at zero in its registers instead
-  if (!((p->persistent || p->persistent_mdnn) && !p->split_adam)) {
+  if (!(engine(p) && !p->split_adam)) {
     BSIG_REQUIRE(aligned(p->buf.exp_avg, 16) && aligned(p->buf.exp_avg_sq, 16),
                  "fit_begin: the Adam moment buffers must be 16-byte aligned");
     add_zero(p->buf.exp_avg, (size_t)p->L.total * sizeof(float));
@@ -1001,21 +986,14 @@ extern "C" int bsig_fit_begin(bsig_fit_plan* p, uint64_t seed, int64_t norm_batc
 
 // data-parallel plans covered by a persistent kernel: the held-out evaluations run inside
 // the per-update launches too (the one after the last update in the launch that takes its
-// pending Adam step)
+// pending Adam step; a rank of a streamed first layer or of wide heads evaluates between its launches)
 static int dp_eval_total(const bsig_fit_plan* p) {
-  const char* no_ike = getenv("BSIG_NO_INKERNEL_EVAL");
-  if (!p->split_adam || p->buf.n_test < 1 || p->n_updates < 1 || (no_ike && no_ike[0] == '1')) return 0;
-  if (p->persistent && persist_eval_supported(persist_shape(p))) return (int)p->n_updates;
-  // (a data-parallel rank of a streamed first layer or of wide heads evaluates between its launches)
-  if (p->persistent_mdnn && persist_mdnn_dp_eval_supported(persist_mdnn_shape(p)))
-    return (int)p->n_updates;
-  return 0;
+  return engine(p) && p->split_adam && p->buf.n_test >= 1 && evals_in_launch(p, true, false) ? (int)p->n_updates : 0;
 }
 
 extern "C" int bsig_fit_grad(bsig_fit_plan* p, bsig_stream_t stream) {
   BSIG_REQUIRE(p && p->bound && p->split_adam, "fit_grad: plan not bound with SPLIT_ADAM");
-  if (p->persistent) return enqueue_persistent(p, 1, as_stream(stream), dp_eval_total(p));
-  if (p->persistent_mdnn) return enqueue_persistent_mdnn(p, 1, as_stream(stream), dp_eval_total(p));
+  if (engine(p)) return enqueue_persistent(p, 1, as_stream(stream), dp_eval_total(p));
   if (p->use_graph) { BSIG_TRY(ensure_graphs(p)); BSIG_HIP(hipGraphLaunch(p->g_grad, as_stream(stream))); return BSIG_OK; }
   return enqueue_grad(p, as_stream(stream), false);
 }
@@ -1024,9 +1002,9 @@ extern "C" int bsig_fit_apply(bsig_fit_plan* p, bsig_stream_t stream) {
   BSIG_REQUIRE(p && p->bound && p->split_adam, "fit_apply: plan not bound with SPLIT_ADAM");
   // persistent kernel: the step is taken by the next bsig_fit_grad launch while it
   // loads its tiles (bsig_fit_eval / bsig_fit_flush take it at once)
-  if (p->persistent || (p->persistent_mdnn && !p->mdnn_streams)) { p->adam_pending = true; return BSIG_OK; }
+  if (engine(p) && !p->eng.streams) { p->adam_pending = true; return BSIG_OK; }
   // (a streamed first layer: the flat Adam kernel, with the step sizes the launch left in the state block)
-  if (p->persistent_mdnn) return enqueue_apply(p, as_stream(stream));
+  if (engine(p)) return enqueue_apply(p, as_stream(stream));
   if (p->use_graph) { BSIG_TRY(ensure_graphs(p)); BSIG_HIP(hipGraphLaunch(p->g_apply, as_stream(stream))); return BSIG_OK; }
   return enqueue_apply(p, as_stream(stream));
 }
@@ -1034,25 +1012,22 @@ extern "C" int bsig_fit_apply(bsig_fit_plan* p, bsig_stream_t stream) {
 extern "C" int bsig_fit_takes_features(const bsig_fit_plan* p, int64_t n_train) {
   // a hoisted MDRFF plan keeps one feature row per training row when the call visits its rows
   // more than once: bsig_fit_set_features then replaces the projection and nothing reads
-  // x_train / x_test afterwards (same condition as feat_unique in bsig_fit_bind)
-  const char* no_cache = getenv("BSIG_NO_FEAT_CACHE");
-  return p && p->hoist && n_train >= 1 && n_train <= p->n_updates * p->batch &&
-                 !(no_cache && no_cache[0] == '1') ? 1 : 0;
+  // x_train / x_test afterwards (feat_unique in bsig_fit_bind)
+  return p && n_train >= 1 && feat_cache_applies(p, n_train) ? 1 : 0;
 }
 
 extern "C" int bsig_fit_accepts_factors(const bsig_fit_plan* p) {
   // every update runs in the persistent kernel of the two-layer MDNN, whose first-layer tile
   // workgroups form the products; the evaluations read materialised held-out rows
   // (a plan with a streamed first layer: only through bsig_fit_accepts_factor_rows, which sees S and A)
-  return p && p->persistent_mdnn_cap && !p->mdnn_streams && p->n_updates >= 1 ? 1 : 0;
+  return p && p->eng.kind == 2 && !p->eng.streams ? 1 : 0;
 }
 
 extern "C" int bsig_fit_accepts_factor_rows(const bsig_fit_plan* p, int s_dim, int a_dim) {
   // ... for these factor dimensions: a plan whose first layer is STREAMED (it does not fit the
   // chip: cfg/anymal.yaml, cfg/shadow_hand_more.yaml) covers A % 4 == 0 and factor rows of two
   // minibatches in a workgroup's LDS
-  return p && p->persistent_mdnn_cap && p->n_updates >= 1 &&
-                 persist_mdnn_accepts_factors(persist_mdnn_shape(p), s_dim, a_dim) ? 1 : 0;
+  return p && p->eng.kind == 2 && persist_mdnn_factors_fit(p->mg, p->cfg.input_dim, s_dim, a_dim) ? 1 : 0;
 }
 
 // Would a call bound with these factor rows and bind flags evaluate its held-out pairs from their
@@ -1060,26 +1035,19 @@ extern "C" int bsig_fit_accepts_factor_rows(const bsig_fit_plan* p, int s_dim, i
 // materialised held-out summary rows and the caller need not build them (bsig_fit_buffers.x_test
 // may be null).
 extern "C" int bsig_fit_evaluates_from_factors(const bsig_fit_plan* p, int s_dim, int a_dim, int bind_flags) {
-  if (!p || !p->persistent_mdnn_cap || !p->mdnn_streams || p->n_updates < 1) return 0;
-  if (bind_flags & BSIG_FIT_SPLIT_ADAM) return 0;      // a data-parallel rank evaluates between its launches
-  const char* no_ike = getenv("BSIG_NO_INKERNEL_EVAL");
-  if (no_ike && no_ike[0] == '1') return 0;
-  return persist_mdnn_accepts_factors(persist_mdnn_shape(p), s_dim, a_dim) &&
-                 persist_mdnn_eval_supported(persist_mdnn_shape(p)) ? 1 : 0;
+  // (a data-parallel rank evaluates between its launches)
+  return p && p->eng.streams && bsig_fit_accepts_factor_rows(p, s_dim, a_dim) &&
+                 evals_in_launch(p, (bind_flags & BSIG_FIT_SPLIT_ADAM) != 0, true) ? 1 : 0;
 }
 
 extern "C" int bsig_fit_is_persistent(const bsig_fit_plan* p) {
-  if (!p) return 0;
-  if (p->persistent) return 1;
-  return p->persistent_mdnn ? 2 : 0;
+  return p ? engine(p) : 0;
 }
 
 extern "C" int bsig_fit_flush(bsig_fit_plan* p, bsig_stream_t stream) {
   BSIG_REQUIRE(p && p->bound, "fit_flush: plan not bound");
-  if (p->persistent && p->split_adam && p->adam_pending)
+  if (engine(p) && p->split_adam && p->adam_pending)
     return enqueue_persistent(p, 0, as_stream(stream));
-  if (p->persistent_mdnn && p->split_adam && p->adam_pending)
-    return enqueue_persistent_mdnn(p, 0, as_stream(stream));
   return BSIG_OK;
 }
 
@@ -1089,8 +1057,7 @@ extern "C" int bsig_fit_eval(bsig_fit_plan* p, bsig_stream_t stream) {
   if (const int total = dp_eval_total(p)) {
     // evaluations inside the launches: all but the last are already under way
     if (++p->dp_evals_done < count_evals(total)) return BSIG_OK;
-    return p->persistent ? enqueue_persistent(p, 0, as_stream(stream), total)
-                         : enqueue_persistent_mdnn(p, 0, as_stream(stream), total);
+    return enqueue_persistent(p, 0, as_stream(stream), total);
   }
   BSIG_REQUIRE(p->buf.n_test < 1 || p->buf.x_test,
                "fit_eval: this binding has no held-out summary rows (its evaluations run inside bsig_fit_run)");
@@ -1103,13 +1070,11 @@ extern "C" int bsig_fit_eval(bsig_fit_plan* p, bsig_stream_t stream) {
 // the plan is covered by it, else n replays of the update graph
 static int enqueue_updates(bsig_fit_plan* p, int64_t n, hipStream_t st) {
   if (n <= 0) return BSIG_OK;
-  if (p->persistent && !p->split_adam) return enqueue_persistent(p, (int)n, st);
-  if (p->persistent_mdnn && !p->split_adam) return enqueue_persistent_mdnn(p, (int)n, st);
-  if (p->persistent || p->persistent_mdnn) {   // data-parallel plan driven without an exchange (one rank)
+  if (engine(p) && !p->split_adam) return enqueue_persistent(p, (int)n, st);
+  if (engine(p)) {   // data-parallel plan driven without an exchange (one rank)
     for (int64_t it = 0; it < n; ++it) {
-      BSIG_TRY(p->persistent ? enqueue_persistent(p, 1, st, dp_eval_total(p))
-                             : enqueue_persistent_mdnn(p, 1, st, dp_eval_total(p)));
-      if (p->persistent_mdnn && p->mdnn_streams) BSIG_TRY(enqueue_apply(p, st));
+      BSIG_TRY(enqueue_persistent(p, 1, st, dp_eval_total(p)));
+      if (p->eng.streams) BSIG_TRY(enqueue_apply(p, st));
       else p->adam_pending = true;
     }
     return BSIG_OK;
@@ -1149,15 +1114,9 @@ extern "C" int bsig_fit_run(bsig_fit_plan* p, int64_t n_updates, bsig_stream_t s
   hipStream_t st = as_stream(stream);
   if (p->use_graph) BSIG_TRY(ensure_graphs(p));
   // plans covered by a persistent kernel: the whole call, evaluations included, is ONE launch
-  const char* no_ike = getenv("BSIG_NO_INKERNEL_EVAL");
-  if (p->persistent && !p->split_adam && n_updates >= 1 && p->buf.n_test >= 1 &&
-      !(no_ike && no_ike[0] == '1') && persist_eval_supported(persist_shape(p)))
+  if (engine(p) && !p->split_adam && n_updates >= 1 && p->buf.n_test >= 1 &&
+      evals_in_launch(p, false, p->buf.x_test_factors != nullptr))
     return enqueue_persistent(p, (int)n_updates, st, (int)n_updates);
-  // (a streamed first layer evaluates in the launch only from the held-out pairs' factor rows)
-  if (p->persistent_mdnn && !p->split_adam && n_updates >= 1 && p->buf.n_test >= 1 &&
-      !(no_ike && no_ike[0] == '1') && persist_mdnn_eval_supported(persist_mdnn_shape(p)) &&
-      (!p->mdnn_streams || p->buf.x_test_factors))
-    return enqueue_persistent_mdnn(p, (int)n_updates, st, (int)n_updates);
   const int64_t every = std::max<int64_t>(n_updates / 5, 1);   // mdnn.py:235
   int64_t done = 0;
   for (int64_t it = 0; it < n_updates; ++it) {
@@ -1250,7 +1209,7 @@ static int ensure_dp_graph(bsig_fit_plan* p, bsig_comm* comm) {
   if (p->g_dp) { (void)hipGraphExecDestroy(p->g_dp); p->g_dp = nullptr; }
   p->g_dp_comm = comm; p->g_dp_error[0] = 0;
   const char* env = getenv("BSIG_DP_GRAPH");
-  if (!p->use_graph || !p->persistent || bsig_comm_transport(comm) != 1 || !(env && env[0] == '1')) {
+  if (!p->use_graph || engine(p) != 1 || bsig_comm_transport(comm) != 1 || !(env && env[0] == '1')) {
     p->g_dp_state = -2;
     snprintf(p->g_dp_error, sizeof(p->g_dp_error), "%s",
              !(env && env[0] == '1') ? "not requested (BSIG_DP_GRAPH=1)" :
@@ -1313,45 +1272,36 @@ static bool dp_resident_applies(const bsig_fit_plan* p, const bsig_comm* comm, i
     told = true;
     want = false;
   }
-  const char* no_ike = getenv("BSIG_NO_INKERNEL_EVAL");
-  if (!(want && bsig_comm_transport(comm) == 1 && n_updates >= 1 && n_updates == p->n_updates && !p->adam_pending &&
-        p->buf.n_test >= 1 && !(no_ike && no_ike[0] == '1')))
-    return false;
-  if (p->persistent)
-    return p->buf.x_kind == BSIG_X_ROWS && persist_variant(persist_shape(p)) == 2 && persist_eval_supported(persist_shape(p));
-  // the two-layer MDNN with its first layer resident on the chip (not the streamed kernel)
-  return p->persistent_mdnn && !p->mdnn_streams && persist_mdnn_eval_supported(persist_mdnn_shape(p));
+  // (the two-layer MDNN: with its first layer resident on the chip -- a streamed one takes factor
+  // rows, whose held-out pairs a resident launch does not evaluate)
+  return want && bsig_comm_transport(comm) == 1 && n_updates >= 1 && n_updates == p->n_updates && !p->adam_pending &&
+         engine(p) && p->buf.n_test >= 1 && evals_in_launch(p, false, false) &&
+         (engine(p) != 1 || p->buf.x_kind == BSIG_X_ROWS);
 }
 
 static int run_dp_resident(bsig_fit_plan* p, bsig_comm* comm, int64_t n_updates, hipStream_t st) {
   const auto t0_host = std::chrono::steady_clock::now();
   CommXr xr;
   BSIG_TRY(comm_xr(comm, st, &xr));
-  // At most `depth` calls in flight on the exchange stream (BSIG_DP_XR_DEPTH, 0: no limit): the host
-  // waits for the end of call c - depth before it enqueues the exchange of call c (the launch of call c
-  // is in `st` by then, the GPU does not idle).  1: with 3 calls or more of stream operations
-  // outstanding, calls timed out once ~65 000 operations had gone through the stream (always around
-  // the 210th call of a process; depth 1 and 2 ran 400+ calls clean, same speed).
-  static const int depth = [] { const char* e = getenv("BSIG_DP_XR_DEPTH"); return e ? std::min(std::max(atoi(e), 0), CommXr::kRing - 1) : 1; }();
+  // At most `depth` calls in flight on the exchange stream: the host waits for the end of call c - depth
+  // before it enqueues the exchange of call c (the launch of call c is in `st` by then, the GPU does not
+  // idle).  1: with 3 calls or more of stream operations outstanding, calls timed out once ~65 000
+  // operations had gone through the stream (always around the 210th call of a process; depth 1 and 2
+  // ran 400+ calls clean, same speed).
+  constexpr int depth = 1;
   const int slot = (int)(xr.calls % CommXr::kRing);
   BSIG_HIP(hipEventRecord(xr.ev_begin[slot], st));
   BSIG_HIP(hipStreamWaitEvent(xr.stream, xr.ev_begin[slot], 0));
-  if (p->persistent) BSIG_TRY(enqueue_persistent(p, (int)n_updates, st, (int)n_updates, &xr));
-  else BSIG_TRY(enqueue_persistent_mdnn(p, (int)n_updates, st, (int)n_updates, &xr));
-  if (depth > 0 && xr.calls >= depth)
+  BSIG_TRY(enqueue_persistent(p, (int)n_updates, st, (int)n_updates, &xr));
+  if (xr.calls >= depth)
     BSIG_HIP(hipEventSynchronize(xr.ev_end[(int)((xr.calls - depth) % CommXr::kRing)]));
-  // (diagnostics, 1-rank groups only: BSIG_DP_XR_NO_COLLECTIVE=1 leaves the -- identity -- all-reduce
-  // out, which isolates the hand-off from the collective's kernels on the 8 free CUs)
-  const char* nc = getenv("BSIG_DP_XR_NO_COLLECTIVE");
-  const bool skip = nc && nc[0] == '1' && bsig_comm_world(comm) == 1;
   // (tests: BSIG_DP_XR_DROP_CALL=k leaves the k-th resident call of the communicator, 0-based, without
   // its exchange -- the launch's bounded polls give up, as when the exchange stream is not served)
   const char* drop = getenv("BSIG_DP_XR_DROP_CALL");
   const bool dropped = drop && atoll(drop) == xr.calls;
   for (int64_t u = 1; u <= (dropped ? 0 : n_updates); ++u) {
     BSIG_HIP(hipStreamWaitValue32(xr.stream, xr.ready, xr.base + (uint32_t)u, hipStreamWaitValueGte, 0xFFFFFFFFu));
-    if (!skip)
-      BSIG_TRY(allreduce_grads(p, comm, reinterpret_cast<bsig_stream_t>(xr.stream)));
+    BSIG_TRY(allreduce_grads(p, comm, reinterpret_cast<bsig_stream_t>(xr.stream)));
     BSIG_HIP(hipStreamWriteValue32(xr.stream, xr.done, xr.base + (uint32_t)u, 0));
   }
   BSIG_HIP(hipEventRecord(xr.ev_end[slot], xr.stream));
@@ -1485,7 +1435,9 @@ extern "C" int bsig_debug_persist_geometry(int batch, int feat_dim, int out_dim,
   if (!out) return 0;
   const PersistShape s{batch, feat_dim, out_dim, n_comp, max_test};
   const int rc = persist_geometry(s, out);
-  // which kernel a launch of this shape would really be (asks the device; 0 / 1 where there is none)
-  out[13] = persist_variant(s);
+  // which kernel a launch of this shape would really be (asks the device; 0 where there is none)
+  UGeom g;
+  PersistEngine e;
+  out[13] = persist_resolve(s, &g, &e) ? 2 : 0;
   return rc;
 }

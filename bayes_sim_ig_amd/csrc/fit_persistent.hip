@@ -1509,13 +1509,6 @@ void persist_set_profile_buffer(void* buf) { g_prof = reinterpret_cast<long long
 void* persist_profile_buffer() { return g_prof; }
 
 // ---------------------------------------------------------------- host side
-struct UGeom {
-  int NT, Bp, MT, FP, KS, ksteps, KB, WP, Nh, NhP, n_blocks, k_slices, G, T, n_owner, R;
-  int per_wave, xs_floats;
-  int eval_passes, NE, RE;      // eval_passes 0: evaluations stay outside the launches
-  size_t lds, slab_floats, dout_floats, eval_floats;
-};
-
 // One candidate tiling (NT 16-row blocks per tile, k-slices of KS columns) -> geometry and a
 // cost estimate (us per update, relative).
 static bool u_geom_try(const PersistShape& s, int NT, int KS, UGeom* g, double* cost) {
@@ -1619,6 +1612,18 @@ int persist_geometry(const PersistShape& s, int32_t* out) {
   return 1;
 }
 
+// the > 64 KB dynamic-LDS limit of every instantiation this file launches
+static int u_allow_dynamic_lds() {
+  static bool done[64] = {};
+  const void* kernels[6] = {reinterpret_cast<const void*>(linear_head_updates_kernel<false, 1>),
+                            reinterpret_cast<const void*>(linear_head_updates_kernel<false, 2>),
+                            reinterpret_cast<const void*>(linear_head_updates_kernel<true, 1>),
+                            reinterpret_cast<const void*>(linear_head_updates_kernel<false, 1, true>),
+                            reinterpret_cast<const void*>(linear_head_updates_kernel<true, 2>),
+                            reinterpret_cast<const void*>(linear_head_updates_kernel<false, 2, true>)};
+  return allow_dynamic_lds(done, kernels, 6, kULds);
+}
+
 template <int NT>
 static bool u_can_host(const UGeom& g) {
   int dev = 0;
@@ -1628,43 +1633,10 @@ static bool u_can_host(const UGeom& g) {
   // every workgroup of the launch must be resident at once (they wait for each other): the
   // runtime's own occupancy answer for this kernel at this LDS size must admit a workgroup per CU
   int per_cu = 0;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(linear_head_updates_kernel<false, NT>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, kULds) != hipSuccess ||
+  if (u_allow_dynamic_lds() != BSIG_OK ||
       hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, linear_head_updates_kernel<false, NT>, kUT, g.lds) != hipSuccess)
     return false;
   return per_cu >= 1;
-}
-static bool u_device_can_host(const UGeom& g) { return g.NT == 1 ? u_can_host<1>(g) : u_can_host<2>(g); }
-
-// (asked on every launch: the answers -- a device query each -- are kept per shape and device)
-int persist_variant(const PersistShape& s) {
-  struct Key { int dev, batch, feat_dim, out_dim, n_comp, max_test, variant; };
-  static thread_local Key cache[8];
-  static thread_local int n_cache = 0, next = 0;
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-  for (int i = 0; i < n_cache; ++i) {
-    const Key& k = cache[i];
-    if (k.dev == dev && k.batch == s.batch && k.feat_dim == s.feat_dim && k.out_dim == s.out_dim &&
-        k.n_comp == s.n_comp && k.max_test == s.max_test)
-      return k.variant;
-  }
-  UGeom g;
-  int v = 0;
-  // (2: this file's unified workgroups; 0: the per-phase kernels.  1 was fit_persistent_v1.hip -- the
-  // round-1..3 decomposition, no shipped configuration reached it, retired in round 6)
-  if (u_geom(s, &g) && u_device_can_host(g)) v = 2;
-  cache[next] = Key{dev, s.batch, s.feat_dim, s.out_dim, s.n_comp, s.max_test, v};
-  next = (next + 1) % 8;
-  n_cache = std::min(n_cache + 1, 8);
-  return v;
-}
-
-bool persist_supported(const PersistShape& s) { return persist_variant(s) != 0; }
-bool persist_eval_supported(const PersistShape& s) {
-  const int v = persist_variant(s);
-  UGeom g;
-  return v == 2 && u_geom(s, &g) && g.eval_passes > 0;
 }
 
 static size_t u_data_bytes(const UGeom& g) {
@@ -1673,18 +1645,20 @@ static size_t u_data_bytes(const UGeom& g) {
 // flags, granules and (last 256 bytes) the word the tile workgroups of a resident rank count themselves in
 static size_t u_sync_bytes() { return 2 * kFlagArr * sizeof(unsigned) + (6 + 16) * kGranArr * 8 + 256; }
 
-size_t persist_workspace_bytes(const PersistShape& s) {
-  const int v = persist_variant(s);
-  UGeom g;
-  if (v != 2 || !u_geom(s, &g)) return 0;
-  return u_data_bytes(g) + u_sync_bytes();
+// (the unified workgroups of this file; shapes they cannot host run the per-phase kernels -- the
+// round-1..3 decomposition fit_persistent_v1.hip was retired in round 6)
+bool persist_resolve(const PersistShape& s, UGeom* g, PersistEngine* e) {
+  UGeom c;
+  if (!u_geom(s, &c) || !(c.NT == 1 ? u_can_host<1>(c) : u_can_host<2>(c))) return false;
+  *g = c;
+  e->kind = 1; e->streams = false;
+  e->eval_single = e->eval_dp = c.eval_passes > 0;
+  e->workspace_bytes = u_data_bytes(c) + u_sync_bytes();
+  return true;
 }
 
-int persist_reset_regions(const PersistShape& s, void* workspace, size_t workspace_bytes,
-                          ZeroRegion* regions) {
-  UGeom g;
-  BSIG_REQUIRE(u_geom(s, &g), "persistent updates: shape not covered");
-  BSIG_REQUIRE(workspace && workspace_bytes >= persist_workspace_bytes(s),
+int persist_reset_regions(const UGeom& g, void* workspace, size_t workspace_bytes, ZeroRegion* regions) {
+  BSIG_REQUIRE(workspace && workspace_bytes >= u_data_bytes(g) + u_sync_bytes(),
                "persistent updates: workspace too small");
   char* base = reinterpret_cast<char*>(workspace);
   const size_t slab_bytes = g.slab_floats * sizeof(float);
@@ -1696,21 +1670,6 @@ int persist_reset_regions(const PersistShape& s, void* workspace, size_t workspa
 
 template <int NT>
 static int u_launch(const UGeom& g, const UArgs& p, bool dp, int n, bool do_eval, hipStream_t st) {
-  // the > 64 KB dynamic-LDS attribute is per device (the plan's device is the current one:
-  // the Python mirror enters the model's device around every call)
-  static bool attr_set_dev[64] = {};
-  int attr_dev = 0;
-  BSIG_HIP(hipGetDevice(&attr_dev));
-  bool& attr_set = attr_set_dev[attr_dev & 63];
-  if (!attr_set) {
-    BSIG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(linear_head_updates_kernel<false, NT>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, kULds));
-    BSIG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(linear_head_updates_kernel<true, NT>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, kULds));
-    BSIG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(linear_head_updates_kernel<false, NT, true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, kULds));
-    attr_set = true;
-  }
   if (p.xr_ready)
     hipLaunchKernelGGL((linear_head_updates_kernel<false, NT, true>), dim3(g.T), dim3(kUT), g.lds, st, p);
   else if (dp)
@@ -1721,14 +1680,10 @@ static int u_launch(const UGeom& g, const UArgs& p, bool dp, int n, bool do_eval
   return BSIG_OK;
 }
 
-int persist_run(const PersistShape& s, const PersistBuffers& b, const PersistHyper& hy, int n,
-                hipStream_t st) {
-  UGeom g;
-  BSIG_REQUIRE(u_geom(s, &g), "persistent updates: shape not covered");
+int persist_run(const PersistShape& s, const UGeom& g, const PersistBuffers& b, int n, hipStream_t st) {
   BSIG_REQUIRE(b.feats && b.y && b.ids && b.params && b.exp_avg && b.exp_avg_sq && b.state &&
                    b.train_loss && b.workspace, "persistent updates: null buffer");
-  BSIG_REQUIRE(b.workspace_bytes >= persist_workspace_bytes(s),
-               "persistent updates: workspace too small");
+  BSIG_REQUIRE(b.workspace_bytes >= u_data_bytes(g) + u_sync_bytes(), "persistent updates: workspace too small");
   BSIG_REQUIRE(b.ld_feats % 4 == 0 && aligned(b.feats, 16) && b.ld_feats >= s.feat_dim,
                "persistent updates: features must be 16-byte aligned rows");
   BSIG_REQUIRE(!(b.adam_pending && !b.grads), "persistent updates: pending Adam step without gradients");
@@ -1758,6 +1713,7 @@ int persist_run(const PersistShape& s, const PersistBuffers& b, const PersistHyp
                ((reinterpret_cast<uintptr_t>(b.params) | reinterpret_cast<uintptr_t>(b.exp_avg) |
                  reinterpret_cast<uintptr_t>(b.exp_avg_sq) | reinterpret_cast<uintptr_t>(b.grads)) & 15) == 0) ? 1 : 0;
   p.state = b.state; p.train_loss = b.train_loss;
+  const PersistHyper& hy = b.hy;
   p.lr = hy.lr; p.beta1 = hy.beta1; p.beta2 = hy.beta2;
   p.adam_eps = hy.adam_eps; p.eps_noise = hy.eps_noise; p.min_w = hy.min_weight;
   p.ll_limit = hy.ll_limit; p.inv_norm = 1.0f / (float)hy.norm_batch;

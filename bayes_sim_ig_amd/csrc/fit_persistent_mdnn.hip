@@ -53,16 +53,7 @@ __global__ __launch_bounds__(kMT) void mdnn_updates_kernel(MdnnArgs p) {
 }
 
 // ---------------------------------------------------------------- host side
-struct MdnnGeom {
-  int FR, Nh, Nh16, NhP, k_slices, G1, n_owner, n_small, x_floats;
-  int wide;                     // head outputs formed by the head-block workgroups (see MdnnArgs)
-  int stream, s_chunks;         // W1 streamed by G1 tile workgroups (fit_persistent_mdnn_stream.hip)
-  int mr;                       // minibatch rows per owner workgroup
-  int eval_passes;              // 0: evaluations stay outside the launches
-  size_t lds;
-  size_t slab_floats, act_floats, dout_floats, eval_floats, eval_slab_floats;
-};
-
+// (the four switches below are read while a plan resolves its engine: once per plan)
 static bool mdnn_geom(const PersistMdnnShape& s, MdnnGeom* g) {
   if (s.batch < 1 || s.input_dim < 1 || s.h1 != kMH || s.h2 != kMH ||
       s.activation != BSIG_ACT_TANH || s.out_dim < 1 || s.n_comp < 1 || s.n_comp > 64)
@@ -156,9 +147,18 @@ static bool mdnn_device_can_host(const MdnnGeom& g) {
   if (prop.multiProcessorCount < g.G1 + g.n_owner + g.n_small || (size_t)prop.maxSharedMemoryPerMultiProcessor < g.lds)
     return false;
   // the runtime's own occupancy answer (registers, LDS, wave slots) must admit a workgroup per CU
+  static bool lds_set[64] = {};
+  const void* kernels[16] = {
+#define BSIG_K(a, b, c, d) reinterpret_cast<const void*>(mdnn_updates_kernel<a, b, c, d>)
+      BSIG_K(false, false, false, false), BSIG_K(true, false, false, false), BSIG_K(false, true, false, false),
+      BSIG_K(true, true, false, false),   BSIG_K(false, false, true, false), BSIG_K(true, false, true, false),
+      BSIG_K(false, true, true, false),   BSIG_K(true, true, true, false),   BSIG_K(false, false, false, true),
+      BSIG_K(true, false, false, true),   BSIG_K(false, true, false, true),  BSIG_K(true, true, false, true),
+      BSIG_K(false, false, true, true),   BSIG_K(true, false, true, true),   BSIG_K(false, true, true, true),
+      BSIG_K(true, true, true, true)};
+#undef BSIG_K
   int per_cu = 0;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(mdnn_updates_kernel<false, false, false, false>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, kMLdsLimit) != hipSuccess ||
+  if (allow_dynamic_lds(lds_set, kernels, 16, kMLdsLimit) != BSIG_OK ||
       hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mdnn_updates_kernel<false, false, false, false>, kMT,
                                                    std::min(g.lds, (size_t)kMLdsLimit)) != hipSuccess)
     return false;
@@ -175,36 +175,6 @@ int persist_mdnn_geometry(const PersistMdnnShape& s, int32_t* out) {
   return 1;
 }
 
-bool persist_mdnn_supported(const PersistMdnnShape& s) {
-  MdnnGeom g;
-  return mdnn_geom(s, &g) && mdnn_device_can_host(g);
-}
-int persist_mdnn_streams(const PersistMdnnShape& s) {
-  MdnnGeom g;
-  return mdnn_geom(s, &g) && mdnn_device_can_host(g) && g.stream ? 1 : 0;
-}
-// the LDS of a streamed plan's tile workgroups for S x A cross-correlation factors
-static bool mdnn_stream_fits(const MdnnGeom& g, int S, int A, int* nip, int* pf, size_t* lds) {
-  return mdnn_stream_tile_geom(g.FR, ceil_div(g.s_chunks, g.G1 / 4), S, A, nip, pf, lds);
-}
-bool persist_mdnn_accepts_factors(const PersistMdnnShape& s, int S, int A) {
-  MdnnGeom g;
-  if (!mdnn_geom(s, &g) || !mdnn_device_can_host(g)) return false;
-  if ((int64_t)S * A + 2 != s.input_dim || S < 1 || A < 1) return false;
-  if (!g.stream) return true;
-  int nip, pf; size_t lds;
-  return mdnn_stream_fits(g, S, A, &nip, &pf, &lds);
-}
-bool persist_mdnn_eval_supported(const PersistMdnnShape& s) {
-  MdnnGeom g;
-  return mdnn_geom(s, &g) && mdnn_device_can_host(g) && g.eval_passes > 0;
-}
-// ... by a data-parallel rank (one launch per update): narrow heads on a resident first layer only
-bool persist_mdnn_dp_eval_supported(const PersistMdnnShape& s) {
-  MdnnGeom g;
-  return mdnn_geom(s, &g) && mdnn_device_can_host(g) && g.eval_passes > 0 && !g.wide && !g.stream;
-}
-
 constexpr size_t kPackFloats = (size_t)2 * kMH * kMH;   // both parities
 static size_t mdnn_wide_floats(const MdnnGeom& g) {
   return g.wide ? g.dout_floats + (size_t)(g.NhP / kMNB) * g.act_floats : 0;
@@ -216,17 +186,41 @@ static size_t mdnn_data_bytes(const MdnnGeom& g) {
 // flags, granules and (last 256 bytes) the word the workgroups of a resident rank count themselves in
 static size_t mdnn_sync_bytes() { return 14 * kFlagArr * sizeof(unsigned) + 6 * kGranArr * 8 + 256; }
 
-size_t persist_mdnn_workspace_bytes(const PersistMdnnShape& s) {
-  MdnnGeom g;
-  if (!mdnn_geom(s, &g)) return 0;
-  return mdnn_data_bytes(g) + mdnn_sync_bytes();
+bool persist_mdnn_resolve(const PersistMdnnShape& s, MdnnGeom* g, PersistEngine* e) {
+  MdnnGeom c;
+  if (!mdnn_geom(s, &c) || !mdnn_device_can_host(c)) return false;
+  c.s_S = c.s_A = c.s_dp = c.s_nip = c.s_pf = 0; c.s_lds = 0;
+  *g = c;
+  e->kind = 2; e->streams = c.stream != 0;
+  e->eval_single = c.eval_passes > 0;
+  // (a data-parallel rank, one launch per update: narrow heads on a resident first layer only)
+  e->eval_dp = c.eval_passes > 0 && !c.wide && !c.stream;
+  e->workspace_bytes = mdnn_data_bytes(c) + mdnn_sync_bytes();
+  return true;
 }
 
-int persist_mdnn_reset_regions(const PersistMdnnShape& s, void* workspace, size_t workspace_bytes,
-                               ZeroRegion* regions) {
-  MdnnGeom g;
-  BSIG_REQUIRE(mdnn_geom(s, &g), "persistent MDNN updates: shape not covered");
-  BSIG_REQUIRE(workspace && workspace_bytes >= persist_mdnn_workspace_bytes(s),
+// the LDS of a streamed plan's tile workgroups for S x A cross-correlation factors
+static bool mdnn_stream_fits(const MdnnGeom& g, int S, int A, int* nip, int* pf, size_t* lds) {
+  return mdnn_stream_tile_geom(g.FR, ceil_div(g.s_chunks, g.G1 / 4), S, A, nip, pf, lds);
+}
+bool persist_mdnn_factors_fit(const MdnnGeom& g, int input_dim, int S, int A) {
+  if ((int64_t)S * A + 2 != input_dim || S < 1 || A < 1) return false;
+  int nip, pf; size_t lds;
+  return !g.stream || mdnn_stream_fits(g, S, A, &nip, &pf, &lds);
+}
+int persist_mdnn_resolve_stream(MdnnGeom* g, int input_dim, bool full_cov, int S, int A, bool dp) {
+  int nip = 0, pf = 0;
+  size_t lds = 0;
+  BSIG_REQUIRE(g->stream && (int64_t)S * A + 2 == input_dim && mdnn_stream_fits(*g, S, A, &nip, &pf, &lds),
+               "persistent MDNN updates: factor rows S=%d A=%d not covered by the streamed first layer", S, A);
+  // the tile workgroups' LDS depends on the factor dimensions: the launch's occupancy is known only now
+  BSIG_TRY(mdnn_stream_can_host(dp, g->wide != 0, full_cov, g->G1 + g->n_owner + g->n_small, std::max(g->lds, lds)));
+  g->s_S = S; g->s_A = A; g->s_dp = dp ? 1 : 0; g->s_nip = nip; g->s_pf = pf; g->s_lds = lds;
+  return BSIG_OK;
+}
+
+int persist_mdnn_reset_regions(const MdnnGeom& g, void* workspace, size_t workspace_bytes, ZeroRegion* regions) {
+  BSIG_REQUIRE(workspace && workspace_bytes >= mdnn_data_bytes(g) + mdnn_sync_bytes(),
                "persistent MDNN updates: workspace too small");
   char* base = reinterpret_cast<char*>(workspace);
   const size_t slab_bytes = g.slab_floats * sizeof(float);
@@ -236,13 +230,11 @@ int persist_mdnn_reset_regions(const PersistMdnnShape& s, void* workspace, size_
   return BSIG_OK;
 }
 
-int persist_mdnn_run(const PersistMdnnShape& s, const PersistMdnnBuffers& b,
-                     const PersistHyper& hy, int n, hipStream_t st) {
-  MdnnGeom g;
-  BSIG_REQUIRE(mdnn_geom(s, &g), "persistent MDNN updates: shape not covered");
+int persist_mdnn_run(const PersistMdnnShape& s, const MdnnGeom& g, const PersistMdnnBuffers& b, int n,
+                     hipStream_t st) {
   BSIG_REQUIRE(b.x && b.y && b.ids && b.params && b.exp_avg && b.exp_avg_sq && b.state &&
                    b.train_loss && b.workspace, "persistent MDNN updates: null buffer");
-  BSIG_REQUIRE(b.workspace_bytes >= persist_mdnn_workspace_bytes(s),
+  BSIG_REQUIRE(b.workspace_bytes >= mdnn_data_bytes(g) + mdnn_sync_bytes(),
                "persistent MDNN updates: workspace too small");
   const bool fac = b.x_kind == BSIG_X_CROSSCORR_FACTORS;
   BSIG_REQUIRE(b.x_kind == BSIG_X_ROWS || fac, "persistent MDNN updates: unknown x_kind");
@@ -259,35 +251,13 @@ int persist_mdnn_run(const PersistMdnnShape& s, const PersistMdnnBuffers& b,
   BSIG_REQUIRE(!(b.xr_ready && !(b.grads && b.xr_done && !b.adam_pending && !g.stream && b.do_eval && b.n_total == n && n >= 1)),
                "persistent MDNN updates: a resident data-parallel launch takes the whole call, evaluations inside");
   if (n <= 0 && !b.adam_pending && !b.do_eval) return BSIG_OK;
-  int s_nip = 0, s_pf = 0;
-  size_t s_lds = 0;
   if (g.stream) {
     BSIG_REQUIRE(fac, "persistent MDNN updates: a streamed first layer takes cross-correlation factor rows");
-    BSIG_REQUIRE(mdnn_stream_fits(g, b.x_s, b.x_a, &s_nip, &s_pf, &s_lds),
+    BSIG_REQUIRE(b.x_s == g.s_S && b.x_a == g.s_A,     // (resolved at bind: persist_mdnn_resolve_stream)
                  "persistent MDNN updates: factor rows S=%d A=%d not covered by the streamed first layer",
                  b.x_s, b.x_a);
     BSIG_REQUIRE(!b.adam_pending && n >= 1 && !(b.do_eval && b.grads),
                  "persistent MDNN updates: a streamed first layer takes its Adam step outside");
-  }
-  // the > 64 KB dynamic-LDS attribute is per device (the plan's device is the current one:
-  // the Python mirror enters the model's device around every call)
-  static bool attr_set_dev[64] = {};
-  int attr_dev = 0;
-  BSIG_HIP(hipGetDevice(&attr_dev));
-  bool& attr_set = attr_set_dev[attr_dev & 63];
-  if (!attr_set) {
-    const void* kernels[16] = {
-#define BSIG_K(a, b, c, d) reinterpret_cast<const void*>(mdnn_updates_kernel<a, b, c, d>)
-        BSIG_K(false, false, false, false), BSIG_K(true, false, false, false), BSIG_K(false, true, false, false),
-        BSIG_K(true, true, false, false),   BSIG_K(false, false, true, false), BSIG_K(true, false, true, false),
-        BSIG_K(false, true, true, false),   BSIG_K(true, true, true, false),   BSIG_K(false, false, false, true),
-        BSIG_K(true, false, false, true),   BSIG_K(false, true, false, true),  BSIG_K(true, true, false, true),
-        BSIG_K(false, false, true, true),   BSIG_K(true, false, true, true),   BSIG_K(false, true, true, true),
-        BSIG_K(true, true, true, true)};
-#undef BSIG_K
-    for (const void* k : kernels)
-      BSIG_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMLdsLimit));
-    attr_set = true;
   }
   MdnnArgs p{};
   p.B = s.batch; p.FR = g.FR; p.I = s.input_dim; p.Nh = g.Nh; p.Nh16 = g.Nh16; p.NhP = g.NhP;
@@ -309,6 +279,7 @@ int persist_mdnn_run(const PersistMdnnShape& s, const PersistMdnnBuffers& b,
     p.fast_rows = (e && e[0] == '0') ? 0 : ((e && e[0] == '2') ? 2 : 1);     // (2: also for wide first layers)
   }
   p.state = b.state; p.train_loss = b.train_loss;
+  const PersistHyper& hy = b.hy;
   p.lr = hy.lr; p.beta1 = hy.beta1; p.beta2 = hy.beta2;
   p.adam_eps = hy.adam_eps; p.eps_noise = hy.eps_noise; p.min_w = hy.min_weight;
   p.ll_limit = hy.ll_limit; p.inv_norm = 1.0f / (float)hy.norm_batch;
@@ -329,7 +300,7 @@ int persist_mdnn_run(const PersistMdnnShape& s, const PersistMdnnBuffers& b,
   p.o_wide = p.oe + (g.wide && g.eval_passes > 0 ? g.dout_floats : 0);
   p.dz2_part = p.o_wide + g.dout_floats;
   p.hpre = g.wide ? p.dz2_part + (size_t)(g.NhP / kMNB) * g.act_floats : p.o_wide;   // (o_wide / dz2_part: wide plans only)
-  p.stream = g.stream; p.s_chunks = g.s_chunks; p.s_nip = s_nip; p.s_pf = s_pf;
+  p.stream = g.stream; p.s_chunks = g.s_chunks; p.s_nip = g.s_nip; p.s_pf = g.s_pf;
   char* sync = base + mdnn_data_bytes(g);
   p.flag_fwd = reinterpret_cast<unsigned*>(sync);
   p.flag_own = p.flag_fwd + kFlagArr;
@@ -384,7 +355,7 @@ int persist_mdnn_run(const PersistMdnnShape& s, const PersistMdnnBuffers& b,
     else BSIG_MDNN_LAUNCH(DP_, FAC_, false, false, kMR);                     \
   } while (0)
   const bool dp = b.grads != nullptr && !b.xr_ready, full = s.full_cov != 0;      // (resident: the single-rank instantiations)
-  if (g.stream) return mdnn_stream_launch(p, dp, g.wide != 0, full, (int)grid.x, std::max(g.lds, s_lds), st);
+  if (g.stream) return mdnn_stream_launch(p, dp, g.wide != 0, full, (int)grid.x, std::max(g.lds, g.s_lds), st);
   if (dp && fac) BSIG_MDNN_LAUNCH_WF(true, true);
   else if (dp) BSIG_MDNN_LAUNCH_WF(true, false);
   else if (fac) BSIG_MDNN_LAUNCH_WF(false, true);

@@ -3,7 +3,7 @@
 // covariance; fit_persistent_mdnn.hip): a run of consecutive Adam updates
 // (mdnn.py:219-233) in ONE launch.
 #pragma once
-#include "common.h"
+#include "persist.h"
 
 namespace bsig {
 
@@ -12,58 +12,55 @@ struct PersistMdnnShape {
   int max_test = 0;   // held-out rows the plan may evaluate inside the launches (0: none)
 };
 
-struct PersistMdnnBuffers {
+// The decomposition fit_persistent_mdnn.hip plans for a shape (host only)
+struct MdnnGeom {
+  int FR, Nh, Nh16, NhP, k_slices, G1, n_owner, n_small, x_floats;
+  int wide;                     // head outputs formed by the head-block workgroups (see MdnnArgs)
+  int stream, s_chunks;         // W1 streamed by G1 tile workgroups (fit_persistent_mdnn_stream.hip)
+  int mr;                       // minibatch rows per owner workgroup
+  int eval_passes;              // 0: evaluations stay outside the launches
+  size_t lds;
+  size_t slab_floats, act_floats, dout_floats, eval_floats, eval_slab_floats;
+  // streamed W1: the tile workgroups' layout of S x A factor rows, known at bind
+  // (persist_mdnn_resolve_stream; s_S = 0: none yet)
+  int s_S, s_A, s_dp, s_nip, s_pf;
+  size_t s_lds;
+};
+
+struct PersistMdnnBuffers : PersistCommon {
   const float* x; int64_t ldx;            // summary rows (training split of the chunk), or
   int x_kind = 0, x_s = 0, x_a = 0;       // ... cross-correlation factor rows (bsig.h: the tile
                                           // workgroups form x[i*A + j] = sf[i] * af[j] themselves)
-  const int32_t* ids;                     // [n_updates*batch] minibatch row ids (rows of x and y)
-  const float* y; int64_t ldy;            // normalised targets
-  float* params; float* exp_avg; float* exp_avg_sq;   // flat buffers
   int64_t w1_off, b1_off, w2_off, b2_off, wh_off, bh_off;
-  int32_t* state;                         // the fit engine's 16-word state block
-  float* train_loss;                      // [n_updates]
-  void* workspace; size_t workspace_bytes;
-  // data-parallel ranks (null / 0 otherwise): the gradients of the update go to `grads`
-  // (flat layout) for the caller's all-reduce instead of into Adam; with `adam_pending` the
-  // launch first takes the Adam step of the previous update from the (reduced) `grads`.
-  // n = 0 with adam_pending: that step only.
-  float* grads = nullptr; int adam_pending = 0;
-  // ... or RESIDENT across the exchange, as persist.h: PersistBuffers::xr_* (plans whose first layer is
-  // resident on the chip and whose evaluations run inside the launch; ONE launch for the whole call)
-  unsigned* xr_ready = nullptr; const unsigned* xr_done = nullptr; unsigned xr_base = 0;
-  // held-out evaluations inside the launch (persist_mdnn_eval_supported): after update `it`
-  // of the call with it % eval_every == 0 and after the last of its n_total updates
-  // (mdnn.py:235-242); evaluation k writes test_loss[state[1]] and advances state[1]
-  int do_eval = 0; int eval_every = 1; int n_total = 0; int n_test = 0;
-  // streamed first layer: the held-out pairs' factor rows (in-launch evaluation)
-  const float* x_test_fac = nullptr; int64_t ldx_test_fac = 0;
+  // held-out rows of the in-launch evaluations: summary rows, or -- streamed first layer -- the
+  // held-out pairs' factor rows
   const float* x_test = nullptr; int64_t ldx_test = 0;
-  const float* y_test = nullptr; int64_t ldy_test = 0;
-  float* test_loss = nullptr;
+  const float* x_test_fac = nullptr; int64_t ldx_test_fac = 0;
 };
 
-struct PersistHyper;   // persist.h
-
-bool persist_mdnn_supported(const PersistMdnnShape& s);
+// The decomposition of a shape and whether the device can hold every workgroup of its launch at once
+// (asks the device and raises the kernels' dynamic-LDS limit: once per plan).  With a streamed first
+// layer (it does not fit the chip) such a plan takes cross-correlation factor rows only; the Adam step
+// of a data-parallel rank runs outside the launches (flat kernel after the all-reduce); a single rank's
+// held-out evaluations run INSIDE its one launch, from the held-out pairs' factor rows
+// (bsig_fit_evaluates_from_factors).  false: not covered, *g and *e as they were.
+bool persist_mdnn_resolve(const PersistMdnnShape& s, MdnnGeom* g, PersistEngine* e);
+// S x A cross-correlation factor rows give the first layer's input_dim and -- streamed first layer --
+// fit its tile workgroups (arithmetic only; bsig.h: x_kind)
+bool persist_mdnn_factors_fit(const MdnnGeom& g, int input_dim, int S, int A);
+// streamed first layer, at bind: the tile workgroups' layout for S x A factor rows, and whether the
+// device can hold every workgroup of the launch (data-parallel or single-rank instantiation) at once
+// (asks the device).  *g unchanged on failure.
+int persist_mdnn_resolve_stream(MdnnGeom* g, int input_dim, bool full_cov, int S, int A, bool dp);
 // (diagnostics) the decomposition fit_persistent_mdnn.hip plans for a shape, bsig.h: bsig_debug_persist_mdnn_geometry
 int persist_mdnn_geometry(const PersistMdnnShape& s, int32_t* out);
-// ... with the first layer STREAMED by the tile workgroups (it does not fit the chip): such a plan
-// takes cross-correlation factor rows only; the Adam step of a data-parallel rank runs outside the
-// launches (flat kernel after the all-reduce); a single rank's held-out evaluations run INSIDE its
-// one launch, from the held-out pairs' factor rows (bsig_fit_evaluates_from_factors)
-int persist_mdnn_streams(const PersistMdnnShape& s);
-// ... and S x A cross-correlation factor rows are covered (bsig.h: x_kind)
-bool persist_mdnn_accepts_factors(const PersistMdnnShape& s, int S, int A);
-// ... and the held-out evaluations of up to s.max_test rows can run inside the launches
-bool persist_mdnn_eval_supported(const PersistMdnnShape& s);
-bool persist_mdnn_dp_eval_supported(const PersistMdnnShape& s);
-size_t persist_mdnn_workspace_bytes(const PersistMdnnShape& s);
-struct ZeroRegion;   // persist.h
-int persist_mdnn_reset_regions(const PersistMdnnShape& s, void* workspace, size_t workspace_bytes,
-                               ZeroRegion* regions);
+int persist_mdnn_reset_regions(const MdnnGeom& g, void* workspace, size_t workspace_bytes, ZeroRegion* regions);
 // n consecutive updates starting at the state block's step counter; advances the
 // counter, the jitter RNG stream and the Adam bias-correction powers
-int persist_mdnn_run(const PersistMdnnShape& s, const PersistMdnnBuffers& b,
-                     const PersistHyper& h, int n, hipStream_t st);
+int persist_mdnn_run(const PersistMdnnShape& s, const MdnnGeom& g, const PersistMdnnBuffers& b, int n,
+                     hipStream_t st);
+// fit_persistent_mdnn_stream.hip: can the device hold the streamed launch's `grid` workgroups of `lds`
+// bytes at once (asks the device)?
+int mdnn_stream_can_host(bool dp, bool wide, bool full, int grid, size_t lds);
 
 }  // namespace bsig
