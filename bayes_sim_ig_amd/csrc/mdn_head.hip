@@ -542,6 +542,16 @@ static int head_geom(const bsig_head_dims* d, int64_t batch, HeadGeom* g) {
   return BSIG_OK;
 }
 
+// The kernel mdn_head_nll_launch runs for a geometry (bsig_debug_head_geometry reports it).
+enum HeadPath { kPathWave2 = 0, kPathWave8 = 1, kPathDiag = 2, kPathFull = 3 };
+static int head_sweeps(const HeadGeom& g) { return ceil_div(g.D, 64 / g.K); }
+static HeadPath head_path(const HeadGeom& g) {
+  // (rows of at most two sweeps -- D <= 2 * (64 / K): every BASELINE shape -- run the kernel that
+  // carries only the two-sweep row body: fewer registers, twice the rows per CU in flight)
+  if (g.wave_per_row) return head_sweeps(g) <= 2 ? kPathWave2 : kPathWave8;
+  return g.Ls > 0 ? kPathFull : kPathDiag;
+}
+
 // workspace floats: [sig partials kSigMax][block_lse nblk][block_uds nblk][colsum slabs x Nh]
 static size_t head_ws_floats(const HeadGeom& g) {
   return kSigMax + 2 * (size_t)g.blocks + (size_t)kMaxSlabs * g.Nh;
@@ -596,20 +606,21 @@ int mdn_head_nll_launch(const bsig_head_dims* dims, const float* seg_w, int64_t 
   a.sig_partials = sig_partials; a.n_sig = n_sig;
   a.d_out = d_out; a.ld_dout = ld_dout;
   a.block_lse = block_lse; a.block_uds = block_uds; a.nonfinite = nonfinite;
-  if (g.wave_per_row) {
-    // (rows of at most two sweeps -- D <= 2 * (64 / K): every BASELINE shape -- run the kernel that
-    // carries only the two-sweep row body: fewer registers, twice the rows per CU in flight)
-    const int nq = ceil_div(g.D, 64 / g.K);
-    if (nq <= 2)
+  switch (head_path(g)) {
+    case kPathWave2:
       hipLaunchKernelGGL((mdn_nll_diag_wave_kernel<kWavesPerBlock, 2>), dim3(g.blocks), dim3(g.threads), g.lds, st, a);
-    else
+      break;
+    case kPathWave8:
       hipLaunchKernelGGL((mdn_nll_diag_wave_kernel<kWavesPerBlock, kElemsPerLane>), dim3(g.blocks), dim3(g.threads),
                          g.lds, st, a);
+      break;
+    case kPathFull:
+      hipLaunchKernelGGL(mdn_nll_kernel<true>, dim3(g.blocks), dim3(g.threads), g.lds, st, a);
+      break;
+    case kPathDiag:
+      hipLaunchKernelGGL(mdn_nll_kernel<false>, dim3(g.blocks), dim3(g.threads), g.lds, st, a);
+      break;
   }
-  else if (g.Ls > 0)
-    hipLaunchKernelGGL(mdn_nll_kernel<true>, dim3(g.blocks), dim3(g.threads), g.lds, st, a);
-  else
-    hipLaunchKernelGGL(mdn_nll_kernel<false>, dim3(g.blocks), dim3(g.threads), g.lds, st, a);
   BSIG_CHECK_LAUNCH("mdn_nll");
   // finish: loss, jitter-scale gradient correction, head bias gradients
   const bool correct = jitter && d_out != nullptr;
@@ -645,6 +656,21 @@ extern "C" size_t bsig_head_workspace_bytes(const bsig_head_dims* d, int64_t bat
   if (batch < 1) batch = 1;
   if (head_geom(d, batch, &g) != BSIG_OK) return 0;
   return head_ws_floats(g) * sizeof(float);
+}
+
+extern "C" int bsig_debug_head_geometry(const bsig_head_dims* d, int64_t batch, int32_t* out) {
+  BSIG_REQUIRE(out, "head geometry: null pointer");
+  for (int i = 0; i < 16; ++i) out[i] = 0;
+  BSIG_REQUIRE(batch >= 1 && batch < (1 << 30), "head geometry: bad batch");
+  HeadGeom g;
+  BSIG_TRY(head_geom(d, batch, &g));
+  // the launcher's kernel, and the row body diag_row_impl picks inside a wavefront kernel
+  const int nq = head_sweeps(g);
+  out[0] = head_path(g);
+  out[1] = g.wave_per_row ? (nq <= 2 ? 2 : nq <= 4 ? 4 : kElemsPerLane) : 0;
+  out[2] = g.R; out[3] = g.threads; out[4] = (int32_t)g.lds; out[5] = g.blocks;
+  out[6] = g.slabs; out[7] = g.rows_per_slab; out[8] = nq; out[9] = g.Nh;
+  return BSIG_OK;
 }
 
 extern "C" int bsig_mdn_head_outputs(const bsig_head_dims* dims, const float* head_out,

@@ -152,6 +152,16 @@ typedef struct bsig_head_dims {
 int64_t bsig_head_width(const bsig_head_dims* dims);          /* Nh */
 size_t bsig_head_workspace_bytes(const bsig_head_dims* dims, int64_t batch);
 
+/* Diagnostics / tests: the device path the head kernels (bsig_mdn_head_nll, bsig_mdn_nll_from_tuple,
+ * the per-phase fit) take for this shape at this minibatch size -- host arithmetic only, no device is
+ * asked.  out[16] = { path (0: one wavefront per row, kernel of at most two sweeps; 1: the same with up
+ * to eight sweeps; 2: thread per component, diagonal; 3: thread per component, full covariance),
+ * row body of a wavefront path (2, 4 or 8 sweeps; 0 otherwise), rows per workgroup R, threads per
+ * workgroup, LDS bytes per workgroup, workgroups, row slabs of the finishing kernel, rows per slab,
+ * sweeps ceil(D / (64 / K)), head width Nh, 0... }.  Returns BSIG_OK, or the code a launch of a
+ * refused shape returns (out all zero). */
+int bsig_debug_head_geometry(const bsig_head_dims* dims, int64_t batch, int32_t* out);
+
 /* forward() tuple from raw head outputs, mdnn.py:109-119.  `noise` [B,D,K]
  * is the injected rand_like draw (NULL: Philox noise from seed/stream_id). */
 int bsig_mdn_head_outputs(const bsig_head_dims* dims, const float* head_out,

@@ -240,15 +240,116 @@ class OracleMDRFF(OracleMDNN):
 
 
 # --------------------------------------------- closed-form fp64 head check
+def _split_head(o, d, k, ls):
+    b = o.shape[0]
+    logits = o[:, :k]
+    mu = o[:, k:k + d * k].reshape(b, d, k)
+    pre = o[:, k + d * k:k + 2 * d * k].reshape(b, d, k)
+    low = o[:, k + 2 * d * k:k + 2 * d * k + ls * k].reshape(b, ls, k) if ls else None
+    return logits, mu, pre, low
+
+
+def _mixture_weights(logits, min_weight):
+    """softmax -> clamp -> renormalise (mdnn.py:109-111): (s, csum, w)"""
+    s = np.exp(logits - logits.max(axis=1, keepdims=True))
+    s /= s.sum(axis=1, keepdims=True)
+    c = np.clip(s, min_weight, 1.0)
+    csum = c.sum(axis=1, keepdims=True)
+    return s, csum, c / csum
+
+
+def _component_logp(y, mu, sig, low, d):
+    """log N(y; mu_k, T_k T_k^T) of every (row, component), T_k = diag(sig) + strict lower, and
+    its derivatives per unit of d loss / d logp: (logp [B,K], d/dmu, d/dsig [B,D,K],
+    d/dlower [B,Ls,K] or None).  Full covariance by batched fp64 triangular solves."""
+    r = y[:, :, None] - mu
+    half_log_2pi = 0.5 * d * math.log(2 * math.pi)
+    logdet = np.log(sig).sum(axis=1)
+    if low is None:
+        z = r / sig
+        return -0.5 * (z * z).sum(axis=1) - logdet - half_log_2pi, z / sig, (z * z - 1.0) / sig, None
+    b, k = sig.shape[0], sig.shape[2]
+    rows, cols = np.tril_indices(d, -1)
+    t = np.zeros((b, k, d, d))
+    t[:, :, np.arange(d), np.arange(d)] = sig.transpose(0, 2, 1)
+    t[:, :, rows, cols] = low.transpose(0, 2, 1)
+    tt = torch.from_numpy(t)
+    rt = torch.from_numpy(np.ascontiguousarray(r.transpose(0, 2, 1)))[..., None]
+    v = torch.linalg.solve_triangular(tt, rt, upper=False)                      # T v = r
+    q = torch.linalg.solve_triangular(tt.transpose(-1, -2), v, upper=True)      # T^T q = v
+    v, q = v[..., 0].numpy(), q[..., 0].numpy()                                 # [B, K, D]
+    logp = -0.5 * (v * v).sum(axis=2) - logdet - half_log_2pi
+    g_low = (q[:, :, rows] * v[:, :, cols]).transpose(0, 2, 1)                  # (q v^T)[rows, cols]
+    return logp, q.transpose(0, 2, 1), (q * v).transpose(0, 2, 1) - 1.0 / sig, g_low
+
+
+def _mixture_nll(logp, w, b, min_weight, ll_limit):
+    """-mean logsumexp(clamp(logp) + log clamp(w)) (mdnn.py:159-178) and its pieces"""
+    lp = np.clip(logp, -ll_limit, ll_limit)
+    wc = np.clip(w, min_weight, 1.0)
+    rr = lp + np.log(wc)
+    mx = rr.max(axis=1, keepdims=True)
+    lse = mx[:, 0] + np.log(np.exp(rr - mx).sum(axis=1))
+    sc = -np.exp(rr - lse[:, None]) / b
+    g_lp = sc * ((logp >= -ll_limit) & (logp <= ll_limit))
+    return -lse.mean(), lse, sc, wc, g_lp
+
+
 def mdn_head_closed_form(head_out, y, out_dim, n_comp, full_cov,
-                         eps_noise=0.0, noise=None):
+                         eps_noise=0.0, noise=None, min_weight=MIN_WEIGHT,
+                         ll_limit=LL_LIMIT):
     """fp64 numpy evaluation of the MDN head on raw head outputs.
 
     head_out [B, Nh] = [logits K | mu D*K | pre_diag D*K | lower Ls*K] with
     index d*K+k inside each block (mdnn.py:109-119).  Returns
-    (loss, d_head_out, dict(weights, mu, l_d, lower, lse)).
-    Formulas: SURVEY Appendix A.1-A.3, derived from mdnn.py:108-178.
+    (loss, d_head_out, dict(weights, mu, l_d, lower, lse, logp)).
+    Formulas: SURVEY Appendix A.1-A.3, derived from mdnn.py:108-178;
+    vectorised over rows and components (``_mdn_head_closed_form_loop`` is
+    the row-by-row statement it is checked against).
     """
+    o = np.asarray(head_out, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    b, d, k = o.shape[0], out_dim, n_comp
+    ls = d * (d - 1) // 2 if full_cov else 0
+    logits, mu, pre, low = _split_head(o, d, k, ls)
+    s, csum, w = _mixture_weights(logits, min_weight)
+    sig0 = np.exp(pre)
+    eps = eps_noise * sig0.mean()
+    u = np.zeros_like(sig0) if noise is None else np.asarray(noise, np.float64)
+    sig = sig0 + u * eps
+    logp, g_mu_unit, g_sig_unit, g_low_unit = _component_logp(y, mu, sig, low, d)
+    loss, lse, sc, wc, g_lp = _mixture_nll(logp, w, b, min_weight, ll_limit)
+    d_mu = g_lp[:, None, :] * g_mu_unit
+    d_sig = g_lp[:, None, :] * g_sig_unit
+    d_sig0 = d_sig + (eps_noise / sig0.size) * np.sum(u * d_sig)
+    d_pre = d_sig0 * sig0
+    g_w = sc / wc * ((w >= min_weight) & (w <= 1.0))
+    g_c = (g_w - (g_w * w).sum(axis=1, keepdims=True)) / csum
+    g_s = g_c * ((s >= min_weight) & (s <= 1.0))
+    d_logits = s * (g_s - (g_s * s).sum(axis=1, keepdims=True))
+    parts = [d_logits, d_mu.reshape(b, -1), d_pre.reshape(b, -1)]
+    if ls:
+        parts.append((g_lp[:, None, :] * g_low_unit).reshape(b, -1))
+    aux = dict(weights=w, mu=mu, l_d=sig, lower=low, lse=lse, logp=logp)
+    return loss, np.concatenate(parts, axis=1), aux
+
+
+def mdn_nll_from_tuple(weights, mu, l_d, lower, y, full_cov, min_weight=MIN_WEIGHT,
+                       ll_limit=LL_LIMIT):
+    """fp64 mdn_loss_fn (mdnn.py:127-178) of a forward() tuple: weights [B,K], mu / l_d [B,D,K],
+    lower [B,Ls,K] (full covariance) -- the loss alone."""
+    w = np.asarray(weights, np.float64)
+    mu, sig = np.asarray(mu, np.float64), np.asarray(l_d, np.float64)
+    low = np.asarray(lower, np.float64) if full_cov else None
+    logp = _component_logp(np.asarray(y, np.float64), mu, sig, low, mu.shape[1])[0]
+    return _mixture_nll(logp, w, w.shape[0], min_weight, ll_limit)[0]
+
+
+def _mdn_head_closed_form_loop(head_out, y, out_dim, n_comp, full_cov,
+                               eps_noise=0.0, noise=None, min_weight=MIN_WEIGHT,
+                               ll_limit=LL_LIMIT):
+    """mdn_head_closed_form row by row, component by component (general
+    dense solves): the plain statement the vectorised form is tested against."""
     o = np.asarray(head_out, dtype=np.float64)
     y = np.asarray(y, dtype=np.float64)
     b, d, k = o.shape[0], out_dim, n_comp
@@ -259,7 +360,7 @@ def mdn_head_closed_form(head_out, y, out_dim, n_comp, full_cov,
     low = o[:, k + 2 * d * k:k + 2 * d * k + ls * k].reshape(b, ls, k) if ls else None
     s = np.exp(logits - logits.max(axis=1, keepdims=True))
     s /= s.sum(axis=1, keepdims=True)
-    c = np.clip(s, MIN_WEIGHT, 1.0)
+    c = np.clip(s, min_weight, 1.0)
     csum = c.sum(axis=1, keepdims=True)
     w = c / csum
     sig0 = np.exp(pre)
@@ -290,22 +391,22 @@ def mdn_head_closed_form(head_out, y, out_dim, n_comp, full_cov,
                                 - 0.5 * d * math.log(2 * math.pi))
                 g_mu_unit[bi, :, ki] = z / sig[bi, :, ki]
                 g_sig_unit[bi, :, ki] = (z * z - 1.0) / sig[bi, :, ki]
-    lp = np.clip(logp, -LL_LIMIT, LL_LIMIT)
-    wc = np.clip(w, MIN_WEIGHT, 1.0)
+    lp = np.clip(logp, -ll_limit, ll_limit)
+    wc = np.clip(w, min_weight, 1.0)
     rr = lp + np.log(wc)
     mx = rr.max(axis=1, keepdims=True)
     lse = mx[:, 0] + np.log(np.exp(rr - mx).sum(axis=1))
     loss = -lse.mean()
     gamma = np.exp(rr - lse[:, None])
     sc = -gamma / b
-    g_lp = sc * ((logp >= -LL_LIMIT) & (logp <= LL_LIMIT))
+    g_lp = sc * ((logp >= -ll_limit) & (logp <= ll_limit))
     d_mu = g_lp[:, None, :] * g_mu_unit
     d_sig = g_lp[:, None, :] * g_sig_unit
     d_sig0 = d_sig + (eps_noise / sig0.size) * np.sum(u * d_sig)
     d_pre = d_sig0 * sig0
-    g_w = sc / wc * ((w >= MIN_WEIGHT) & (w <= 1.0))
+    g_w = sc / wc * ((w >= min_weight) & (w <= 1.0))
     g_c = (g_w - (g_w * w).sum(axis=1, keepdims=True)) / csum
-    g_s = g_c * ((s >= MIN_WEIGHT) & (s <= 1.0))
+    g_s = g_c * ((s >= min_weight) & (s <= 1.0))
     d_logits = s * (g_s - (g_s * s).sum(axis=1, keepdims=True))
     parts = [d_logits, d_mu.reshape(b, -1), d_pre.reshape(b, -1)]
     if ls:

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from conftest import ROOT, golden
+import head_cases as H
 
 import bayes_sim_ig_amd as B
 from bayes_sim_ig_amd import _lib, pdf
@@ -358,3 +359,114 @@ def test_mdnn_kernel_workgroup_planner():
         else:
             assert g['mr'] == 8 and inp % 2 == 0
     assert n_ok > 150
+
+
+# ------------------------------------------------ mixture-density head paths (host arithmetic)
+HEAD_GEOM = ['path', 'body', 'R', 'threads', 'lds', 'blocks', 'slabs', 'rows_per_slab', 'nq', 'Nh']
+
+
+def head_geometry(batch, d, k, full):
+    """bsig_debug_head_geometry: (return code, dict of its outputs)"""
+    import ctypes as C
+    hd = _lib.HeadDims()
+    hd.out_dim, hd.n_comp, hd.full_cov = d, k, 1 if full else 0
+    hd.eps_noise, hd.min_weight, hd.ll_limit = 1e-5, 1e-5, 1e5
+    out = (C.c_int32 * 16)(*([-1] * 16))
+    rc = _lib.load().bsig_debug_head_geometry(C.byref(hd), batch, out)
+    assert list(out)[len(HEAD_GEOM):] == [0] * (16 - len(HEAD_GEOM))
+    return rc, dict(zip(HEAD_GEOM, list(out)))
+
+
+def test_philox_known_answers():
+    """tests/head_cases.py's Philox4x32-10 (the mirror of common.h the drawn-noise GPU tests
+    regenerate the jitter from): the Random123 known answers."""
+    got = H.philox4x32_10(0, 0, np.zeros(1, np.uint64))[0]
+    assert ['%08x' % v for v in got] == ['6627e8d5', 'e169c58d', 'bc57ac4c', '9b00dbd8']
+    got = H.philox4x32_10(2**64 - 1, 2**64 - 1, np.array([2**64 - 1], np.uint64))[0]
+    assert ['%08x' % v for v in got] == ['408f276d', '41c83b0e', 'a20bc7c6', '6d5451fd']
+
+
+def test_jitter_draw_mappings():
+    """The two element -> draw mappings of head_cases: every (row, d, k) of a row gets its own
+    Philox word (the wavefront mapping uses all four words of a counter and two counters per lane),
+    and the rows do not share draws."""
+    for b, d, k in [(3, 48, 10), (2, 8, 64), (2, 40, 3), (2, 1, 1)]:
+        for fn in (H.draws_wave, H.draws_flat):
+            u = fn(b, d, k, 7, 11)
+            assert u.shape == (b, d, k) and (u >= 0).all() and (u < 1).all()
+            assert len(np.unique(u)) == u.size            # 24-bit draws: no collision at these sizes
+    # element (d = 7, k = 2) of row 1 at K = 10: lane 1 * 10 + 2 of sweep 1, counter (64 + 12) * 2, word 1
+    u = H.draws_wave(2, 13, 10, 5, 9)
+    w = H.philox4x32_10(5, 9, np.array([(64 + 12) * 2], np.uint64))[0]
+    assert u[1, 7, 2] == (int(w[1]) >> 8) / 2.0**24
+    u = H.draws_flat(2, 13, 10, 5, 9)
+    w = H.philox4x32_10(5, 9, np.array([(13 + 7) * 10 + 2], np.uint64))[0]
+    assert u[1, 7, 2] == (int(w[0]) >> 8) / 2.0**24
+
+
+@pytest.mark.parametrize('case', H.CASES, ids=[H.case_id(c) for c in H.CASES])
+def test_head_case_table_resolves_to_its_path(case):
+    batch, d, k, full, path, body, multi = case
+    rc, g = head_geometry(batch, d, k, full)
+    assert rc == 0
+    assert (g['path'], g['body'], g['slabs'] > 1) == (path, body, multi)
+    assert g['Nh'] == k + 2 * d * k + (d * (d - 1) // 2 if full else 0) * k
+    assert g['nq'] == -(-d // (64 // k)) and g['lds'] <= 64 * 1024
+    assert g['blocks'] == -(-batch // g['R']) and g['threads'] % 64 == 0
+    assert g['slabs'] * g['rows_per_slab'] >= batch and g['slabs'] <= 64
+    if path in (0, 1):
+        assert (g['R'], g['threads']) == (8, 512)
+    else:
+        assert g['threads'] >= g['R'] * k
+
+
+def test_head_case_table_covers_every_path():
+    """The GPU head tests' case table reaches every device path and row body, tall batches, partial
+    blocks, and the component counts where lane arithmetic goes wrong."""
+    got = {(c[4], c[5]) for c in H.CASES}
+    assert got >= {(H.PATH_WAVE2, 2), (H.PATH_WAVE8, 4), (H.PATH_WAVE8, 8), (H.PATH_DIAG, 0),
+                   (H.PATH_FULL, 0)}
+    assert {1, 7, 1001, 1025, 8193} <= {c[0] for c in H.CASES}
+    assert {1, 3, 7, 10, 16, 33, 64} <= {c[2] for c in H.CASES}
+    for path in (H.PATH_WAVE2, H.PATH_WAVE8, H.PATH_DIAG, H.PATH_FULL):
+        assert any(c[6] for c in H.CASES if c[4] == path), H.PATH_NAMES[path]   # multi-slab finish
+    # partial last workgroups: 7 rows of an 8-row wavefront block, 1001 rows of an R-row block
+    for c in H.CASES:
+        if c[0] in (7, 1001):
+            g = head_geometry(*c[:4])[1]
+            assert c[0] % g['R'] != 0 or g['R'] == 1, H.case_id(c)
+    assert 1001 % head_geometry(1001, 49, 10, False)[1]['R'] == 1
+
+
+@pytest.mark.parametrize('k', [1, 3, 7, 10, 16, 33, 64])
+def test_head_path_boundaries_in_d(k):
+    """Two sweeps -> the 4-sweep body at D = 2 * (64 / K) + 1, -> the 8-sweep body at 4 * (64 / K) + 1,
+    -> the thread-per-component kernel at nine sweeps."""
+    g = 64 // k
+    for d, want in [(2 * g, (0, 2)), (2 * g + 1, (1, 4)), (4 * g, (1, 4)), (4 * g + 1, (1, 8)),
+                    (8 * g, (1, 8)), (8 * g + 1, (2, 0))]:
+        rc, geo = head_geometry(100, d, k, False)
+        assert rc == 0 and (geo['path'], geo['body']) == want, (d, k, geo)
+        assert geo['nq'] == -(-d // g)
+
+
+def test_head_finish_slab_boundaries():
+    for batch, slabs, rows in [(1024, 1, 1024), (1025, 9, 114), (8192, 64, 128), (8193, 64, 129)]:
+        for shape in [(13, 10, False), (49, 10, False), (4, 16, True)]:
+            rc, g = head_geometry(batch, *shape)
+            assert rc == 0 and (g['slabs'], g['rows_per_slab']) == (slabs, rows), (batch, shape, g)
+
+
+def test_head_full_covariance_lds_limit():
+    """Full covariance: D32 K10 fits one row per workgroup; D48 K10 needs more than 64 KB and is
+    refused with the error a launch returns."""
+    for batch in (1, 1025, 8193):
+        rc, g = head_geometry(batch, 32, 10, True)
+        assert rc == 0 and (g['path'], g['R'], g['threads']) == (3, 1, 64)
+    rc, g = head_geometry(*H.REFUSED)
+    assert rc == _lib.BSIG_EUNSUPPORTED and all(v == 0 for v in g.values())
+    assert 'LDS' in _lib.load().bsig_last_error().decode()
+    # ... as a launch of it does, before it touches the device
+    hd = _lib.HeadDims()
+    hd.out_dim, hd.n_comp, hd.full_cov = 48, 10, 1
+    assert _lib.load().bsig_head_workspace_bytes(ctypes.byref(hd), 4) == 0

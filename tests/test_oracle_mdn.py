@@ -244,3 +244,48 @@ def test_pendulum_reference_fixture():
         osum.summary_start(tsa[:, :, :3], tsa[:, :, 3:]))[0]
     nll = -oden.mog_logpdf(a, ms, ls, g['true_params'].reshape(1, -1))
     np.testing.assert_allclose(nll, g['mog.nll_true'], rtol=1e-3)
+
+
+@pytest.mark.parametrize('b,d,k,full,eps,min_w,ll', [
+    (7, 3, 4, False, 0.0, oest.MIN_WEIGHT, oest.LL_LIMIT),
+    (9, 5, 3, True, 1e-5, oest.MIN_WEIGHT, oest.LL_LIMIT),
+    (5, 1, 1, False, 0.3, oest.MIN_WEIGHT, oest.LL_LIMIT),
+    (6, 2, 5, True, 0.0, oest.MIN_WEIGHT, oest.LL_LIMIT),
+    (11, 4, 6, False, 0.25, 0.1, 5.5),          # both weight clamps and the logp clamp active
+    (8, 6, 4, True, 0.25, 0.15, 7.0)])
+def test_vectorised_closed_form_equals_loop(b, d, k, full, eps, min_w, ll):
+    """The broadcast / batched-triangular-solve head oracle equals the row-by-row loop (general
+    dense solves) to 1e-12, clamped rows and components included."""
+    rng = np.random.RandomState(b * 31 + d * 7 + k)
+    ls = d * (d - 1) // 2 if full else 0
+    o = rng.randn(b, k + 2 * d * k + ls * k) * 0.6
+    o[:, :k] *= 5.0
+    y = rng.rand(b, d)
+    u = rng.rand(b, d, k)
+    kw = dict(eps_noise=eps, noise=u, min_weight=min_w, ll_limit=ll)
+    loss, grad, aux = oest.mdn_head_closed_form(o, y, d, k, full, **kw)
+    loss0, grad0, aux0 = oest._mdn_head_closed_form_loop(o, y, d, k, full, **kw)
+    if ll < oest.LL_LIMIT:     # the clamps this case is there for really bite
+        assert (np.abs(aux['logp']) > ll).any() and (np.abs(aux['logp']) < ll).any()
+        assert (aux['weights'] < min_w).any()
+    assert abs(loss - loss0) <= 1e-12 * max(1.0, abs(loss0))
+    np.testing.assert_allclose(grad, grad0, rtol=1e-12, atol=1e-12 * np.abs(grad0).max())
+    for key in ('weights', 'l_d', 'lse', 'logp'):
+        np.testing.assert_allclose(aux[key], aux0[key], rtol=1e-12, atol=1e-12, err_msg=key)
+    # the tuple form gives the same loss from the same tuple
+    t = oest.mdn_nll_from_tuple(aux['weights'], aux['mu'], aux['l_d'], aux['lower'], y, full,
+                                min_weight=min_w, ll_limit=ll)
+    assert abs(t - loss0) <= 1e-12 * max(1.0, abs(loss0))
+
+
+def test_vectorised_closed_form_is_fast_on_a_tall_batch():
+    """8193 rows x 64 components (the multi-slab head shapes) evaluate in seconds."""
+    import time
+    rng = np.random.RandomState(0)
+    b, d, k = 8193, 9, 64
+    o = rng.randn(b, k + 2 * d * k).astype(np.float32)
+    t0 = time.perf_counter()
+    loss, grad, _ = oest.mdn_head_closed_form(o, rng.rand(b, d), d, k, False, eps_noise=1e-5,
+                                              noise=rng.rand(b, d, k))
+    assert time.perf_counter() - t0 < 10.0
+    assert np.isfinite(loss) and grad.shape == o.shape and np.isfinite(grad).all()
