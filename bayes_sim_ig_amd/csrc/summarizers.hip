@@ -350,16 +350,9 @@ __global__ __launch_bounds__(256) void crosscorr_wave_kernel(
     }
     __syncthreads();
     if (!active) continue;
-    float part = 0.f;
-    for (int i = lane; i < S; i += 64) part += sf[i];
-    const float mean = wave_sum(part) / (float)S;
-    part = 0.f;
-    for (int i = lane; i < S; i += 64) {
-      const float dlt = sf[i] - mean;
-      part += dlt * dlt;
-    }
-    const float ss = wave_sum(part);
-    const float sdev = (S < 2) ? 0.f : sqrtf(ss / (float)(S - 1));
+    // (the statistics of every other path: an fp32 sum of squares overflows from |sf| ~ 1e19)
+    float mean, sdev;
+    row_mean_std(sf, S, lane, mean, sdev);
     if (fac) {
       float* f = fac + traj * ld_fac;
       for (int i = lane; i < S + A; i += 64) f[i] = sf[i];     // af follows sf in LDS
@@ -607,26 +600,6 @@ extern "C" int64_t bsig_summary_dim(int kind, int traj_len, int sd, int ad, int 
   return -1;
 }
 
-extern "C" int bsig_summary_start(const float* states, const float* actions, float* out,
-                                  int64_t n, int t_states, int t_actions, int sd, int ad,
-                                  int max_t, int64_t ld_out, bsig_stream_t stream) {
-  bsig::Range roctx_range("bsig_summary_start");
-  if (n == 0) return BSIG_OK;
-  BSIG_REQUIRE(states && actions && out, "summary_start: null pointer");
-  BSIG_REQUIRE(n >= 0 && t_states >= 1 && t_actions >= 1 && sd >= 1 && ad >= 1 && max_t >= 1,
-               "summary_start: bad dims n=%lld ts=%d ta=%d sd=%d ad=%d max_t=%d",
-               (long long)n, t_states, t_actions, sd, ad, max_t);
-  BSIG_REQUIRE(ld_out >= (int64_t)max_t * (sd + ad), "summary_start: ld_out too small");
-  if (n == 0) return BSIG_OK;
-  const int width = sd + ad;
-  const int threads = width >= 192 ? 256 : (width >= 96 ? 128 : 64);
-  hipLaunchKernelGGL((summary_start_kernel<10>), dim3(grid_for(n)), dim3(threads), 0,
-                     as_stream(stream), states, actions, out, n, t_states, t_actions, sd,
-                     ad, max_t, ld_out);
-  BSIG_CHECK_LAUNCH("summary_start");
-  return BSIG_OK;
-}
-
 namespace bsig {
 static int crosscorr_window(int t_states, int sd) {
   int w = sd > 50 ? 5 : 10;                       // summarizers.py:96-98
@@ -634,6 +607,158 @@ static int crosscorr_window(int t_states, int sd) {
   return w;
 }
 
+// The device path of a summarizer launch: the launchers take their kernel, store loop and launch
+// shape from these helpers, and bsig_debug_summary_path reports what they pick.
+enum SumKernel { kKStart = 0, kKCcWave = 1, kKCcQuads = 2, kKCc = 3, kKSig3 = 4, kKSig12 = 5 };
+enum SumStore { kStElem = 0, kStQuad = 1, kStVec4 = 2, kStVec4Tail = 3, kStLine = 4, kStFactors = 5 };
+struct SumPath {
+  int kernel = 0, store = 0, prefetch = 0, threads = 0;
+  size_t lds = 0;
+  int grid = 0, rstep = 0, dmax = 0, steps = 0, depth = 0;
+  int vec4 = 0;                 // crosscorr_kernel's vec4 argument
+};
+
+static int start_path(int64_t n, int t_states, int t_actions, int sd, int ad, int max_t,
+                      int64_t ld_out, SumPath* p) {
+  BSIG_REQUIRE(n >= 0 && t_states >= 1 && t_actions >= 1 && sd >= 1 && ad >= 1 && max_t >= 1,
+               "summary_start: bad dims n=%lld ts=%d ta=%d sd=%d ad=%d max_t=%d",
+               (long long)n, t_states, t_actions, sd, ad, max_t);
+  BSIG_REQUIRE(ld_out >= (int64_t)max_t * (sd + ad), "summary_start: ld_out too small");
+  const int width = sd + ad;
+  p->kernel = kKStart;
+  p->store = kStElem;
+  p->threads = width >= 192 ? 256 : (width >= 96 ? 128 : 64);
+  p->grid = grid_for(n);
+  p->steps = max_t;
+  return BSIG_OK;
+}
+
+// the materialised summary (has_out), its factors (has_fac), or both
+static int crosscorr_path(int64_t n, int t_states, int t_actions, int sd, int ad, bool has_out,
+                          int64_t ld_out, bool out_align16, bool has_fac, int64_t ld_fac, SumPath* p) {
+  BSIG_REQUIRE(n >= 0 && sd >= 2 && ad >= 1, "crosscorr: bad dims sd=%d ad=%d", sd, ad);
+  BSIG_REQUIRE(t_states > 1, "crosscorr: traj_len must be > 1 (summarizers.py:94)");
+  BSIG_REQUIRE(t_actions >= 1, "crosscorr: no actions");
+  const int w = crosscorr_window(t_states, sd);
+  const int64_t S = (int64_t)w * (sd - 1), A = (int64_t)w * ad;
+  BSIG_REQUIRE(!has_out || ld_out >= S * A + 2, "crosscorr: ld_out too small");
+  BSIG_REQUIRE(!has_fac || ld_fac >= S + A + 3, "crosscorr: ld_factors too small (need S + A + 3 = %lld)",
+               (long long)(S + A + 3));
+  const size_t lds = (size_t)(S + A + 8) * sizeof(float);
+  if (lds > 150 * 1024) {
+    set_error("crosscorr: %zu B of LDS needed", lds);
+    return BSIG_EUNSUPPORTED;
+  }
+  p->steps = w;
+  p->threads = 256;
+  if (S * A <= 2048 && (S + A) * 4 * sizeof(float) <= 32 * 1024) {
+    p->kernel = kKCcWave;
+    p->store = has_out ? kStElem : kStFactors;
+    p->lds = (size_t)(S + A) * 4 * sizeof(float);
+    p->grid = (int)std::min<int64_t>(ceil_div<int64_t>(n, 4), 65536);
+    return BSIG_OK;
+  }
+  p->lds = lds;
+  p->grid = grid_for(n);
+  p->vec4 = has_out && (ld_out % 4 == 0) && out_align16;
+  const int qpr = (int)(A >> 2);
+  // the materialised summary alone, quads of action features: the lean streaming kernel
+  if (has_out && !has_fac && p->vec4 && (A & 3) == 0 && sd - 1 <= 256 && ad <= 256 && w <= 10 &&
+      getenv("BSIG_CC_GENERAL") == nullptr) {
+    int m8 = 8; for (int g = qpr; (g & 1) == 0 && m8 > 1; g >>= 1) m8 >>= 1;   // 8 / gcd(qpr, 8)
+    const int rstep = (256 / qpr) / m8 * m8;
+    if (rstep >= 1 && S * qpr >= 512) {
+      p->kernel = kKCcQuads;
+      p->store = kStQuad;
+      p->prefetch = 1;
+      p->rstep = rstep;
+      return BSIG_OK;
+    }
+  }
+  // crosscorr_kernel at 256 threads: its pf_ok and the store loop its arguments select
+  p->kernel = kKCc;
+  p->prefetch = sd - 1 <= 256 && ad <= 256 && w <= 10;
+  if (!has_out) {
+    p->store = kStFactors;
+  } else if (p->vec4 && (A & 3) == 0 && A <= 4 * 256) {
+    p->store = kStQuad;
+    p->rstep = 256 / qpr;
+  } else if (p->vec4) {
+    p->store = (S * A) % 4 ? kStVec4Tail : kStVec4;
+  } else {
+    p->store = kStElem;
+  }
+  return BSIG_OK;
+}
+
+static int signature_path(int64_t n, int length, int sd, int ad, int depth, int64_t ld_out,
+                          bool out_align16, SumPath* p) {
+  BSIG_REQUIRE(n >= 0 && length >= 2 && sd >= 1 && ad >= 1,
+               "signature: bad dims length=%d sd=%d ad=%d", length, sd, ad);
+  const int d = 1 + sd + ad;
+  if (depth <= 0) depth = ref_signature_depth(d);
+  BSIG_REQUIRE(depth >= 1 && depth <= 3, "signature: depth %d not in 1..3", depth);
+  BSIG_REQUIRE(ld_out >= bsig_summary_dim(3, length, sd, ad, depth),
+               "signature: ld_out too small");
+  p->depth = depth;
+  p->steps = length;
+  p->grid = grid_for(n);
+  if (depth == 3) {
+    if (d > 32) {
+      set_error("signature: depth 3 needs path dim <= 32 (got %d)", d);
+      return BSIG_EUNSUPPORTED;
+    }
+    const size_t lds = ((size_t)((length * d + 3) & ~3) + (size_t)(length - 1) * ((d + 3) & ~3) +
+                        (size_t)d * d * d + 4) * sizeof(float);
+    if (lds > 150 * 1024) {
+      set_error("signature: %zu B of LDS needed", lds);
+      return BSIG_EUNSUPPORTED;
+    }
+    p->kernel = kKSig3;
+    p->lds = lds;
+    p->threads = (int)round_up<int64_t>((int64_t)d * d, 64);
+    p->dmax = d <= 8 ? 8 : (d <= 16 ? 16 : (d <= 24 ? 24 : 32));
+    p->prefetch = length * sd <= p->threads && length * ad <= p->threads;   // signature3_kernel's pf_ok
+    p->store = (ld_out & 3) == 0 && out_align16 ? kStLine : kStElem;
+    return BSIG_OK;
+  }
+  size_t lds = 0;
+  if (depth == 2) {
+    lds = (size_t)length * d * sizeof(float);
+    if (lds > 150 * 1024) {
+      set_error("signature: %zu B of LDS needed", lds);
+      return BSIG_EUNSUPPORTED;
+    }
+  }
+  p->kernel = kKSig12;
+  p->store = kStElem;
+  p->lds = lds;
+  p->threads = 256;
+  return BSIG_OK;
+}
+
+// bsig_crosscorr_expand's grid for rows of `total` floats
+static dim3 expand_grid(int total, int64_t n) {
+  return dim3(std::min(ceil_div(total, 256), 64), (unsigned)std::min<int64_t>(n, 16384));
+}
+}  // namespace bsig
+
+extern "C" int bsig_summary_start(const float* states, const float* actions, float* out,
+                                  int64_t n, int t_states, int t_actions, int sd, int ad,
+                                  int max_t, int64_t ld_out, bsig_stream_t stream) {
+  bsig::Range roctx_range("bsig_summary_start");
+  if (n == 0) return BSIG_OK;
+  BSIG_REQUIRE(states && actions && out, "summary_start: null pointer");
+  SumPath p;
+  BSIG_TRY(start_path(n, t_states, t_actions, sd, ad, max_t, ld_out, &p));
+  hipLaunchKernelGGL((summary_start_kernel<10>), dim3(p.grid), dim3(p.threads), 0,
+                     as_stream(stream), states, actions, out, n, t_states, t_actions, sd,
+                     ad, max_t, ld_out);
+  BSIG_CHECK_LAUNCH("summary_start");
+  return BSIG_OK;
+}
+
+namespace bsig {
 // the materialised summary (`out`), its factors (`fac`), or both
 static int crosscorr_launch(const float* states, const float* actions, float* out, int64_t ld_out,
                             float* fac, int64_t ld_fac, int64_t n, int t_states, int t_actions,
@@ -641,47 +766,30 @@ static int crosscorr_launch(const float* states, const float* actions, float* ou
                             hipStream_t st) {
   if (n == 0) return BSIG_OK;
   BSIG_REQUIRE(states && actions && (out || fac), "crosscorr: null pointer");
-  BSIG_REQUIRE(n >= 0 && sd >= 2 && ad >= 1, "crosscorr: bad dims sd=%d ad=%d", sd, ad);
-  BSIG_REQUIRE(t_states > 1, "crosscorr: traj_len must be > 1 (summarizers.py:94)");
-  BSIG_REQUIRE(t_actions >= 1, "crosscorr: no actions");
-  const int w = crosscorr_window(t_states, sd);
-  const int64_t S = (int64_t)w * (sd - 1), A = (int64_t)w * ad;
-  BSIG_REQUIRE(!out || ld_out >= S * A + 2, "crosscorr: ld_out too small");
-  BSIG_REQUIRE(!fac || ld_fac >= S + A + 3, "crosscorr: ld_factors too small (need S + A + 3 = %lld)",
-               (long long)(S + A + 3));
-  const size_t lds = (size_t)(S + A + 8) * sizeof(float);
-  if (lds > 150 * 1024) {
-    set_error("crosscorr: %zu B of LDS needed", lds);
-    return BSIG_EUNSUPPORTED;
-  }
-  if (S * A <= 2048 && (S + A) * 4 * sizeof(float) <= 32 * 1024) {
-    const int64_t blocks = ceil_div<int64_t>(n, 4);
-    hipLaunchKernelGGL(crosscorr_wave_kernel, dim3((int)std::min<int64_t>(blocks, 65536)),
-                       dim3(256), (size_t)(S + A) * 4 * sizeof(float), st, states,
-                       actions, out, n, t_states, t_actions, sd, ad, w, use_state_diff, ld_out,
-                       nonfinite, fac, ld_fac);
-    BSIG_CHECK_LAUNCH("crosscorr_wave");
-    return BSIG_OK;
-  }
-  const int vec4 = out && (ld_out % 4 == 0) && aligned(out, 16);
-  // the materialised summary alone, quads of action features: the lean streaming kernel
-  if (out && !fac && vec4 && (A & 3) == 0 && sd - 1 <= 256 && ad <= 256 && w <= 10 &&
-      getenv("BSIG_CC_GENERAL") == nullptr) {
-    const int qpr = (int)(A >> 2);
-    int m8 = 8; for (int g = qpr; (g & 1) == 0 && m8 > 1; g >>= 1) m8 >>= 1;   // 8 / gcd(qpr, 8)
-    const int rstep = (256 / qpr) / m8 * m8;
-    if (rstep >= 1 && S * qpr >= 512) {
-      hipLaunchKernelGGL(crosscorr_quads_kernel, dim3(grid_for(n)), dim3(256), lds, st, states, actions,
-                         out, n, t_states, t_actions, sd, ad, w, use_state_diff, ld_out, rstep, nonfinite);
+  SumPath p;
+  BSIG_TRY(crosscorr_path(n, t_states, t_actions, sd, ad, out != nullptr, ld_out, aligned(out, 16),
+                          fac != nullptr, ld_fac, &p));
+  const int w = p.steps;
+  switch (p.kernel) {
+    case kKCcWave:
+      hipLaunchKernelGGL(crosscorr_wave_kernel, dim3(p.grid), dim3(p.threads), p.lds, st, states,
+                         actions, out, n, t_states, t_actions, sd, ad, w, use_state_diff, ld_out,
+                         nonfinite, fac, ld_fac);
+      BSIG_CHECK_LAUNCH("crosscorr_wave");
+      return BSIG_OK;
+    case kKCcQuads:
+      hipLaunchKernelGGL(crosscorr_quads_kernel, dim3(p.grid), dim3(p.threads), p.lds, st, states,
+                         actions, out, n, t_states, t_actions, sd, ad, w, use_state_diff, ld_out,
+                         p.rstep, nonfinite);
       BSIG_CHECK_LAUNCH("crosscorr_quads");
       return BSIG_OK;
-    }
+    default:
+      hipLaunchKernelGGL(crosscorr_kernel, dim3(p.grid), dim3(p.threads), p.lds, st,
+                         states, actions, out, n, t_states, t_actions, sd, ad, w,
+                         use_state_diff, ld_out, p.vec4, nonfinite, fac, ld_fac);
+      BSIG_CHECK_LAUNCH("crosscorr");
+      return BSIG_OK;
   }
-  hipLaunchKernelGGL(crosscorr_kernel, dim3(grid_for(n)), dim3(256), lds, st,
-                     states, actions, out, n, t_states, t_actions, sd, ad, w,
-                     use_state_diff, ld_out, vec4, nonfinite, fac, ld_fac);
-  BSIG_CHECK_LAUNCH("crosscorr");
-  return BSIG_OK;
 }
 
 // out[r, i*A + j] = sf[i] * af[j], out[r, S*A] = mean, out[r, S*A + 1] = std  from factor rows
@@ -738,10 +846,8 @@ extern "C" int bsig_crosscorr_expand(const float* factors, int64_t ld_factors, i
   BSIG_REQUIRE(factors && out && n >= 0 && s_dim >= 1 && a_dim >= 1, "crosscorr_expand: bad args");
   BSIG_REQUIRE(ld_factors >= s_dim + a_dim + 3 && ld_out >= (int64_t)s_dim * a_dim + 2,
                "crosscorr_expand: leading dims too small");
-  const int total = s_dim * a_dim + 2;
-  const dim3 grid(std::min(ceil_div(total, 256), 64), (unsigned)std::min<int64_t>(n, 16384));
-  hipLaunchKernelGGL(crosscorr_expand_kernel, grid, dim3(256), 0, as_stream(stream), factors,
-                     ld_factors, n, s_dim, a_dim, out, ld_out);
+  hipLaunchKernelGGL(crosscorr_expand_kernel, expand_grid(s_dim * a_dim + 2, n), dim3(256), 0,
+                     as_stream(stream), factors, ld_factors, n, s_dim, a_dim, out, ld_out);
   BSIG_CHECK_LAUNCH("crosscorr_expand");
   return BSIG_OK;
 }
@@ -752,51 +858,50 @@ extern "C" int bsig_signature(const float* states, const float* actions, float* 
   bsig::Range roctx_range("bsig_signature");
   if (n == 0) return BSIG_OK;
   BSIG_REQUIRE(states && actions && out, "signature: null pointer");
-  BSIG_REQUIRE(n >= 0 && length >= 2 && sd >= 1 && ad >= 1,
-               "signature: bad dims length=%d sd=%d ad=%d", length, sd, ad);
-  const int d = 1 + sd + ad;
-  if (depth <= 0) depth = ref_signature_depth(d);
-  BSIG_REQUIRE(depth >= 1 && depth <= 3, "signature: depth %d not in 1..3", depth);
-  BSIG_REQUIRE(ld_out >= bsig_summary_dim(3, length, sd, ad, depth),
-               "signature: ld_out too small");
-  if (n == 0) return BSIG_OK;
-  if (depth == 3) {
-    if (d > 32) {
-      set_error("signature: depth 3 needs path dim <= 32 (got %d)", d);
-      return BSIG_EUNSUPPORTED;
-    }
-    const size_t lds = ((size_t)((length * d + 3) & ~3) + (size_t)(length - 1) * ((d + 3) & ~3) +
-                        (size_t)d * d * d + 4) * sizeof(float);
-    if (lds > 150 * 1024) {
-      set_error("signature: %zu B of LDS needed", lds);
-      return BSIG_EUNSUPPORTED;
-    }
-    const int threads = (int)round_up<int64_t>((int64_t)d * d, 64);
-    if (d <= 8)
-      hipLaunchKernelGGL((signature3_kernel<8>), dim3(grid_for(n)), dim3(threads), lds,
-                         as_stream(stream), states, actions, out, n, length, sd, ad, ld_out);
-    else if (d <= 16)
-      hipLaunchKernelGGL((signature3_kernel<16>), dim3(grid_for(n)), dim3(threads), lds,
-                         as_stream(stream), states, actions, out, n, length, sd, ad, ld_out);
-    else if (d <= 24)
-      hipLaunchKernelGGL((signature3_kernel<24>), dim3(grid_for(n)), dim3(threads), lds,
-                         as_stream(stream), states, actions, out, n, length, sd, ad, ld_out);
-    else
-      hipLaunchKernelGGL((signature3_kernel<32>), dim3(grid_for(n)), dim3(threads), lds,
-                         as_stream(stream), states, actions, out, n, length, sd, ad, ld_out);
-  } else {
-    size_t lds = 0;
-    if (depth == 2) {
-      lds = (size_t)length * d * sizeof(float);
-      if (lds > 150 * 1024) {
-        set_error("signature: %zu B of LDS needed", lds);
-        return BSIG_EUNSUPPORTED;
-      }
-    }
-    hipLaunchKernelGGL(signature12_kernel, dim3(grid_for(n)), dim3(256), lds,
-                       as_stream(stream), states, actions, out, n, length, sd, ad, depth,
-                       ld_out);
-  }
+  SumPath p;
+  BSIG_TRY(signature_path(n, length, sd, ad, depth, ld_out, aligned(out, 16), &p));
+  const dim3 grid(p.grid), block(p.threads);
+  const hipStream_t st = as_stream(stream);
+  if (p.kernel == kKSig12)
+    hipLaunchKernelGGL(signature12_kernel, grid, block, p.lds, st, states, actions, out, n, length,
+                       sd, ad, p.depth, ld_out);
+  else if (p.dmax == 8)
+    hipLaunchKernelGGL((signature3_kernel<8>), grid, block, p.lds, st, states, actions, out, n,
+                       length, sd, ad, ld_out);
+  else if (p.dmax == 16)
+    hipLaunchKernelGGL((signature3_kernel<16>), grid, block, p.lds, st, states, actions, out, n,
+                       length, sd, ad, ld_out);
+  else if (p.dmax == 24)
+    hipLaunchKernelGGL((signature3_kernel<24>), grid, block, p.lds, st, states, actions, out, n,
+                       length, sd, ad, ld_out);
+  else
+    hipLaunchKernelGGL((signature3_kernel<32>), grid, block, p.lds, st, states, actions, out, n,
+                       length, sd, ad, ld_out);
   BSIG_CHECK_LAUNCH("signature");
+  return BSIG_OK;
+}
+
+extern "C" int bsig_debug_summary_path(int kind, int64_t n, int t_states, int t_actions, int sd,
+                                       int ad, int depth, int max_t, int64_t ld_out, int out_align16,
+                                       int factors, int32_t* out) {
+  BSIG_REQUIRE(out, "summary path: null pointer");
+  for (int i = 0; i < 16; ++i) out[i] = 0;
+  BSIG_REQUIRE(n >= 1, "summary path: bad n=%lld", (long long)n);
+  SumPath p;
+  dim3 ex(0, 0);
+  if (kind == 0) {
+    BSIG_TRY(start_path(n, t_states, t_actions, sd, ad, max_t, ld_out, &p));
+  } else if (kind == 1 || kind == 2) {
+    BSIG_TRY(crosscorr_path(n, t_states, t_actions, sd, ad, !factors, factors ? 0 : ld_out,
+                            out_align16 != 0, factors != 0, factors ? ld_out : 0, &p));
+    ex = expand_grid(p.steps * (sd - 1) * p.steps * ad + 2, n);
+  } else if (kind == 3) {
+    BSIG_TRY(signature_path(n, t_states, sd, ad, depth, ld_out, out_align16 != 0, &p));
+  } else {
+    BSIG_REQUIRE(false, "summary path: bad kind %d", kind);
+  }
+  out[0] = p.kernel; out[1] = p.store; out[2] = p.prefetch; out[3] = p.threads;
+  out[4] = (int32_t)p.lds; out[5] = p.grid; out[6] = p.rstep; out[7] = p.dmax;
+  out[8] = p.steps; out[9] = p.depth; out[10] = (int32_t)ex.x; out[11] = (int32_t)ex.y;
   return BSIG_OK;
 }

@@ -94,6 +94,22 @@ int bsig_signature(const float* states, const float* actions, float* out,
                    int64_t n, int length, int sd, int ad, int depth,
                    int64_t ld_out, bsig_stream_t stream);
 
+/* Diagnostics / tests: the device path a summarizer launch takes for this shape -- host arithmetic
+ * only, no device is asked.  kind as bsig_summary_dim (kind 3: t_states is the path length; kind 0:
+ * max_t steps).  ld_out is the output pitch (kinds 1, 2 with factors != 0: the factor-row pitch of
+ * bsig_crosscorr_factors), out_align16 whether the output base is 16-byte aligned.
+ * out[16] = { kernel (0: summary_start, 1: crosscorr wave, 2: crosscorr quads, 3: crosscorr
+ * workgroup, 4: signature depth 3, 5: signature depth 1-2), store (0: one float per thread,
+ * 1: a quad of action features per thread, 2: generic float4, 3: generic float4 + scalar tail,
+ * 4: line-aligned float4 runs, 5: factor rows only), register prefetch of the next trajectory
+ * (1) or fetch in place (0), threads per workgroup, LDS bytes, workgroups, rows per sweep of the
+ * quad store (0 otherwise), DMAX of the depth-3 kernel (0 otherwise), steps W / max_t / length,
+ * signature depth, bsig_crosscorr_expand's x and y workgroups for factor rows of this shape, 0... }.
+ * Returns BSIG_OK, or the code a launch of a refused shape returns (out all zero). */
+int bsig_debug_summary_path(int kind, int64_t n, int t_states, int t_actions, int sd, int ad,
+                            int depth, int max_t, int64_t ld_out, int out_align16, int factors,
+                            int32_t* out);
+
 /* ------------------------------------------------------------------ */
 /* fp32 MFMA GEMM with fused epilogues (v_mfma_f32_32x32x2_f32)        */
 /* C[m,n] = epi( sum_k A(m,k) * B(n,k) )                               */

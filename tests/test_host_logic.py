@@ -12,6 +12,7 @@ import torch
 
 from conftest import ROOT, golden
 import head_cases as H
+import summary_cases as S
 
 import bayes_sim_ig_amd as B
 from bayes_sim_ig_amd import _lib, pdf
@@ -470,3 +471,186 @@ def test_head_full_covariance_lds_limit():
     hd = _lib.HeadDims()
     hd.out_dim, hd.n_comp, hd.full_cov = 48, 10, 1
     assert _lib.load().bsig_head_workspace_bytes(ctypes.byref(hd), 4) == 0
+
+
+# ------------------------------------------------ summarizer paths (host arithmetic)
+def summary_path(*args):
+    """bsig_debug_summary_path: (return code, dict of its outputs)"""
+    out = (ctypes.c_int32 * 16)(*([-1] * 16))
+    rc = _lib.load().bsig_debug_summary_path(*args, out)
+    assert list(out)[len(S.PATH_FIELDS):] == [0] * (16 - len(S.PATH_FIELDS))
+    return rc, dict(zip(S.PATH_FIELDS, list(out)))
+
+
+@pytest.mark.parametrize('case', S.CASES, ids=[S.case_id(c) for c in S.CASES])
+def test_summary_case_table_resolves_to_its_path(case):
+    rc, p = summary_path(*S.query_args(case))
+    assert rc == 0, _lib.load().bsig_last_error()
+    assert (p['kernel'], p['store'], p['prefetch']) == (case.kernel, case.store, case.prefetch), p
+    for k, v in case.want.items():
+        assert p[k] == v, (k, p)
+    n = case.n
+    if case.kernel == S.K_WAVE:
+        s, a = S.dims(case)
+        assert (p['threads'], p['lds'], p['grid']) == (256, 16 * (s + a), min(-(-n // 4), 65536))
+    else:
+        assert p['grid'] == min(n, S.GRID_CAP) and p['threads'] % 64 == 0
+    if case.kind in (S.CORR, S.CORRDIFF):
+        s, a = S.dims(case)
+        assert p['steps'] == S.window(case.t, case.sd)
+        assert (p['ex_x'], p['ex_y']) == (min(-(-(s * a + 2) // 256), 64), min(n, S.GRID_CAP))
+        if case.kernel != S.K_WAVE:
+            assert p['threads'] == 256 and p['lds'] == 4 * (s + a + 8)
+        assert (p['rstep'] > 0) == (case.store == S.ST_QUAD)
+        if case.kernel == S.K_QUADS:     # 128-byte runs: rstep A/4 quads a multiple of 8
+            assert p['rstep'] * (a // 4) % 8 == 0 and p['rstep'] * (a // 4) <= 256
+    elif case.kind == S.SIG:
+        d = 1 + case.sd + case.ad
+        assert p['depth'] == S.sig_depth(case) and p['steps'] == case.t
+        if case.kernel == S.K_SIG3:
+            assert p['threads'] == -(-d * d // 64) * 64 and p['dmax'] >= d > p['dmax'] - 8
+            assert p['prefetch'] == (case.t * case.sd <= p['threads'] and case.t * case.ad <= p['threads'])
+    else:
+        assert p['steps'] == case.max_t
+
+
+def test_summary_case_table_covers_every_path():
+    """The GPU summarizer tests' case table reaches every kernel, store loop and fetch, the
+    boundaries between them, and a second trajectory per workgroup on each grid-striding path."""
+    got = {(c.kernel, c.store, c.prefetch) for c in S.CASES}
+    assert got >= {(S.K_START, S.ST_ELEM, 0), (S.K_WAVE, S.ST_ELEM, 0), (S.K_WAVE, S.ST_FACTORS, 0),
+                   (S.K_QUADS, S.ST_QUAD, 1)} | \
+        {(S.K_CC, st, pf) for st in (S.ST_QUAD, S.ST_VEC4_TAIL, S.ST_FACTORS) for pf in (0, 1)} | \
+        {(S.K_CC, st, 1) for st in (S.ST_VEC4, S.ST_ELEM)} | \
+        {(S.K_SIG3, st, 1) for st in (S.ST_LINE, S.ST_ELEM)} | \
+        {(S.K_SIG3, S.ST_LINE, 0), (S.K_SIG12, S.ST_ELEM, 0)}
+    assert {8, 16, 24, 32} <= {c.want.get('dmax') for c in S.CASES}
+    assert {c.want['threads'] for c in S.CASES if c.kind == S.START} == {64, 128, 256}
+    assert {1, 2} <= {S.sig_depth(c) for c in S.CASES if c.kernel == S.K_SIG12}
+    assert {1, 8, 24, 128, 256} <= {c.want.get('rstep') for c in S.CASES if c.kernel == S.K_QUADS}
+    assert any(c.max_t != 10 for c in S.CASES if c.kind == S.START)
+    assert any(c.t != c.ta for c in S.CASES if c.kind == S.START)
+    big = {(c.kernel, c.store, c.prefetch) for c in S.CASES if c.n > S.GRID_CAP}
+    assert big >= {(c.kernel, c.store, c.prefetch) for c in S.CASES
+                   if c.kernel in (S.K_QUADS, S.K_CC, S.K_SIG3)}
+    assert any(c.n >= S.N_WAVE for c in S.CASES if c.kernel == S.K_WAVE and not c.factors)
+    assert any(c.n >= S.N_WAVE for c in S.CASES if c.kernel == S.K_WAVE and c.factors)
+    # the wide factor rows whose expansion grid-strides in x (S A + 2 > 64 x 256), and in y
+    assert any(c.factors and S.dims(c)[0] * S.dims(c)[1] + 2 > 64 * 256 for c in S.CASES)
+    assert any(c.factors and c.n > S.GRID_CAP for c in S.CASES)
+
+
+def _cc_case(t, sd, ad, n=5, **kw):
+    return S.C('x', S.CORRDIFF, n, t, t, sd, ad, 0, 0, 0, **kw)
+
+
+@pytest.mark.parametrize('shape,want', [
+    ((4, 129, 1), S.K_WAVE), ((4, 130, 1), S.K_QUADS),          # S A = 2048 | 2064
+    ((8, 33, 1), S.K_WAVE), ((8, 34, 1), S.K_QUADS),            # S A = 2048 | 2112
+    ((6, 257, 4), S.K_QUADS), ((6, 258, 4), S.K_CC),            # sd - 1 = 256 | 257
+    ((3, 3, 256), S.K_QUADS), ((3, 3, 257), S.K_CC),            # ad = 256 | 257
+    ((3, 3, 300), S.K_CC), ((11, 300, 2), S.K_CC)])
+def test_crosscorr_path_boundaries(shape, want):
+    c = _cc_case(*shape)
+    rc, p = summary_path(*S.query_args(c))
+    assert rc == 0 and p['kernel'] == want, (shape, p)
+    s, a = S.dims(c)
+    if want == S.K_WAVE:
+        assert s * a == 2048
+    else:
+        assert s * a > 2048 and p['prefetch'] == (c.sd - 1 <= 256 and c.ad <= 256)
+    # factor rows never take the quads kernel; a misaligned or odd pitch drops the float4 stores
+    rc, p = summary_path(*S.query_args(c._replace(factors=True)))
+    assert rc == 0 and p['kernel'] == (S.K_WAVE if want == S.K_WAVE else S.K_CC)
+    assert p['store'] == S.ST_FACTORS
+    for odd in (c._replace(off=1), c._replace(pad=1 if (S.width(c) + 1) % 4 else 2)):
+        rc, p = summary_path(*S.query_args(odd))
+        assert rc == 0 and (p['kernel'], p['store']) == \
+            ((S.K_WAVE, S.ST_ELEM) if want == S.K_WAVE else (S.K_CC, S.ST_ELEM)), (odd, p)
+
+
+def test_crosscorr_quads_rstep_boundaries():
+    """rstep = (256 / (A/4)) rounded down to a multiple of 8 / gcd(A/4, 8): 1 at A/4 = 136, 0 (the
+    workgroup kernel's quad store, 256 / (A/4) rows per sweep) at A/4 = 35 and 150."""
+    for shape, kernel, rstep in [((8, 3, 68), S.K_QUADS, 1), ((21, 8, 14), S.K_CC, 7),
+                                 ((21, 3, 60), S.K_CC, 1), ((4, 130, 1), S.K_QUADS, 256),
+                                 ((51, 60, 8), S.K_QUADS, 24), ((21, 48, 12), S.K_QUADS, 8)]:
+        rc, p = summary_path(*S.query_args(_cc_case(*shape)))
+        assert rc == 0 and (p['kernel'], p['store'], p['rstep']) == (kernel, S.ST_QUAD, rstep), shape
+
+
+def test_crosscorr_generic_store_boundaries():
+    # A % 4 != 0: generic float4 loop; its scalar tail exactly when S A % 4 != 0
+    for shape, store in [((21, 25, 1), S.ST_VEC4), ((5, 52, 3), S.ST_VEC4_TAIL),
+                         ((21, 20, 110), S.ST_VEC4), ((21, 20, 102), S.ST_QUAD),   # A = 1100 | 1020
+                         ((3, 3, 257), S.ST_VEC4_TAIL)]:
+        c = _cc_case(*shape)
+        rc, p = summary_path(*S.query_args(c))
+        s, a = S.dims(c)
+        assert rc == 0 and (p['kernel'], p['store']) == (S.K_CC, store), (shape, p)
+        assert (store == S.ST_VEC4_TAIL) == ((s * a) % 4 != 0)
+
+
+@pytest.mark.parametrize('width,threads', [(95, 64), (96, 128), (191, 128), (192, 256)])
+def test_summary_start_thread_boundaries(width, threads):
+    for max_t in (1, 10, 23):
+        rc, p = summary_path(S.START, 3, 5, 7, width - 2, 2, 0, max_t, max_t * width, 1, 0)
+        assert rc == 0 and (p['kernel'], p['threads'], p['steps']) == (S.K_START, threads, max_t)
+
+
+def test_signature_dmax_and_fetch_boundaries():
+    for d, dmax in [(8, 8), (9, 16), (16, 16), (17, 24), (24, 24), (25, 32), (32, 32)]:
+        c = S.C('x', S.SIG, 3, 4, 4, d - 3, 2, 0, 0, 0, depth=3)
+        rc, p = summary_path(*S.query_args(c))
+        assert rc == 0 and (p['kernel'], p['dmax'], p['threads']) == \
+            (S.K_SIG3, dmax, -(-d * d // 64) * 64), d
+    # L sd against the thread count: 64 prefetches, 65 is fetched in place (and L ad alike)
+    for t, sd, ad, pf in [(16, 4, 3, 1), (13, 5, 2, 0), (16, 3, 4, 1), (13, 2, 5, 0)]:
+        rc, p = summary_path(*S.query_args(S.C('x', S.SIG, 3, t, t, sd, ad, 0, 0, 0)))
+        assert rc == 0 and (p['threads'], p['prefetch']) == (64, pf), (t, sd, ad)
+    # default depth: 3 up to d = 22, 2 from d = 23 (the depth-2 kernel), 1 past d = 110
+    for d, kernel, depth in [(22, S.K_SIG3, 3), (23, S.K_SIG12, 2), (110, S.K_SIG12, 2),
+                             (111, S.K_SIG12, 1)]:
+        rc, p = summary_path(*S.query_args(S.C('x', S.SIG, 3, 5, 5, d - 3, 2, 0, 0, 0)))
+        assert rc == 0 and (p['kernel'], p['depth']) == (kernel, depth), d
+
+
+@pytest.mark.parametrize('name,kind,t,sd,ad,depth,factors', S.REFUSED, ids=[r[0] for r in S.REFUSED])
+def test_refused_summary_shapes(name, kind, t, sd, ad, depth, factors):
+    """Each refusal: BSIG_EUNSUPPORTED from the query (out all zero) and from the C entry point,
+    before it touches the device; one step short of it the shape resolves."""
+    lib = _lib.load()
+    fake = ctypes.c_void_p(4096)
+    c = S.C(name, kind, 4, t, t, sd, ad, 0, 0, 0, depth=depth, factors=factors)
+    rc, p = summary_path(*S.query_args(c))
+    assert rc == _lib.BSIG_EUNSUPPORTED and all(v == 0 for v in p.values()), p
+    assert ('LDS' in lib.bsig_last_error().decode()) == ('lds' in name)
+    ld = S.pitch(c)
+    if kind == S.SIG:
+        rc = lib.bsig_signature(fake, fake, fake, 4, t, sd, ad, depth, ld, None)
+    elif factors:
+        rc = lib.bsig_crosscorr_factors(fake, fake, fake, 4, t, t, sd, ad, 0, ld, None, None)
+    else:
+        rc = lib.bsig_crosscorr(fake, fake, fake, 4, t, t, sd, ad, 1, ld, None, None)
+    assert rc == _lib.BSIG_EUNSUPPORTED
+    if 'lds' in name:
+        smaller = c._replace(t=t - 1) if kind == S.SIG else c._replace(sd=sd - 1)
+        rc, p = summary_path(*S.query_args(smaller))
+        assert rc == 0 and p['lds'] <= 150 * 1024, p
+    else:
+        rc, p = summary_path(*S.query_args(c._replace(ad=ad - 1)))
+        assert rc == 0 and p['dmax'] == 32
+
+
+def test_summary_path_argument_errors():
+    lib = _lib.load()
+    rc, p = summary_path(*S.query_args(S.CASES[0], n=0))
+    assert rc == _lib.BSIG_EINVAL and all(v == 0 for v in p.values())
+    rc, _ = summary_path(4, 3, 5, 5, 3, 1, 0, 10, 64, 1, 0)
+    assert rc == _lib.BSIG_EINVAL and 'kind' in lib.bsig_last_error().decode()
+    c = _cc_case(21, 4, 1)
+    rc, _ = summary_path(*S.query_args(c._replace(pad=-3)))            # pitch < S A + 2
+    assert rc == _lib.BSIG_EINVAL and 'ld_out' in lib.bsig_last_error().decode()
+    rc, _ = summary_path(*S.query_args(c._replace(t=1, ta=1)))
+    assert rc == _lib.BSIG_EINVAL and 'traj_len' in lib.bsig_last_error().decode()
+    assert lib.bsig_debug_summary_path(0, 3, 5, 5, 3, 1, 0, 10, 64, 1, 0, None) == _lib.BSIG_EINVAL
