@@ -7,6 +7,7 @@ streams and torch.distributed.
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -50,6 +51,29 @@ class FitBuffers(C.Structure):
                 ('state', vp), ('workspace', vp), ('workspace_bytes', sz),
                 ('x_kind', i32), ('x_s', i32), ('x_a', i32),
                 ('x_test_factors', vp), ('ldx_test_factors', i64)]
+
+
+# bsig_fit_chunk (include/bsig.h): one entry per chunk of a block launch, 64 bytes
+FIT_CHUNK = np.dtype([('row0', '<i8'), ('n_train', '<i4'), ('n_test', '<i4'), ('ids_off', '<i8'),
+                      ('seed', '<u8'), ('rng_ctr0', '<u8'), ('n_updates', '<i4'), ('eval_every', '<i4'),
+                      ('train_slot', '<i4'), ('test_slot', '<i4'), ('upd_base', '<i4'), ('eval_base', '<i4')])
+
+
+def fit_chunk_table(sizes, seeds, n_updates, batch_size, test_frac):
+    """The chunk table of a block launch (bsig_fit_run_block) for consecutive chunks of ``sizes`` pairs:
+    rows and ids of the chunks follow each other, every chunk holds out its last rows (mdnn.py:206-211),
+    evaluates every max(n_updates // 5, 1) updates and after the last (mdnn.py:235), starts its jitter
+    streams at 1 with its own seed (what bsig_fit_begin does per call) and logs behind the chunk before."""
+    every = max(n_updates // 5, 1)
+    n_evals = len([it for it in range(n_updates) if it % every == 0 or it + 1 == n_updates])
+    table = np.zeros(len(sizes), dtype=FIT_CHUNK)
+    row0 = 0
+    for c, (n_tot, seed) in enumerate(zip(sizes, seeds)):
+        n_train = max(int(n_tot * (1.0 - test_frac)), 1)
+        table[c] = (row0, n_train, n_tot - n_train, c * n_updates * batch_size, seed, 1, n_updates, every,
+                    c * n_updates, c * n_evals, c * n_updates, c * n_evals)
+        row0 += n_tot
+    return table
 
 
 _PROTOS = {
@@ -133,6 +157,9 @@ _PROTOS = {
     'bsig_comm_broadcast': (C.c_int, [vp, vp, i64, C.c_int, vp]),
     'bsig_comm_destroy': (None, [vp]),
     'bsig_fit_pack_logs': (C.c_int, [vp, i64, vp, vp]),
+    'bsig_fit_block_chunks': (C.c_int, [vp, i64]),
+    'bsig_fit_run_block': (C.c_int, [vp, vp, i64, i64, vp, i64, vp, i64, vp, vp, C.c_int, vp, vp, vp, i64, vp]),
+    'bsig_debug_block_launch': (C.c_int, [C.c_int, C.c_int, C.c_int]),
     'bsig_fit_run_dp': (C.c_int, [vp, vp, i64, vp, vp]),
 }
 COMM_ID_BYTES = 128

@@ -140,14 +140,16 @@ class BayesSim(object):
             # A rank that stayed resident across the exchange first goes back to one launch per update
             # (MDNN._give_up_a_level), the per-phase kernels come second.
             from .mdnn import PersistentTimeout
+            # A model that ran blocks of chunks in one launch first goes back to one launch per chunk.
             snap = self.model._snapshot()
             for _ in range(2):
                 calls0 = self.model._resident_calls()
+                blocks0 = getattr(self.model, '_block_launches', 0)
                 try:
                     return self._fit_once(params, traj_states, traj_actions)
                 except PersistentTimeout:
                     self.model._restore(snap)
-                    self.model._give_up_a_level(calls0)
+                    self.model._give_up_a_level(calls0, blocks0)
         return self._fit_once(params, traj_states, traj_actions)
 
     def _fit_once(self, params, traj_states, traj_actions):
@@ -181,6 +183,22 @@ class BayesSim(object):
                 lo, hi = done, min(n, done + block)
                 summ = self._summarize(traj_states[lo:hi], traj_actions[lo:hi], flag, lazy=True)
                 feats = self.model.rff.to_features(summ) if is_rff else None
+                if feats is not None and dp is None:
+                    # the block's chunks in ONE launch of the persistent update kernel, where the model's
+                    # plan can (else: chunk by chunk below; a chunk without a held-out row runs on its own)
+                    sizes, at = [], lo
+                    while at < hi:
+                        sizes.append(BayesSim.get_n_trajs_per_batch(n, at))
+                        at += sizes[-1]
+                    sizes = sizes[:self.model.block_prefix(sizes, BayesSim.TEST_FRACTION)]
+                    rows = sum(sizes)
+                    logs = self.model.run_training_block(
+                        feats[:rows], params[lo:lo + rows], sizes, BayesSim.NUM_GRAD_UPDATES,
+                        BayesSim.MINIBATCH_SIZE, BayesSim.TEST_FRACTION) if sizes else None
+                    if logs is not None:
+                        pending.extend(logs)
+                        done += rows
+                        continue
             if block:
                 pending.append(self.run_training(
                     params[done:done + m], None, None, _defer=True,

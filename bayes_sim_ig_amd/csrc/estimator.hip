@@ -470,9 +470,13 @@ static PersistMdnnShape persist_mdnn_shape(const bsig_fit_plan* p) {
 // update whose gradients go to the flat gradient buffer, after the pending Adam step of the previous
 // one; n = 0 flushes that step.  eval_total > 0: the launch belongs to a call of eval_total updates
 // whose held-out evaluations run inside the launches.  xr: the whole call in one launch, resident
-// across the exchange (persist.h).
+// across the exchange (persist.h).  blk: a block of chunks in one launch (bsig_fit_run_block), n the updates of a chunk.
+struct BlockRun {
+  const float* feats; int64_t ld_feats; const float* y; int64_t ldy; const int32_t* ids;
+  const bsig_fit_chunk* chunks; int n_chunks, max_test, total_updates; float* train_loss; float* test_loss;
+};
 static int enqueue_persistent(bsig_fit_plan* p, int n, hipStream_t st, int eval_total = 0,
-                              const CommXr* xr = nullptr) {
+                              const CommXr* xr = nullptr, const BlockRun* blk = nullptr) {
   PlanMem m; plan_mem(p, &m);
   const bsig_fit_buffers& b = p->buf;
   PersistCommon c;
@@ -501,6 +505,13 @@ static int enqueue_persistent(bsig_fit_plan* p, int n, hipStream_t st, int eval_
     pb.feat_ids = p->feat_unique ? b.ids_table : nullptr;
     pb.w_off = p->L.head_w_off; pb.b_off = p->L.head_b_off;
     pb.eval_row0 = p->feat_unique ? b.n_train : p->n_updates * p->batch;  // as eval_inputs()
+    if (blk) {
+      pb.feats = blk->feats; pb.ld_feats = blk->ld_feats; pb.feat_ids = blk->ids; pb.eval_row0 = 0;
+      pb.y = blk->y; pb.ldy = blk->ldy; pb.ids = blk->ids;
+      pb.train_loss = blk->train_loss; pb.test_loss = blk->test_loss;
+      pb.y_test = blk->y; pb.ldy_test = blk->ldy; pb.n_test = blk->max_test;
+      pb.chunks = blk->chunks; pb.n_chunks = blk->n_chunks;
+    }
     return persist_run(persist_shape(p), p->ug, pb, n, st);
   }
   PersistMdnnBuffers pb;
@@ -808,6 +819,7 @@ extern "C" int bsig_fit_create_ex(const bsig_mdn_cfg* cfg, int64_t batch,
       persist_mdnn_resolve(persist_mdnn_shape(p), &p->mg, &p->eng);
   }
   if (set("BSIG_NO_INKERNEL_EVAL")) p->eng.eval_single = p->eng.eval_dp = false;
+  p->eng.block_launch = block_launch_resolved(p->eng.kind, p->eng.eval_single, set("BSIG_FIT_CHUNK_PER_LAUNCH"));
   p->eng.workspace_bytes = round_up<size_t>(p->eng.workspace_bytes, 256);
   if (p->hoist) {
     p->feats_bytes = round_up<size_t>(feats, 256);
@@ -929,9 +941,9 @@ extern "C" int bsig_fit_set_features(bsig_fit_plan* p, const float* feats, int64
   return BSIG_OK;
 }
 
-extern "C" int bsig_fit_begin(bsig_fit_plan* p, uint64_t seed, int64_t norm_batch,
-                              bsig_stream_t stream) {
-  bsig::Range roctx_range("bsig_fit_begin");
+// project: fill the MDRFF feature cache unless the caller handed the rows' features over (a block of
+// chunks reads the caller's feature rows of the whole block: nothing to project)
+static int fit_begin(bsig_fit_plan* p, uint64_t seed, int64_t norm_batch, bsig_stream_t stream, bool project) {
   BSIG_REQUIRE(p && p->bound, "fit_begin: plan not bound");
   BSIG_REQUIRE(norm_batch >= 1, "fit_begin: norm_batch must be >= 1");
   if (norm_batch != p->norm_batch) { drop_graphs(p); p->norm_batch = norm_batch; }
@@ -977,11 +989,17 @@ extern "C" int bsig_fit_begin(bsig_fit_plan* p, uint64_t seed, int64_t norm_batc
   const int blocks = (int)std::min<int64_t>(std::max<int64_t>(ceil_div<int64_t>(total4, 256 * 4), 1), 1024);
   hipLaunchKernelGGL(fit_begin_kernel, dim3(blocks), dim3(256), 0, st, p->buf.state, seed, bz);
   BSIG_CHECK_LAUNCH("fit_begin");
-  if (p->hoist) {
+  if (p->hoist && project) {
     if (p->feats_preloaded) p->feats_preloaded = false;   // handed over for this call
     else { p->ext_feats = nullptr; BSIG_TRY(enqueue_hoisted_rff(p, st)); }
   }
   return ensure_graphs(p);
+}
+
+extern "C" int bsig_fit_begin(bsig_fit_plan* p, uint64_t seed, int64_t norm_batch,
+                              bsig_stream_t stream) {
+  bsig::Range roctx_range("bsig_fit_begin");
+  return fit_begin(p, seed, norm_batch, stream, true);
 }
 
 // data-parallel plans covered by a persistent kernel: the held-out evaluations run inside
@@ -1151,6 +1169,70 @@ extern "C" int bsig_fit_pack_logs(bsig_fit_plan* p, int64_t n_updates, float* ou
   hipLaunchKernelGGL(pack_logs_kernel, dim3(1), dim3(64), 0, as_stream(stream), p->buf.train_loss,
                      p->buf.test_loss, p->buf.state, (int)n_updates, (int)count_evals(n_updates), out);
   BSIG_CHECK_LAUNCH("pack_logs");
+  return BSIG_OK;
+}
+
+namespace bsig {
+// pack_logs_kernel for every chunk of a block (workgroup c: chunk c; stride floats per chunk)
+__global__ void pack_block_logs_kernel(const float* train_loss, const float* test_loss, const int32_t* state,
+                                       const bsig_fit_chunk* chunks, int n_evals, float* out) {
+  const bsig_fit_chunk ch = chunks[blockIdx.x];
+  float* o = out + (int64_t)blockIdx.x * (2 * n_evals + 1);
+  if (threadIdx.x == 0) {
+    int e = 0;
+    for (int it = 0; it < ch.n_updates; ++it)
+      if (it % ch.eval_every == 0 || it + 1 == ch.n_updates) { o[e] = train_loss[ch.train_slot + it]; ++e; }
+    o[2 * n_evals] = (float)state[ST_NONFINITE];
+  }
+  for (int i = threadIdx.x; i < n_evals; i += blockDim.x) o[n_evals + i] = test_loss[ch.test_slot + i];
+}
+}  // namespace bsig
+
+extern "C" int bsig_debug_block_launch(int engine_kind, int eval_in_launch, int forced_single) {
+  return block_launch_resolved(engine_kind, eval_in_launch != 0, forced_single != 0) ? 1 : 0;
+}
+
+extern "C" int bsig_fit_block_chunks(const bsig_fit_plan* p, int64_t n_train) {
+  if (!p || !p->bound || p->split_adam || engine(p) != 1 || !p->eng.block_launch) return 0;
+  if (n_train < 1 || !feat_cache_applies(p, n_train) || p->n_updates < 1) return 0;
+  // (the tags: fewer than 2^30 updates in a launch)
+  return (int)std::min<int64_t>(((int64_t)1 << 30) / (p->n_updates + 1), 1 << 16);
+}
+
+extern "C" int bsig_fit_run_block(bsig_fit_plan* p, const float* feats, int64_t ld_feats, int64_t rows,
+                                  const float* y, int64_t ldy, const int32_t* ids, int64_t n_ids,
+                                  const bsig_fit_chunk* chunks_host, const bsig_fit_chunk* chunks_dev, int n_chunks,
+                                  float* train_loss, float* test_loss, float* packed_logs, int64_t norm_batch,
+                                  bsig_stream_t stream) {
+  bsig::Range roctx_range("bsig_fit_run_block");
+  BSIG_REQUIRE(p && p->bound && feats && y && ids && chunks_host && chunks_dev && train_loss && test_loss &&
+               packed_logs, "fit_run_block: plan not bound / null");
+  BSIG_REQUIRE(n_chunks >= 1 && n_chunks <= bsig_fit_block_chunks(p, 1),
+               "fit_run_block: this plan runs one chunk per launch (bsig_fit_block_chunks)");
+  BSIG_REQUIRE(rows >= 1 && ld_feats >= p->cfg.rff_feats && ld_feats % 4 == 0 && aligned(feats, 16) &&
+               ldy >= p->cfg.head.out_dim && n_ids >= 0, "fit_run_block: bad block");
+  const int n_upd = (int)p->n_updates, every = std::max(n_upd / 5, 1), n_ev = (int)p->n_evals;
+  int max_test = 0;
+  for (int c = 0; c < n_chunks; ++c) {
+    const bsig_fit_chunk& k = chunks_host[c];
+    BSIG_REQUIRE(k.n_updates == n_upd && k.eval_every == every && k.upd_base == c * n_upd && k.eval_base == c * n_ev &&
+                 k.train_slot == k.upd_base && k.test_slot == k.eval_base,
+                 "fit_run_block: chunk %d: updates, evaluation schedule or slots out of step with the plan", c);
+    BSIG_REQUIRE(k.n_train >= 1 && k.n_test >= 1 && k.n_test <= p->max_test && feat_cache_applies(p, k.n_train) &&
+                 k.row0 >= 0 && k.row0 + k.n_train + k.n_test <= rows,
+                 "fit_run_block: chunk %d: rows %lld + %d + %d outside the block's %lld (or more than the plan covers)",
+                 c, (long long)k.row0, k.n_train, k.n_test, (long long)rows);
+    BSIG_REQUIRE(k.ids_off == (int64_t)k.upd_base * p->batch && k.ids_off + (int64_t)n_upd * p->batch <= n_ids,
+                 "fit_run_block: chunk %d: ids outside the table", c);
+    max_test = std::max(max_test, k.n_test);
+  }
+  BSIG_TRY(fit_begin(p, chunks_host[0].seed, norm_batch, stream, false));
+  hipStream_t st = as_stream(stream);
+  const BlockRun blk{feats, ld_feats, y, ldy, ids, chunks_dev, n_chunks, max_test, n_chunks * n_upd, train_loss, test_loss};
+  BSIG_TRY(enqueue_persistent(p, n_upd, st, n_upd, nullptr, &blk));
+  hipLaunchKernelGGL(pack_block_logs_kernel, dim3(n_chunks), dim3(64), 0, st, train_loss, test_loss, p->buf.state,
+                     chunks_dev, n_ev, packed_logs);
+  BSIG_CHECK_LAUNCH("pack_block_logs");
   return BSIG_OK;
 }
 

@@ -2,6 +2,11 @@
 // mixture-density head on precomputed features in ONE launch
 // (MDRFF.run_training's inner loop, mdnn.py:219-233, with the RFF projection
 // hoisted: forward mdnn.py:108-119, NLL :127-178, its backward, Adam :203/:229).
+// A launch runs the updates of one run_training call -- or of a BLOCK of consecutive calls
+// (bsig_fit_run_block: up to BayesSim.FIT_BLOCK_CHUNKS chunks of a fit): the weight tiles stay in LDS across
+// the chunk boundaries, where only the Adam moments, the step count and the chunk's rows, ids, seed and log
+// slots change (UCk, read from a chunk table), and the evaluation after a chunk's last update runs in the
+// waits of the next chunk's first updates instead of serially behind the launch.
 //
 // Round 4: UNIFIED workgroups.  The head matrix W [Nh, F] is tiled over the WHOLE chip:
 // workgroup (nb, ks) owns the 16 x KS tile W[16nb.., KS*ks..] (NT = 1; 32 rows with NT = 2
@@ -82,12 +87,86 @@ struct UArgs {
   int64_t eval_row0;
   const float* y_test; int64_t ldy_test;
   float* test_loss;
-  float* eval_slabs;                 // [3][eval_passes][k_slices][B][NhP]
+  float* eval_slabs;                 // [3][eval_passes][k_slices][B][NhP] (eval_passes: the most of any chunk)
   unsigned* flag_eval;               // [G]   evaluation number + 1
   unsigned long long* gran_eval;     // [2][kGranArr]
   long long* prof;                   // diagnostics: [T][kUProf][16] wall-clock stamps, or null
   int prof_t0;                       // ... of updates prof_t0 .. prof_t0 + kUProf of the launch (BSIG_PROF_T0)
+  // a block of chunks in one launch (persist.h: PersistBuffers::chunks): entry c replaces, at the boundary in
+  // front of chunk c, what the fields above say about ONE chunk (n_updates, n_total, eval_every, n_test,
+  // eval_row0, y_test, the state block's step / seed / stream counter); feats, y, ids, train_loss and
+  // test_loss are then the block's.  null: one chunk, described by the fields above (n_chunks = 1).
+  const bsig_fit_chunk* chunks; int n_chunks;
 };
+
+// What a workgroup keeps of the chunk it is in (workgroup-uniform; read at the chunk boundary)
+struct UCk {
+  int step0, n_updates, n_total, eval_every, do_eval;
+  // Flag and granule tags count the updates / evaluations of the LAUNCH (they must stay monotonic across
+  // chunks): update t of the chunk has epoch ubase + step + 1, evaluation e the tag evbase + e + 1.  The
+  // widest tag is epoch * 4 + 3 in 32 bits: a launch holds fewer than 2^30 updates (persist_run checks;
+  // 32 chunks of 100 updates and 6 evaluations reach epoch 3200 and evaluation tag 192).  Adam, the jitter
+  // streams and the evaluation schedule count chunk-local steps.
+  unsigned ubase, evbase;
+  // (The update loops index the ids and the train-loss log by the update of the LAUNCH, epoch - 1: the chunks'
+  // ids and log slots follow each other, the ids are rows of the block; n_updates, eval_every and do_eval are the
+  // same for every chunk of a launch -- the loops read the launch's arguments, which cost no live register.)
+  uint64_t seed, rng_ctr0;
+};
+__device__ __forceinline__ int u_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ int64_t u_uniform(int64_t v) {
+  return (int64_t)(((uint64_t)(uint32_t)u_uniform((int)((uint64_t)v >> 32)) << 32) | (uint32_t)u_uniform((int)(uint64_t)v));
+}
+__device__ __forceinline__ void u_chunk_load(const UArgs& p, int c, UCk& k) {
+  if (p.chunks == nullptr) {
+    k.step0 = p.state[0]; k.n_updates = p.n_updates; k.n_total = p.n_total; k.eval_every = p.eval_every;
+    k.do_eval = p.do_eval; k.ubase = 0u; k.evbase = 0u;
+    k.seed = reinterpret_cast<const uint64_t*>(p.state + 8)[0];
+    k.rng_ctr0 = reinterpret_cast<const uint64_t*>(p.state + 8)[1];
+    return;
+  }
+  const bsig_fit_chunk& e = p.chunks[c];
+  k.step0 = 0; k.n_updates = u_uniform(e.n_updates); k.n_total = k.n_updates; k.eval_every = u_uniform(e.eval_every);
+  k.do_eval = 1; k.ubase = (unsigned)u_uniform(e.upd_base); k.evbase = (unsigned)u_uniform(e.eval_base);
+  k.seed = (uint64_t)u_uniform((int64_t)e.seed); k.rng_ctr0 = (uint64_t)u_uniform((int64_t)e.rng_ctr0);
+}
+
+// One held-out evaluation: evaluation e (chunk-local) of chunk c.  Built where it is used (the evaluation
+// whose parts run in the waits of the NEXT chunk's first updates still belongs to its own chunk).
+struct UEval {
+  int n_test, passes; int64_t row0;  // held-out feature rows feats[row0 .. row0 + n_test)
+  const float* y_test; int64_t ldy_test;
+  float* out;                        // its slot of the test-loss log (null: test_loss[state[1]], one chunk)
+  unsigned gidx;                     // evaluation number of the launch: slab buffer gidx % 3, tag gidx + 1
+  uint64_t seed, stream;             // jitter stream (one per update and per evaluation, in program order:
+                                     // the per-phase path's numbering)
+};
+__device__ __forceinline__ UEval u_eval_of(const UArgs& p, int c, int e) {
+  UEval v;
+  int every, n_total, step0;
+  uint64_t ctr0;
+  if (p.chunks == nullptr) {
+    v.n_test = p.n_test; v.row0 = p.eval_row0; v.y_test = p.y_test; v.ldy_test = p.ldy_test; v.out = nullptr;
+    v.gidx = (unsigned)e; every = p.eval_every; n_total = p.n_total; step0 = p.state[0];
+    v.seed = reinterpret_cast<const uint64_t*>(p.state + 8)[0];
+    ctr0 = reinterpret_cast<const uint64_t*>(p.state + 8)[1];
+  } else {
+    const bsig_fit_chunk& k = p.chunks[c];
+    v.n_test = u_uniform(k.n_test); v.row0 = u_uniform(k.row0) + u_uniform(k.n_train);
+    v.y_test = p.y + v.row0 * p.ldy; v.ldy_test = p.ldy; v.out = p.test_loss + u_uniform(k.test_slot) + e;
+    v.gidx = (unsigned)u_uniform(k.eval_base) + (unsigned)e; every = u_uniform(k.eval_every);
+    n_total = u_uniform(k.n_updates); step0 = 0;
+    v.seed = (uint64_t)u_uniform((int64_t)k.seed); ctr0 = (uint64_t)u_uniform((int64_t)k.rng_ctr0);
+  }
+  v.passes = (v.n_test + p.B - 1) / p.B;
+  // the update it precedes: e * every + 1, the call's update count for the evaluation after the last update
+  const int at = min(e * every + 1, n_total);
+  const int ev0 = p.do_eval || p.chunks ? (step0 == 0 ? 0 : (step0 - 1) / every + 1) : 0;
+  v.stream = ctr0 + (uint64_t)(at - step0) + (uint64_t)(e - ev0);
+  return v;
+}
+// index of the evaluation after the last update of a call of n_total updates
+__device__ __forceinline__ int u_last_eval(int n_total, int every) { return n_total <= 1 ? 0 : (n_total - 2) / every + 1; }
 
 __device__ __forceinline__ f32x4 umfma(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
@@ -131,8 +210,8 @@ __device__ __forceinline__ int u_evals_before(int s, int every) { return s == 0 
 
 #define BSIG_USTAMP(k)                                                           \
   do {                                                                           \
-    if (p.prof && threadIdx.x == 0 && t >= p.prof_t0 && t < p.prof_t0 + kUProf)  \
-      p.prof[((int64_t)wg * kUProf + t - p.prof_t0) * 16 + (k)] = wall_clock64(); \
+    if (p.prof && threadIdx.x == 0 && pt >= p.prof_t0 && pt < p.prof_t0 + kUProf)  \
+      p.prof[((int64_t)wg * kUProf + pt - p.prof_t0) * 16 + (k)] = wall_clock64(); \
   } while (0)
 
 // which row the owners of this launch run: workgroup-uniform, the same for every launch of a shape.
@@ -233,17 +312,17 @@ __device__ __forceinline__ void u_rows_sum4(const float* slabs, RowOff&& rowoff,
   }
 }
 
-// ---- tile part of held-out evaluation eidx: held-out rows x this tile's weights (the B operand
-//      straight from memory, six 16-column steps at a time) -> evaluation slab buffer eidx % 3, flag
+// ---- tile part of held-out evaluation ev: held-out rows x this tile's weights (the B operand
+//      straight from memory, six 16-column steps at a time) -> evaluation slab buffer gidx % 3, flag
 template <int NT>
 __device__ __forceinline__ void u_tile_eval(const UArgs& p, const float* Wl, const float* biasl, int slot,
-                                            int ks, int n0, int k0, int eidx) {
+                                            int ks, int n0, int k0, const UEval& ev) {
   int tid = threadIdx.x;
   asm volatile("" : "+v"(tid));    // (nothing below may be computed ahead of the update loop and kept live in it)
   const int lane = tid & 63, w = tid >> 6, c16 = lane & 15, g4 = lane >> 4;
   const int B = p.B, NhP = p.NhP;
-  for (int pass = 0; pass < p.eval_passes; ++pass) {
-    const int rows = min(B, p.n_test - pass * B);
+  for (int pass = 0; pass < ev.passes; ++pass) {
+    const int rows = min(B, ev.n_test - pass * B);
     if (rows <= 0) break;
     if (w < p.MT) {
       f32x4 acc[NT];
@@ -252,7 +331,7 @@ __device__ __forceinline__ void u_tile_eval(const UArgs& p, const float* Wl, con
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
         acc[nt] = ks == 0 ? *reinterpret_cast<const f32x4*>(biasl + 16 * nt + 4 * g4) : zero;
       }
-      const int64_t r = p.eval_row0 + pass * B + min(16 * w + c16, rows - 1);
+      const int64_t r = ev.row0 + pass * B + min(16 * w + c16, rows - 1);
       const float* src = p.feats + r * p.ld_feats;
       const float* ap = Wl + c16 * p.WP + 4 * g4;
 #pragma unroll 1
@@ -279,7 +358,7 @@ __device__ __forceinline__ void u_tile_eval(const UArgs& p, const float* Wl, con
       }
       if (16 * w + c16 < rows) {
         const __amdgpu_buffer_rsrc_t sr = xwg_buffer(
-            p.eval_slabs + ((((int64_t)(eidx % 3) * p.eval_passes + pass) * p.k_slices + ks) * B) * NhP + n0);
+            p.eval_slabs + ((((int64_t)(ev.gidx % 3u) * p.eval_passes + pass) * p.k_slices + ks) * B) * NhP + n0);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
           xwg_store4(sr, (16 * w + c16) * NhP + 16 * nt + 4 * g4, acc[nt][0], acc[nt][1], acc[nt][2], acc[nt][3]);
@@ -288,24 +367,24 @@ __device__ __forceinline__ void u_tile_eval(const UArgs& p, const float* Wl, con
   }
   __builtin_amdgcn_s_waitcnt(0);
   __syncthreads();
-  if (tid == 0) flag_raise(p.flag_eval, slot, (unsigned)eidx + 1u);
+  if (tid == 0) flag_raise(p.flag_eval, slot, ev.gidx + 1u);
 }
 
-// ---- row part of held-out evaluation eidx (jitter stream `stream`) by evaluation owner `eo`:
+// ---- row part of held-out evaluation ev by evaluation owner `eo`:
 //      held-out rows eo, eo + NE, ... (RE of them, one wavefront each), forward only
-__device__ __forceinline__ void u_owner_eval(const UArgs& p, float* XS, float* red, int eo, int eidx,
-                                             uint64_t stream, const HeadArgs& a) {
+__device__ __forceinline__ void u_owner_eval(const UArgs& p, float* XS, float* red, int eo, const UEval& ev,
+                                             const HeadArgs& a) {
   int tid = threadIdx.x;
   asm volatile("" : "+v"(tid));
   const int lane = tid & 63, w = tid >> 6;
   const int B = p.B, Nh = p.Nh, NhP = p.NhP, D = p.D, K = p.K, DK = D * K;
   const int per_wave = Nh + D + 3 * K;
   int32_t* flagp = p.state + 2;
-  const unsigned etag = (unsigned)eidx + 1u;
+  const unsigned etag = ev.gidx + 1u;
   if (w == 0) flags_wait(p.flag_eval, p.G, etag, lane, flagp);
   __syncthreads();
-  const int nr = eo < p.n_test ? min(p.RE, (p.n_test - eo + p.NE - 1) / p.NE) : 0;   // this owner's rows
-  const float* ebase = p.eval_slabs + (int64_t)(eidx % 3) * p.eval_passes * p.k_slices * B * NhP;
+  const int nr = eo < ev.n_test ? min(p.RE, (ev.n_test - eo + p.NE - 1) / p.NE) : 0;   // this owner's rows
+  const float* ebase = p.eval_slabs + (int64_t)(ev.gidx % 3u) * p.eval_passes * p.k_slices * B * NhP;
   float eacc = 0.f;
   u_rows_sum(ebase,
              [&](int r) {
@@ -330,7 +409,7 @@ __device__ __forceinline__ void u_owner_eval(const UArgs& p, float* XS, float* r
   float* lpk = rk + K;
   float* dlg = lpk + K;
   if (act)
-    for (int j = lane; j < D; j += 64) yv[j] = p.y_test[(int64_t)erow * p.ldy_test + j];
+    for (int j = lane; j < D; j += 64) yv[j] = ev.y_test[(int64_t)erow * ev.ldy_test + j];
   RowOut ro;
   ro.lse = 0.f; ro.uds = 0.f; ro.bad = false;
 #pragma unroll
@@ -338,13 +417,14 @@ __device__ __forceinline__ void u_owner_eval(const UArgs& p, float* XS, float* r
   if (w < p.RE) {
     HeadArgs ae = a;
     ae.d_out = nullptr;                    // forward only
-    ae.batch = p.n_test;
-    ae.stream_id = stream;
+    ae.batch = ev.n_test;
+    ae.seed = ev.seed;
+    ae.stream_id = ev.stream;
     diag_row(ae, erow, act, lane, tile, yv, rk, lpk, dlg,
              [&] {
                return p.eps_noise != 0.f
                           ? p.eps_noise * (granule_gather(p.gran_eval, p.NE, etag, lane, flagp) /
-                                           ((float)p.n_test * (float)DK))
+                                           ((float)ev.n_test * (float)DK))
                           : 0.f;
              },
              ro);
@@ -359,8 +439,9 @@ __device__ __forceinline__ void u_owner_eval(const UArgs& p, float* XS, float* r
   if (eo == 0 && w == 0) {
     const float sum = granule_gather(p.gran_eval + kGranArr, p.NE, etag, lane, flagp);
     if (lane == 0) {
-      const float l = -sum / (float)p.n_test;
-      p.test_loss[p.state[1]] = l;
+      const float l = -sum / (float)ev.n_test;
+      if (ev.out) *ev.out = l;
+      else p.test_loss[p.state[1]] = l;
       p.state[1] = p.state[1] + 1;
       if (!isfinite(l)) atomicOr(flagp, 1);
     }
@@ -380,6 +461,7 @@ struct UOwn {
   float *XS, *red, *part;         // LDS: row blocks, [64] scratch, partial k-slice sums
   HeadArgs a; RowGeom rg;
   uint64_t rng_ctr0; int step0, ev0; float norm; int32_t* flagp;
+  unsigned ubase;                 // of the chunk (u_own_chunk), as seed, rng_ctr0, step0 and ev0
 };
 __device__ __forceinline__ void u_own_init(const UArgs& p, UOwn& o, int own, bool has_tile, float* XS,
                                            float* red, float* part, int lane0) {
@@ -388,19 +470,18 @@ __device__ __forceinline__ void u_own_init(const UArgs& p, UOwn& o, int own, boo
   o.a = HeadArgs{};
   o.a.D = p.D; o.a.K = p.K; o.a.Nh = p.Nh; o.a.batch = p.B; o.a.from_tuple = 0;
   o.a.min_w = p.min_w; o.a.ll_limit = p.ll_limit; o.a.inv_norm = p.inv_norm;
-  o.a.eps_noise = p.eps_noise; o.a.seed = reinterpret_cast<const uint64_t*>(p.state + 8)[0]; o.a.d_out = p.d_out;
+  o.a.eps_noise = p.eps_noise; o.a.d_out = p.d_out;
   o.rg = row_geom(p.D, p.K, lane0);       // (integer divisions by run-time values: once per launch)
-  o.rng_ctr0 = reinterpret_cast<const uint64_t*>(p.state + 8)[1];
-  o.step0 = p.state[0];
-  o.ev0 = p.do_eval ? u_evals_before(o.step0, p.eval_every) : 0;
   o.norm = (float)p.B * (float)(p.D * p.K);
   o.flagp = p.state + 2;
 }
-// jitter stream of evaluation e (one stream per update and per evaluation, in program order: the
-// per-phase path's numbering); `last`: the evaluation after the call's last update
-__device__ __forceinline__ uint64_t u_eval_stream(const UArgs& p, const UOwn& o, int e, bool last) {
-  const int at = last ? p.n_total : e * p.eval_every + 1;     // the update it precedes
-  return o.rng_ctr0 + (uint64_t)(at - o.step0) + (uint64_t)(e - o.ev0);
+// ... what the owner derives from the chunk: again at every chunk boundary
+__device__ __forceinline__ void u_own_chunk(UOwn& o, const UCk& k) {
+  o.a.seed = k.seed;
+  o.rng_ctr0 = k.rng_ctr0;
+  o.step0 = k.step0;
+  o.ev0 = k.do_eval ? u_evals_before(k.step0, k.eval_every) : 0;
+  o.ubase = k.ubase;
 }
 
 // Update t of the launch for the rows r0 .. r0 + R of this owner (every wavefront of the workgroup
@@ -408,8 +489,9 @@ __device__ __forceinline__ uint64_t u_eval_stream(const UArgs& p, const UOwn& o,
 __device__ __forceinline__ void u_own_update(const UArgs& p, UOwn& o, int t, int w, int lane0, int wg) {
   const int B = p.B, Nh = p.Nh, NhP = p.NhP, D = p.D, K = p.K, DK = D * K;
   const int step = o.step0 + t;
-  const unsigned epoch = (unsigned)step + 1u;
+  const unsigned epoch = o.ubase + (unsigned)step + 1u;
   const uint32_t tag = epoch * 4u;
+  [[maybe_unused]] const int pt = t + (int)o.ubase;       // (diagnostics) update of the launch
   const int own = o.own, r0 = o.r0, per_wave = o.per_wave;
   const bool has_tile = o.has_tile;
   float* XS = o.XS; float* red = o.red; float* Ft = o.part;
@@ -432,7 +514,7 @@ __device__ __forceinline__ void u_own_update(const UArgs& p, UOwn& o, int t, int
     asm volatile("" : "+v"(lane));
     const int tid_l = 64 * w + lane;
     if (active) {      // target row (independent of the forward product)
-      const int64_t yrow = p.ids[(int64_t)step * B + row];
+      const int64_t yrow = p.ids[(int64_t)(epoch - 1u) * B + row];
       for (int j = lane; j < D; j += 64) yv[j] = p.y[yrow * p.ldy + j];
     }
     // the row's jitter draws do not depend on the forward product: drawn in the wait
@@ -471,9 +553,9 @@ __device__ __forceinline__ void u_own_update(const UArgs& p, UOwn& o, int t, int
       GranuleEps ge{gran_rep(p, 0, wg & 7), p.n_owner, tag + 1, lane, flagp, p.eps_noise, norm, {0ull, 0ull, 0ull, 0ull}};
       diag_row_impl(a, rg, row, active, lane, tile, yv, rk, lpk, dlg, ge, ro, eu_pre);
 #ifdef BSIG_ROW_PROF
-      if (p.prof && tid == 0 && t >= p.prof_t0 && t < p.prof_t0 + kUProf)
+      if (p.prof && tid == 0 && pt >= p.prof_t0 && pt < p.prof_t0 + kUProf)
         for (int i = 0; i < 9; ++i)
-          p.prof[(int64_t)256 * kUProf * 16 + ((int64_t)wg * kUProf + t - p.prof_t0) * 16 + i] = ro.ts[i];
+          p.prof[(int64_t)256 * kUProf * 16 + ((int64_t)wg * kUProf + pt - p.prof_t0) * 16 + i] = ro.ts[i];
 #endif
       const float uds_w = wave_sum_dpp(ro.uds);
       if (lane == 0) { red[16 + w] = active ? ro.lse : 0.f; red[32 + w] = uds_w; }
@@ -507,7 +589,7 @@ __device__ __forceinline__ void u_own_update(const UArgs& p, UOwn& o, int t, int
       const float s = granule_gather(loss_granules(p.gran, epoch), p.n_owner, tag + 3, lane, flagp);
       if (lane == 0) {
         const float l = -s / (float)B;
-        p.train_loss[step] = l;
+        p.train_loss[epoch - 1u] = l;
         if (!isfinite(l)) atomicOr(flagp, 1);
       }
     }
@@ -538,8 +620,8 @@ __device__ __forceinline__ void u_own_update(const UArgs& p, UOwn& o, int t, int
 // Update t of the launch for the rows of this owner, every wavefront of the workgroup comes through here
 // (wavefronts 2r, 2r + 1 run row r0 + r; the others only fetch k-slices and keep the barriers).
 #ifdef BSIG_ROW_PROF
-#define BSIG_FSTAMP(i) do { if (p.prof && threadIdx.x == 0 && t >= p.prof_t0 && t < p.prof_t0 + kUProf) \
-    p.prof[(int64_t)256 * kUProf * 16 + ((int64_t)wg * kUProf + t - p.prof_t0) * 16 + (i)] = wall_clock64(); } while (0)
+#define BSIG_FSTAMP(i) do { if (p.prof && threadIdx.x == 0 && pt >= p.prof_t0 && pt < p.prof_t0 + kUProf) \
+    p.prof[(int64_t)256 * kUProf * 16 + ((int64_t)wg * kUProf + pt - p.prof_t0) * 16 + (i)] = wall_clock64(); } while (0)
 #else
 #define BSIG_FSTAMP(i)
 #endif
@@ -555,8 +637,9 @@ __device__ __forceinline__ void u_own_update_fast(const UArgs& p, UOwn& o, int t
   const bool exact = K == KP;
   const int B = p.B, Nh = p.Nh, NhP = p.NhP, D = p.D, DK = D * K, R = p.R;
   const int step = o.step0 + t;
-  const unsigned epoch = (unsigned)step + 1u;
+  const unsigned epoch = o.ubase + (unsigned)step + 1u;
   const uint32_t tag = epoch * 4u;
+  [[maybe_unused]] const int pt = t + (int)o.ubase;       // (diagnostics) update of the launch
   const int own = o.own, r0 = o.r0;
   float* red = o.red; float* part = o.part; float* XS = o.XS;
   int32_t* flagp = o.flagp;
@@ -583,7 +666,7 @@ __device__ __forceinline__ void u_own_update_fast(const UArgs& p, UOwn& o, int t
     yd[i] = 0.f; eu[i] = 0.f;
   }
   if (active) {
-    const int64_t yrow = p.ids[(int64_t)step * B + row];
+    const int64_t yrow = p.ids[(int64_t)(epoch - 1u) * B + row];
 #pragma unroll
     for (int i = 0; i < NQH; ++i)
       if (valid[i]) yd[i] = p.y[yrow * p.ldy + d0 + (h + 2 * i) * GR];
@@ -768,7 +851,7 @@ __device__ __forceinline__ void u_own_update_fast(const UArgs& p, UOwn& o, int t
     const float s = granule_gather(loss_granules(p.gran, epoch), p.n_owner * R, tag + 3, lane, flagp);
     if (lane == 0) {
       const float l = -s / (float)B;
-      p.train_loss[step] = l;
+      p.train_loss[epoch - 1u] = l;
       if (!isfinite(l)) atomicOr(flagp, 1);
     }
   }
@@ -778,10 +861,10 @@ __device__ __forceinline__ void u_own_update_fast(const UArgs& p, UOwn& o, int t
 // The minibatch tile of update `step`, straight into the forward product's B-operand registers:
 // wavefront w < MT holds rows 16w .. 16w+15, lane (c16, g4) the four columns 16S + 4 g4 .. +3 of
 // step S (64 contiguous bytes per row and instruction).
-#define BSIG_U_ROWID(step_)                                                                  \
+#define BSIG_U_ROWID(ids_, row0_, step_)                                                    \
   if (has_tile && w < p.MT) {                                                                \
     const int64_t r = (int64_t)(step_) * B + min(16 * w + c16_l, B - 1);                     \
-    pf_row = p.feat_ids ? (int64_t)p.feat_ids[r] : r;                                        \
+    pf_row = (ids_) ? (row0_) + (int64_t)(ids_)[r] : r;                                      \
   }
 #define BSIG_U_PREFETCH()                                                                    \
   if (has_tile && w < p.MT) {                                                                \
@@ -833,7 +916,11 @@ __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, c
   constexpr int FP = kUFP;
   const int WP = p.WP;
   int32_t* flagp = p.state + 2;
-  const int step0 = p.state[0];
+  // the chunks of the launch (a data-parallel rank's launches hold one, described by the arguments)
+  const int n_chunks = (DP || XR || p.chunks == nullptr) ? 1 : p.n_chunks;
+  UCk ck;
+  u_chunk_load(p, 0, ck);
+  const int step0 = ck.step0;
   if (p.prof && p.n_updates > 0 && tid == 0) p.prof[((int64_t)wg * kUProf) * 16 + 14] = wall_clock64();
   double b1t = reinterpret_cast<const double*>(p.state + 12)[0];
   double b2t = reinterpret_cast<const double*>(p.state + 12)[1];
@@ -985,10 +1072,11 @@ __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, c
   // ---- row-owner state (a tile workgroup that also owns minibatch rows: heads with no CUs to spare)
   UOwn o;
   u_own_init(p, o, own, true, XS, red, Ft, lane0);
+  u_own_chunk(o, ck);
   // evaluation owner: the workgroups without a minibatch row come first
   const int eo = (own - p.n_owner + p.T) % p.T;
   const bool has_erow = p.do_eval && eo < p.NE;
-  int pending_eval = -1;                       // evaluation whose tile part is out and whose row part is due
+  int pending_eval = -1, pending_chunk = 0;    // evaluation whose tile part is out and whose row part is due
 
   // feature tile of the first update (later ones are fetched during the waits)
   f32x4 Freg[kUSteps];
@@ -1000,10 +1088,31 @@ __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, c
   int64_t pf_row = 0;                         // feature row of this lane's minibatch row, next update
   {
     const int c16_l = c16, g4_l = g4;
-    if (p.n_updates > 0) { BSIG_U_ROWID(step0) BSIG_U_PREFETCH() }
+    if (p.n_updates > 0) { BSIG_U_ROWID(p.feat_ids, 0, step0) BSIG_U_PREFETCH() }
   }
   __syncthreads();
 
+  for (int c = 0; c < n_chunks; ++c) {
+  if (c > 0) {
+    // ---- chunk boundary (mdnn.py:203: a fresh optimizer per run_training call).  The weight tile stays in
+    // LDS; the moments restart at zero in the registers, Adam's step count and bias corrections restart.
+    // The feature tile of the chunk's first update is already in flight (requested in the last wait of the
+    // chunk before).  The evaluation after that chunk's last update is still owed: its tile part runs in
+    // the wait of this chunk's update 0, which lies in FRONT of that update's Adam phase -- the weights it
+    // reads from LDS are the ones the last update of its chunk left.
+    u_chunk_load(p, c, ck);
+    u_own_chunk(o, ck);
+#pragma unroll
+    for (int jj = 0; jj < MAXBLK; ++jj)
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) { Mr[jj][nt][v] = 0.f; Vr[jj][nt][v] = 0.f; }
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) { bm[nt] = 0.f; bv[nt] = 0.f; }
+    b1t = 1.0; b2t = 1.0;
+  }
+  const int step0 = ck.step0;
   for (int t = 0; t < p.n_updates; ++t) {
     // Lane-derived indices are laundered at the start of every phase: the address arithmetic and
     // the predicates built on them are loop-invariant, and hoisted out of the update loop they do
@@ -1011,8 +1120,9 @@ __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, c
     int tid_l = tid, c16_l = c16, g4_l = g4;
     asm volatile("" : "+v"(tid_l), "+v"(c16_l), "+v"(g4_l));
     const int step = step0 + t;
-    const unsigned epoch = (unsigned)step + 1u;
+    const unsigned epoch = ck.ubase + (unsigned)step + 1u;
     const uint32_t tag = epoch * 4u;
+    [[maybe_unused]] const int pt = t + (int)ck.ubase;       // (diagnostics) update of the launch
     if (red[63] != 0.f) break;     // time-out bit as sampled during the previous update's wait
     BSIG_USTAMP(0);
     {
@@ -1068,7 +1178,8 @@ __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, c
       if (tid_l == 0) flag_raise(p.flag_fwd, slot, epoch);
       BSIG_USTAMP(3);
       // the next minibatch's row ids (the tile itself is requested further down)
-      if (t + 1 < p.n_updates) { BSIG_U_ROWID(step + 1) }
+      // (behind the chunk's last update: of the first update of the next chunk -- update `epoch` of the launch too)
+      if (t + 1 < p.n_updates || c + 1 < n_chunks) { BSIG_U_ROWID(p.feat_ids, 0, epoch) }
     }
     // the time-out bit (set by any bounded poll on the chip), sampled off the critical path
     if (tid_l == 0)
@@ -1083,13 +1194,14 @@ __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, c
     //      during the previous update, the tile part of the one due after the previous update
     if (__builtin_expect(pending_eval >= 0, 0)) {
       __syncthreads();
-      if (has_erow) u_owner_eval(p, XS, red, eo, pending_eval, u_eval_stream(p, o, pending_eval, false), o.a);
+      if (has_erow) u_owner_eval(p, XS, red, eo, u_eval_of(p, pending_chunk, pending_eval), o.a);
       pending_eval = -1;
     }
-    if (__builtin_expect(p.do_eval && step > 0 && (step - 1) % p.eval_every == 0, 0)) {
-      const int e = u_evals_before(step, p.eval_every) - 1;
-      u_tile_eval<NT>(p, Wl, biasl, slot, ks, n0, k0, e);
-      pending_eval = e;
+    // (update 0 of a later chunk of the launch: the evaluation after the last update of the chunk before)
+    if (__builtin_expect(p.do_eval && (step > 0 ? (step - 1) % p.eval_every == 0 : c > 0), 0)) {
+      pending_chunk = step > 0 ? c : c - 1;
+      pending_eval = step > 0 ? u_evals_before(step, p.eval_every) - 1 : u_last_eval(p.n_updates, p.eval_every);
+      u_tile_eval<NT>(p, Wl, biasl, slot, ks, n0, k0, u_eval_of(p, pending_chunk, pending_eval));
     }
 
     // ---- 3. dW = d_out^T F on this tile, Adam --------------------------------------------------
@@ -1102,7 +1214,7 @@ __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, c
       // straight from its forward flag) and for a row owner (the others are still finishing).  Not
       // earlier: the 18 x 16-byte registers would be live through the row owner's work.  Not later:
       // requested behind the d_out^T block it took 2.6 us out of the dW phase.
-      if (t + 1 < p.n_updates) { BSIG_U_PREFETCH() }
+      if (t + 1 < p.n_updates || c + 1 < n_chunks) { BSIG_U_PREFETCH() }
       BSIG_USTAMP(2);
       // the owners' sum(u * dL/dsigma) granules double as their "d_out rows are out" flags; the
       // jitter-scale gradient term  d pre += (EPS/(B*D*K)) * sum(u*dL/dsigma) * exp(pre)
@@ -1351,6 +1463,7 @@ __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, c
       BSIG_USTAMP(12);
     }
   }
+  }     // (chunks; a launch that gave up: red[63] stays set, the remaining chunks end at their first update)
   if constexpr (XR) {
     // a launch that gave up (a bounded poll timed out, here or in any workgroup) must not leave the
     // exchange stream waiting for gradients that will never come: every wait of the call passes
@@ -1362,16 +1475,17 @@ __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, c
   // ---- evaluations still owed at the end of the launch ------------------------------------------
   if (p.do_eval && !run_aborted(flagp, red, tid)) {
     if (pending_eval >= 0) {
-      if (has_erow) u_owner_eval(p, XS, red, eo, pending_eval, u_eval_stream(p, o, pending_eval, false), o.a);
+      if (has_erow) u_owner_eval(p, XS, red, eo, u_eval_of(p, pending_chunk, pending_eval), o.a);
       pending_eval = -1;
     }
     // the evaluation after the last update of the call (a data-parallel rank: in the launch that
-    // only takes the pending Adam step of that update)
-    if (step0 + p.n_updates == p.n_total && (!DP || p.n_updates == 0)) {
-      const int e = u_evals_before(p.n_total - 1, p.eval_every);
+    // only takes the pending Adam step of that update; a block of chunks: of its last chunk -- the
+    // others' ran in the waits of the chunk behind them)
+    if (ck.step0 + p.n_updates == p.n_total && (!DP || p.n_updates == 0)) {
+      const UEval ev = u_eval_of(p, n_chunks - 1, u_evals_before(p.n_total - 1, p.eval_every));
       __syncthreads();
-      u_tile_eval<NT>(p, Wl, biasl, slot, ks, n0, k0, e);
-      if (has_erow) u_owner_eval(p, XS, red, eo, e, u_eval_stream(p, o, e, true), o.a);
+      u_tile_eval<NT>(p, Wl, biasl, slot, ks, n0, k0, ev);
+      if (has_erow) u_owner_eval(p, XS, red, eo, ev, o.a);
     }
   }
   // ---- write the tile back, advance the engine state -----------------------------------------
@@ -1403,7 +1517,10 @@ __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, c
     p.prof[((int64_t)wg * kUProf) * 16 + 13] = wall_clock64();
   }
   if (wg == 0 && tid == 0 && p.n_updates > 0) {
-    // (an aborted run leaves the counters of the planned run: the call fails anyway)
+    u_chunk_load(p, n_chunks - 1, ck);
+    // (an aborted run leaves the counters of the planned run: the call fails anyway; a block of chunks
+    // leaves what the call of its last chunk would have left)
+    const int step0 = ck.step0;
     int32_t* st = p.state;
     reinterpret_cast<double*>(st + 12)[0] = b1t;
     reinterpret_cast<double*>(st + 12)[1] = b2t;
@@ -1411,12 +1528,13 @@ __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, c
     reinterpret_cast<float*>(st)[5] = a1;
     // (one jitter stream per update and per evaluation, in program order)
     int n_ev = 0;
-    if (p.do_eval) {
-      n_ev = u_evals_before(step0 + p.n_updates, p.eval_every) - u_evals_before(step0, p.eval_every);
-      if (!DP && step0 + p.n_updates == p.n_total && (p.n_total - 1) % p.eval_every != 0) ++n_ev;
+    if (ck.do_eval) {
+      n_ev = u_evals_before(step0 + ck.n_updates, ck.eval_every) - u_evals_before(step0, ck.eval_every);
+      if (!DP && step0 + ck.n_updates == ck.n_total && (ck.n_total - 1) % ck.eval_every != 0) ++n_ev;
     }
-    reinterpret_cast<uint64_t*>(st + 8)[1] += (uint64_t)(p.n_updates + n_ev);
-    st[0] = step0 + p.n_updates;
+    reinterpret_cast<uint64_t*>(st + 8)[0] = ck.seed;
+    reinterpret_cast<uint64_t*>(st + 8)[1] = ck.rng_ctr0 + (uint64_t)(ck.n_updates + n_ev);
+    st[0] = step0 + ck.n_updates;
   }
 }
 
@@ -1428,15 +1546,25 @@ __device__ __forceinline__ void owner_only_workgroup(const UArgs& p, float* smem
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wg = blockIdx.x;
   int32_t* flagp = p.state + 2;
+  const int n_chunks = (dp || p.chunks == nullptr) ? 1 : p.n_chunks;
+  UCk ck;
+  u_chunk_load(p, 0, ck);
   UOwn o;
   u_own_init(p, o, role.owner, false, XS, red, smem, lane0);
+  u_own_chunk(o, ck);
   const bool has_row = role.owner < p.n_owner;
   const int eo = (role.owner - p.n_owner + p.T) % p.T;
   const bool has_erow = p.do_eval && eo < p.NE;
   const int fk = u_fast_kind(p);                    // (one loop, the row picked per update: the evaluation code once)
-  int pending_eval = -1;
+  int pending_eval = -1, pending_chunk = 0;
+  for (int c = 0; c < n_chunks; ++c) {
+  if (c > 0) {      // chunk boundary: see unified_workgroup (a launch that gave up leaves every chunk at its first update)
+    u_chunk_load(p, c, ck);
+    u_own_chunk(o, ck);
+  }
   for (int t = 0; t < p.n_updates; ++t) {
     const int step = o.step0 + t;
+    [[maybe_unused]] const int pt = t + (int)ck.ubase;       // (diagnostics) update of the launch
     // (the time-out bit, sampled behind a barrier: every wavefront must take the same way out.  The
     // round trip sits in this workgroup's wait for the forward product.)
     if (run_aborted(flagp, red, tid)) break;
@@ -1457,20 +1585,23 @@ __device__ __forceinline__ void owner_only_workgroup(const UArgs& p, float* smem
     }
     if (__builtin_expect(pending_eval >= 0, 0)) {
       __syncthreads();
-      if (has_erow) u_owner_eval(p, XS, red, eo, pending_eval, u_eval_stream(p, o, pending_eval, false), o.a);
+      if (has_erow) u_owner_eval(p, XS, red, eo, u_eval_of(p, pending_chunk, pending_eval), o.a);
       pending_eval = -1;
     }
-    if (__builtin_expect(p.do_eval && step > 0 && (step - 1) % p.eval_every == 0, 0))
-      pending_eval = u_evals_before(step, p.eval_every) - 1;
+    if (__builtin_expect(p.do_eval && (step > 0 ? (step - 1) % p.eval_every == 0 : c > 0), 0)) {
+      pending_chunk = step > 0 ? c : c - 1;
+      pending_eval = step > 0 ? u_evals_before(step, p.eval_every) - 1 : u_last_eval(p.n_updates, p.eval_every);
+    }
     __syncthreads();
+  }
   }
   if (p.do_eval && !run_aborted(flagp, red, tid)) {
     if (pending_eval >= 0 && has_erow)
-      u_owner_eval(p, XS, red, eo, pending_eval, u_eval_stream(p, o, pending_eval, false), o.a);
-    if (o.step0 + p.n_updates == p.n_total && (!dp || p.n_updates == 0)) {
-      const int e = u_evals_before(p.n_total - 1, p.eval_every);
+      u_owner_eval(p, XS, red, eo, u_eval_of(p, pending_chunk, pending_eval), o.a);
+    if (ck.step0 + p.n_updates == p.n_total && (!dp || p.n_updates == 0)) {
+      const UEval ev = u_eval_of(p, n_chunks - 1, u_evals_before(p.n_total - 1, p.eval_every));
       __syncthreads();
-      if (has_erow) u_owner_eval(p, XS, red, eo, e, u_eval_stream(p, o, e, true), o.a);
+      if (has_erow) u_owner_eval(p, XS, red, eo, ev, o.a);
     }
   }
 }
@@ -1653,6 +1784,7 @@ bool persist_resolve(const PersistShape& s, UGeom* g, PersistEngine* e) {
   *g = c;
   e->kind = 1; e->streams = false;
   e->eval_single = e->eval_dp = c.eval_passes > 0;
+  e->block_launch = false;      // (bsig_fit_create decides: it reads the switches)
   e->workspace_bytes = u_data_bytes(c) + u_sync_bytes();
   return true;
 }
@@ -1694,6 +1826,10 @@ int persist_run(const PersistShape& s, const UGeom& g, const PersistBuffers& b, 
                                  (int64_t)g.Nh * s.feat_dim < ((int64_t)1 << 29))),
                "persistent updates: a resident data-parallel launch moves 16-byte gradient quads");
   if (n <= 0 && !b.adam_pending && !b.do_eval) return BSIG_OK;
+  // (a block: n_total updates in the launch; the widest tag is epoch * 4 + 3 in 32 bits)
+  BSIG_REQUIRE(!(b.chunks && !(b.n_chunks >= 1 && !b.grads && !b.xr_ready && b.do_eval && b.feat_ids == b.ids &&
+                               n >= 1 && b.n_total == n && (int64_t)b.n_chunks * n < (1 << 30))),
+               "persistent updates: a block of chunks runs on a single rank with the evaluations inside the launch");
   UArgs p{};
   p.B = s.batch; p.Bp = g.Bp; p.MT = g.MT;
   p.Fdim = s.feat_dim; p.KS = g.KS; p.ksteps = g.ksteps; p.KB = g.KB; p.WP = g.WP;
@@ -1738,6 +1874,7 @@ int persist_run(const PersistShape& s, const UGeom& g, const PersistBuffers& b, 
     p.y_test = b.y_test; p.ldy_test = b.ldy_test; p.test_loss = b.test_loss;
     // (the slab buffers are laid out for this call's passes: [3][eval_passes][k_slices][B][NhP])
   }
+  if (b.chunks) { p.chunks = b.chunks; p.n_chunks = b.n_chunks; }
   p.prof = reinterpret_cast<long long*>(persist_profile_buffer());
   if (p.prof) {
     const char* t0 = getenv("BSIG_PROF_T0");

@@ -14,8 +14,15 @@ struct PersistEngine {
   bool streams = false;         // (MDNN) the first layer is streamed: cross-correlation factor rows only
   bool eval_single = false;     // a single rank's call evaluates its held-out rows inside the launch
   bool eval_dp = false;         // ... and so do a data-parallel rank's launches (one per update)
+  bool block_launch = false;    // one launch may run several chunks of a fit (bsig_fit_run_block): linear heads with
+                                // the evaluations inside the launch (block_launch_resolved; single rank: the callers ask)
   size_t workspace_bytes = 0;
 };
+
+// the "several chunks per launch" answer of an engine (forced_single: BSIG_FIT_CHUNK_PER_LAUNCH=1)
+inline bool block_launch_resolved(int kind, bool eval_single, bool forced_single) {
+  return kind == 1 && eval_single && !forced_single;
+}
 
 struct PersistShape {
   int batch, feat_dim, out_dim, n_comp;
@@ -71,6 +78,10 @@ struct PersistBuffers : PersistCommon {
                                           // (null: feats[step*batch + i])
   int64_t w_off, b_off;                   // head weights [Nh, feat_dim] / bias [Nh] inside the flat buffers
   int64_t eval_row0 = 0;                  // held-out rows: feats[eval_row0 .. +n_test)
+  // A block of chunks in one launch (bsig.h: bsig_fit_chunk; device memory, checked by the caller): feats, y, ids
+  // (= feat_ids), train_loss and test_loss are the block's, n_test the most of any chunk, n_total the updates of
+  // the whole launch; every chunk evaluates inside the launch.  null: one chunk, described by the fields above.
+  const bsig_fit_chunk* chunks = nullptr; int n_chunks = 1;
 };
 
 // The tiling of a shape and whether the device can hold every workgroup of its launch at once (asks

@@ -271,11 +271,18 @@ class MDNN(nn.Module):
     def _resident_calls(self):
         return self._dp.resident_calls() if self._dp is not None else 0
 
-    def _give_up_a_level(self, resident_calls_before):
+    def _give_up_a_level(self, resident_calls_before, block_launches_before=None):
         """After a persistent launch timed out.  A data-parallel rank that stayed resident across the
         gradient exchange in the calls since ``resident_calls_before`` first goes back to one launch per
-        update (the exchange stream was not served in time: the launch itself had the chip); a time-out
-        after that, or without the resident exchange: the per-phase kernels."""
+        update (the exchange stream was not served in time: the launch itself had the chip); a model that
+        ran blocks of chunks in one launch since ``block_launches_before`` first goes back to one launch per
+        chunk; a time-out after that, or without either: the per-phase kernels."""
+        if block_launches_before is not None and getattr(self, '_block_launches', 0) > block_launches_before:
+            import warnings
+            warnings.warn('bayes_sim_ig_amd: a persistent launch over a block of chunks timed out; this model '
+                          'continues with one launch per chunk', RuntimeWarning, stacklevel=3)
+            self._no_block_launch = True
+            return
         if self._dp is not None and self._dp.resident_calls() > resident_calls_before:
             import warnings
             warnings.warn('bayes_sim_ig_amd: a data-parallel launch that stays resident across the gradient '
@@ -481,6 +488,130 @@ class MDNN(nn.Module):
                 self._restore(snap)
                 self._give_up_a_level(calls0)
 
+    def _ensure_plan(self, lib, cfg, batch_size, n_train, n_test, n_updates):
+        """The fit plan (graphs, persistent-kernel geometry), keyed by everything baked into it."""
+        key = (batch_size, max(n_test, self._bufs.get('cap_test', 0)), n_updates,
+               cfg.head.eps_noise, cfg.lr, cfg.head.min_weight, cfg.head.ll_limit,
+               max(n_train, self._bufs.get('cap_train', 0)))
+        if self._plan is None or self._plan_key != key:
+            if self._plan:
+                lib.bsig_fit_destroy(self._plan)
+            handle = C.c_void_p()
+            # (a model that met a persistent-launch time-out stays on the per-phase kernels: a plan
+            # option, not the process-wide environment switch)
+            flags = _lib.PLAN_NO_PERSISTENT if getattr(self, '_no_persistent', False) else 0
+            _lib.check(lib.bsig_fit_create_ex(C.byref(cfg), batch_size, key[7], key[1],
+                                              n_updates, flags, C.byref(handle)))
+            self._plan, self._plan_key = handle, key
+            self._bufs['cap_test'], self._bufs['cap_train'] = key[1], key[7]
+
+    @staticmethod
+    def block_prefix(sizes, test_frac):
+        """How many leading chunks of ``sizes`` pairs a block launch can take: those with at least one
+        held-out row (a chunk without one evaluates nothing inside a launch: it runs on its own)."""
+        k = 0
+        for n_tot in sizes:
+            if n_tot - max(int(n_tot * (1.0 - test_frac)), 1) < 1:
+                break
+            k += 1
+        return k
+
+    @_on_model_device
+    def run_training_block(self, feats, y_data, sizes, n_updates, batch_size, test_frac=0.2):
+        """run_training (reference mdnn.py:180-243) on consecutive chunks of ``sizes`` pairs whose RFF
+        features ``feats`` and targets ``y_data`` lie behind each other, as ONE launch of the persistent
+        update kernel (bsig_fit_run_block).  Returns the chunks' PendingLogs, or None when this model's plan
+        runs one chunk per launch (the caller then calls run_training per chunk; nothing has been drawn
+        from an RNG).  The minibatch ids and jitter seeds are drawn chunk by chunk with the calls of the
+        per-chunk path, in its order."""
+        if (self._dp is not None or not self._flat.is_cuda or getattr(self, '_no_block_launch', False)
+                or getattr(self, 'rff', None) is None or len(sizes) < 1):
+            return None
+        lib = self._gpu()
+        self.train()
+        cfg = self._cfg()
+        dev = self._flat.device
+        d, rows = self.output_dim, int(sum(sizes))
+        assert feats.shape[0] == rows == y_data.shape[0] and feats.is_cuda and feats.dtype == torch.float32
+        split = [(max(int(n * (1.0 - test_frac)), 1), n - max(int(n * (1.0 - test_frac)), 1)) for n in sizes]
+        n_train, n_test = max(a for a, _ in split), max(b for _, b in split)
+        self._ensure_plan(lib, cfg, batch_size, n_train, n_test, n_updates)
+        st = _lib.stream()
+        n_chunks, n_ids = len(sizes), len(sizes) * n_updates * batch_size
+        every = max(n_updates // 5, 1)
+        n_e = len([it for it in range(n_updates) if it % every == 0 or it + 1 == n_updates])
+        ldy = _lib.round_up(d, 4)
+        y_stage = self._buf('blk_y', rows * ldy)
+        stage = self._buf('blk_stage', 16 * n_chunks + n_ids, torch.int32)       # [chunk table | ids]
+        train_loss, test_loss = self._buf('blk_train_loss', n_chunks * n_updates), self._buf('blk_test_loss', n_chunks * n_e)
+        state = self._buf('state', 16, torch.int32)
+        ws = self._buf('fit_ws', int(lib.bsig_fit_workspace_bytes(self._plan)) // 4 + 1)
+        # The binding is a complete one of the block's FIRST chunk (its rows, held-out rows, ids and log slots
+        # are the first of the block's): whoever drives the plan through the per-call entry points afterwards
+        # finds every buffer it reads in place.  The summary rows themselves are not staged, as in a
+        # per-chunk call whose features are handed over.
+        ldx = _lib.round_up(self.input_dim, 4)
+        if sizes[0] > self._bufs.get('cap_rows', 0):
+            self._bufs.pop('x_stage', None), self._bufs.pop('y_stage', None)
+            self._bufs['cap_rows'] = sizes[0]
+        x_stage = self._buf('x_stage', self._bufs['cap_rows'] * ldx)
+        coeff, ldc, off = self._rff_args()
+        fb = _lib.FitBuffers()
+        fb.params, fb.grads = self._flat.data_ptr(), self._flat_grad.data_ptr()
+        fb.exp_avg, fb.exp_avg_sq = self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr()
+        fb.rff_coeff = None if coeff is None else coeff.data_ptr()
+        fb.ld_coeff = ldc
+        fb.rff_offset = None if off is None else off.data_ptr()
+        fb.x_train, fb.ldx_train, fb.n_train = x_stage.data_ptr(), ldx, split[0][0]
+        fb.y_train, fb.ldy_train = y_stage.data_ptr(), ldy
+        fb.x_test, fb.ldx_test, fb.n_test = x_stage.data_ptr() + 4 * split[0][0] * ldx, ldx, split[0][1]
+        fb.y_test, fb.ldy_test = y_stage.data_ptr() + 4 * split[0][0] * ldy, ldy
+        fb.ids_table = stage.data_ptr() + 64 * n_chunks
+        fb.train_loss, fb.test_loss = train_loss.data_ptr(), test_loss.data_ptr()
+        fb.state = state.data_ptr()
+        fb.workspace, fb.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+        flags = _lib.FIT_GRAPH if type(self).USE_GRAPH else 0
+        _lib.check(lib.bsig_fit_bind(self._plan, C.byref(fb), flags))
+        if n_chunks > int(lib.bsig_fit_block_chunks(self._plan, n_train)):
+            return None
+        ys, ldy_src = _lib.as_f32_rows(y_data, dev)
+        assert ys.shape[1] == d
+        if self.output_lows is not None:                       # mdnn.py:204-205, once over the block's rows
+            _lib.check(lib.bsig_normalize_rows(
+                _lib.ptr(ys), ldy_src, _lib.ptr(self.output_lows),
+                _lib.ptr(self.output_highs), _lib.ptr(y_stage), ldy, rows, d, st))
+        else:
+            _lib.check(lib.bsig_copy_rows(_lib.ptr(ys), ldy_src, None, _lib.ptr(y_stage), ldy, rows, d, st))
+        # ids (mdnn.py:219-222) and seeds: one numpy draw and one torch draw per chunk, as the per-chunk calls
+        ring = self._bufs.setdefault('blk_ring', {'slots': [], 'next': 0})
+        if not ring['slots'] or ring['slots'][0][0].numel() < 16 * n_chunks + n_ids:
+            ring['slots'] = [[torch.empty(16 * n_chunks + n_ids, dtype=torch.int32, pin_memory=True), None]
+                             for _ in range(4)]
+        slot = ring['slots'][ring['next'] % 4]
+        ring['next'] += 1
+        if slot[1] is not None:
+            slot[1].synchronize()
+        host = slot[0].numpy()
+        seeds = []
+        for c, (n_tr, _) in enumerate(split):
+            lo = 16 * n_chunks + c * n_updates * batch_size
+            host[lo:lo + n_updates * batch_size] = np.random.randint(
+                0, n_tr, (n_updates, batch_size), dtype=np.int32).reshape(-1) + np.int32(sum(sizes[:c]))
+            seeds.append(self._seed())
+        table = _lib.fit_chunk_table(sizes, seeds, n_updates, batch_size, test_frac)
+        host[:16 * n_chunks] = table.view(np.int32)
+        stage[:16 * n_chunks + n_ids].copy_(slot[0][:16 * n_chunks + n_ids], non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record()
+        packed = torch.empty(n_chunks, 2 * n_e + 1, dtype=torch.float32, device=dev)
+        _lib.check(lib.bsig_fit_run_block(
+            self._plan, _lib.ptr(feats), feats.stride(0), rows, _lib.ptr(y_stage), ldy,
+            C.c_void_p(stage.data_ptr() + 64 * n_chunks), n_ids, C.c_void_p(table.ctypes.data),
+            _lib.ptr(stage), n_chunks, _lib.ptr(train_loss), _lib.ptr(test_loss), _lib.ptr(packed),
+            batch_size, st))
+        self._block_launches = getattr(self, '_block_launches', 0) + 1
+        return [PendingLogs(packed[c], n_e, split[c][1], type(self).VERBOSE) for c in range(n_chunks)]
+
     def _may_time_out(self):
         """Could the next call run a persistent kernel?  (Unknown before the first plan exists.)"""
         if getattr(self, '_no_persistent', False) or os.environ.get('BSIG_NO_PERSISTENT') == '1':
@@ -499,21 +630,7 @@ class MDNN(nn.Module):
         n_train = max(int(n_tot * (1.0 - test_frac)), 1)
         n_test = n_tot - n_train
         st = _lib.stream()
-        # plan (graphs, persistent-kernel geometry) keyed by everything baked into it
-        key = (batch_size, max(n_test, self._bufs.get('cap_test', 0)), n_updates,
-               cfg.head.eps_noise, cfg.lr, cfg.head.min_weight, cfg.head.ll_limit,
-               max(n_train, self._bufs.get('cap_train', 0)))
-        if self._plan is None or self._plan_key != key:
-            if self._plan:
-                lib.bsig_fit_destroy(self._plan)
-            handle = C.c_void_p()
-            # (a model that met a persistent-launch time-out stays on the per-phase kernels: a plan
-            # option, not the process-wide environment switch)
-            flags = _lib.PLAN_NO_PERSISTENT if getattr(self, '_no_persistent', False) else 0
-            _lib.check(lib.bsig_fit_create_ex(C.byref(cfg), batch_size, key[7], key[1],
-                                              n_updates, flags, C.byref(handle)))
-            self._plan, self._plan_key = handle, key
-            self._bufs['cap_test'], self._bufs['cap_train'] = key[1], key[7]
+        self._ensure_plan(lib, cfg, batch_size, n_train, n_test, n_updates)
         # a cross-correlation summary may arrive as factor rows (summarizers.CrossCorrFactors):
         # plans whose first layer lives in the persistent kernel consume them as they are
         factored = isinstance(x_data, CrossCorrFactors)

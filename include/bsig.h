@@ -359,6 +359,52 @@ int bsig_fit_updates(bsig_fit_plan* plan, int64_t n_updates, bsig_stream_t strea
  * (bit 0 non-finite, bit 1 poll time-out) as a float. */
 int bsig_fit_pack_logs(bsig_fit_plan* plan, int64_t n_updates, float* out,
                        bsig_stream_t stream);
+/* A BLOCK of consecutive chunks in ONE launch of the persistent update kernel: what a caller that fits
+ * many chunks (bayes_sim_main.py:157-167 calling bayes_sim.py:91-114, i.e. mdnn.py:180-243 once per
+ * chunk) would otherwise do as bind / set_features / begin / run / pack_logs per chunk.  Between two
+ * chunks the reference keeps the weights, creates a fresh Adam (mdnn.py:203), takes the next chunk's rows
+ * (mdnn.py:206-211) and draws new minibatch ids (mdnn.py:219-222): the kernel keeps its weight tiles on
+ * the chip across the boundary, restarts the moments in registers and runs the evaluation after a chunk's
+ * last update (mdnn.py:235-242) in the waits of the next chunk's first updates.  Every number is the one
+ * the per-chunk calls produce, bit for bit.
+ * One table entry per chunk.  The chunk's rows are rows row0 .. row0 + n_train + n_test of the block's
+ * feature and target matrices, the n_test held-out rows last; its [n_updates, batch] minibatch ids (rows of
+ * the BLOCK: row0 + the row number inside the chunk, which is < n_train) start at ids[ids_off], ids_off =
+ * upd_base * batch.  seed / rng_ctr0: the jitter seed and first
+ * stream of the chunk, what a per-chunk begin call would put into the state block (rng_ctr0 = 1).
+ * upd_base / eval_base: updates / evaluations of the launch before the chunk (the kernel's flag and
+ * granule tags count these; fewer than 2^30 updates per launch); the chunk's losses go to
+ * train_loss[train_slot ..] and test_loss[test_slot ..] with train_slot = upd_base, test_slot = eval_base. */
+typedef struct bsig_fit_chunk {
+  int64_t row0;
+  int32_t n_train, n_test;
+  int64_t ids_off;
+  uint64_t seed, rng_ctr0;
+  int32_t n_updates, eval_every;
+  int32_t train_slot, test_slot;
+  int32_t upd_base, eval_base;
+} bsig_fit_chunk;   /* 64 bytes */
+/* How many chunks one launch of this plan (as bound) may run: 0 unless its updates run in the persistent
+ * kernel of the linear heads with the evaluations inside the launch, on a single rank, and each chunk of
+ * up to n_train training rows keeps one feature row per row.  Resolved when the plan is created
+ * (BSIG_FIT_CHUNK_PER_LAUNCH=1, read then, forces 0: one launch per chunk, for A/B runs). */
+int bsig_fit_block_chunks(const bsig_fit_plan* plan, int64_t n_train);
+/* Run the block (plan bound; its x / y / ids / loss buffers are not read: the block's are).  feats
+ * [rows, ld_feats] and y [rows, ldy] (normalised targets) on the device; ids [n_ids] and chunks_dev
+ * [n_chunks] on the device, chunks_host the same table on the host (checked against rows, n_ids and the
+ * plan before anything is enqueued).  Every chunk takes the plan's n_updates updates.  train_loss
+ * [n_chunks * n_updates], test_loss [n_chunks * E] scratch; packed_logs [n_chunks][2 E + 1]: per chunk
+ * what bsig_fit_pack_logs gives for one call (the flag word is the block's).  Includes the begin step
+ * (state block, flags; norm_batch as in bsig_fit_begin). */
+int bsig_fit_run_block(bsig_fit_plan* plan, const float* feats, int64_t ld_feats, int64_t rows,
+                       const float* y, int64_t ldy, const int32_t* ids, int64_t n_ids,
+                       const bsig_fit_chunk* chunks_host, const bsig_fit_chunk* chunks_dev, int n_chunks,
+                       float* train_loss, float* test_loss, float* packed_logs, int64_t norm_batch,
+                       bsig_stream_t stream);
+/* (tests) the "several chunks per launch" answer for an engine description: kind as
+ * bsig_fit_is_persistent reports it, whether a single rank evaluates inside the launch, whether the
+ * per-plan switch forces one chunk per launch. */
+int bsig_debug_block_launch(int engine_kind, int eval_in_launch, int forced_single);
 /* Data-parallel pieces (BSIG_FIT_SPLIT_ADAM; mdnn.py:229-233 with the exchange
  * the reference does not have between loss.backward() and optimizer.step()):
  * bsig_fit_grad = forward + NLL + backward of one minibatch into `grads`
