@@ -10,6 +10,8 @@ import os
 import numpy as np
 import torch
 
+from .protocol import eval_updates, split_rows
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (BSIG_LIB_PATH: another build of the same library, for A/B measurements of kernel variants)
 LIB_PATH = os.environ.get('BSIG_LIB_PATH') or os.path.join(_HERE, 'lib', 'libbsig_hip.so')
@@ -62,15 +64,15 @@ FIT_CHUNK = np.dtype([('row0', '<i8'), ('n_train', '<i4'), ('n_test', '<i4'), ('
 def fit_chunk_table(sizes, seeds, n_updates, batch_size, test_frac):
     """The chunk table of a block launch (bsig_fit_run_block) for consecutive chunks of ``sizes`` pairs:
     rows and ids of the chunks follow each other, every chunk holds out its last rows (mdnn.py:206-211),
-    evaluates every max(n_updates // 5, 1) updates and after the last (mdnn.py:235), starts its jitter
+    evaluates at protocol.eval_updates (mdnn.py:235), starts its jitter
     streams at 1 with its own seed (what bsig_fit_begin does per call) and logs behind the chunk before."""
-    every = max(n_updates // 5, 1)
-    n_evals = len([it for it in range(n_updates) if it % every == 0 or it + 1 == n_updates])
+    every, eval_its = eval_updates(n_updates)
+    n_evals = len(eval_its)
     table = np.zeros(len(sizes), dtype=FIT_CHUNK)
     row0 = 0
     for c, (n_tot, seed) in enumerate(zip(sizes, seeds)):
-        n_train = max(int(n_tot * (1.0 - test_frac)), 1)
-        table[c] = (row0, n_train, n_tot - n_train, c * n_updates * batch_size, seed, 1, n_updates, every,
+        n_train, n_test = split_rows(n_tot, test_frac)
+        table[c] = (row0, n_train, n_test, c * n_updates * batch_size, seed, 1, n_updates, every,
                     c * n_updates, c * n_evals, c * n_updates, c * n_evals)
         row0 += n_tot
     return table

@@ -107,7 +107,7 @@ class BayesSim(object):
         return self.summarizer_fxn(states, actions)
 
     def _lazy_summaries(self):
-        return (getattr(self.model, 'rff', None) is None and self.model._flat.is_cuda and
+        return (self.model.rff is None and self.model._flat.is_cuda and
                 os.environ.get('BSIG_NO_FUSED_SUMMARY') != '1')
 
     def run_training(self, params, traj_states, traj_actions, _defer=False, _finite_flag=None,
@@ -130,75 +130,64 @@ class BayesSim(object):
         pre-recorded pairs: consecutive chunks of at most
         NUM_TRAIN_TRAJ_PER_BATCH pairs, ``run_training`` on each.
         Returns the list of per-chunk log dicts."""
-        if self.model._flat.is_cuda and self.model._may_time_out():
-            # the chunks' logs are read after the last chunk is enqueued: if a persistent launch
-            # turns out not to have had the GPU to itself (its bounded polls gave up), the whole
-            # loop is repeated from here on the per-phase kernels.  A data-parallel group does the
-            # same TOGETHER: the time-out bit travels in the logs every call sums over the ranks
-            # (bsig_fit_run_dp), the rank that timed out keeps enqueueing its all-reduces, so every
-            # rank reads the same flag at the same chunk, restores and repeats
-            # A rank that stayed resident across the exchange first goes back to one launch per update
-            # (MDNN._give_up_a_level), the per-phase kernels come second.
-            from .mdnn import PersistentTimeout
-            # A model that ran blocks of chunks in one launch first goes back to one launch per chunk.
-            snap = self.model._snapshot()
-            for _ in range(2):
-                calls0 = self.model._resident_calls()
-                blocks0 = getattr(self.model, '_block_launches', 0)
-                try:
-                    return self._fit_once(params, traj_states, traj_actions)
-                except PersistentTimeout:
-                    self.model._restore(snap)
-                    self.model._give_up_a_level(calls0, blocks0)
-        return self._fit_once(params, traj_states, traj_actions)
+        # the chunks' logs are read after the last chunk is enqueued: if a persistent launch turns out not
+        # to have had the GPU to itself, the whole loop is repeated from here (MDNN._retrying)
+        return self.model._retrying(lambda: self._fit_once(params, traj_states, traj_actions))
 
-    def _fit_once(self, params, traj_states, traj_actions):
-        n, done, pending = params.shape[0], 0, []
-        dp = getattr(self.model, '_dp', None)
-        if dp is not None:
-            # one all-reduce per update: every rank must run the same chunk schedule, or the
-            # rank with an extra chunk waits for its peers forever
-            counts = dp.gather_counts(n, device=self.model._flat.device)
+    def _check_equal_counts(self, n):
+        """One all-reduce per update: every rank of a data-parallel group must run the same chunk
+        schedule, or the rank with an extra chunk waits for its peers forever."""
+        if self.model._dp is not None:
+            counts = self.model._dp.gather_counts(n, device=self.model._flat.device)
             if len(set(counts)) != 1:
                 raise ValueError('data-parallel fit needs the same number of pairs on every rank '
                                  '(got %s); see dp.equal_shards' % (counts,))
-        flag = None
-        if torch.is_tensor(traj_states) and traj_states.is_cuda:
-            flag = torch.zeros(1, dtype=torch.int32, device=traj_states.device)
-        # The summaries (and an MDRFF's RFF features, rff.py:128-132) are pure functions of the
-        # row: both are computed for a block of chunks at once -- one summarizer launch over
-        # up to 32000 trajectories (and one large MFMA GEMM) instead of one small one per chunk
-        block = 0
-        is_rff = getattr(self.model, 'rff', None) is not None
-        if flag is not None and os.environ.get('BSIG_NO_FIT_PREPROJECT') != '1':
-            row_bytes = 4 * (self.model.input_dim + (self.model.rff.n_feat if is_rff else 0))
-            chunks = max(min(BayesSim.FIT_BLOCK_CHUNKS,
-                             BayesSim.FIT_BLOCK_BYTES // (row_bytes * BayesSim.NUM_TRAIN_TRAJ_PER_BATCH)), 1)
-            block = chunks * BayesSim.NUM_TRAIN_TRAJ_PER_BATCH
+
+    def _block_rows(self):
+        """Pairs per block of fit(): the summaries (and an MDRFF's RFF features, rff.py:128-132) are pure
+        functions of the row, so both are computed for a block of chunks at once -- one summarizer launch
+        over up to 32000 trajectories (and one large MFMA GEMM) instead of one small one per chunk."""
+        row_bytes = 4 * (self.model.input_dim + (self.model.rff.n_feat if self.model.rff is not None else 0))
+        chunks = max(min(BayesSim.FIT_BLOCK_CHUNKS,
+                         BayesSim.FIT_BLOCK_BYTES // (row_bytes * BayesSim.NUM_TRAIN_TRAJ_PER_BATCH)), 1)
+        return chunks * BayesSim.NUM_TRAIN_TRAJ_PER_BATCH
+
+    def _block_launch_sizes(self, n, lo, hi):
+        """The chunks of pairs [lo, hi) of ``n`` that one launch can take (a chunk without a held-out row
+        runs on its own)."""
+        sizes, at = [], lo
+        while at < hi:
+            sizes.append(BayesSim.get_n_trajs_per_batch(n, at))
+            at += sizes[-1]
+        return sizes[:self.model.block_prefix(sizes, BayesSim.TEST_FRACTION)]
+
+    def _fit_once(self, params, traj_states, traj_actions):
+        """Block by block: the block's summaries and features when ``done`` leaves the block before; the
+        block's chunks in ONE launch of the persistent update kernel where the model's plan can; else chunk
+        by chunk.  The logs (and the isfinite asserts) are read back after the last chunk is enqueued: one
+        host synchronisation for the whole fit."""
+        model, n, done, pending = self.model, params.shape[0], 0, []
+        self._check_equal_counts(n)
+        on_gpu = torch.is_tensor(traj_states) and traj_states.is_cuda
+        flag = torch.zeros(1, dtype=torch.int32, device=traj_states.device) if on_gpu else None
+        block = self._block_rows() if on_gpu and os.environ.get('BSIG_NO_FIT_PREPROJECT') != '1' else 0
         lo = hi = 0
         summ = feats = None
         while done < n:
-            m = BayesSim.get_n_trajs_per_batch(n, done)
-            if block and done + m > hi:
+            if block and done >= hi:
                 lo, hi = done, min(n, done + block)
                 summ = self._summarize(traj_states[lo:hi], traj_actions[lo:hi], flag, lazy=True)
-                feats = self.model.rff.to_features(summ) if is_rff else None
-                if feats is not None and dp is None:
-                    # the block's chunks in ONE launch of the persistent update kernel, where the model's
-                    # plan can (else: chunk by chunk below; a chunk without a held-out row runs on its own)
-                    sizes, at = [], lo
-                    while at < hi:
-                        sizes.append(BayesSim.get_n_trajs_per_batch(n, at))
-                        at += sizes[-1]
-                    sizes = sizes[:self.model.block_prefix(sizes, BayesSim.TEST_FRACTION)]
-                    rows = sum(sizes)
-                    logs = self.model.run_training_block(
-                        feats[:rows], params[lo:lo + rows], sizes, BayesSim.NUM_GRAD_UPDATES,
-                        BayesSim.MINIBATCH_SIZE, BayesSim.TEST_FRACTION) if sizes else None
-                    if logs is not None:
-                        pending.extend(logs)
-                        done += rows
-                        continue
+                feats = model.rff.to_features(summ) if model.rff is not None else None
+                sizes = self._block_launch_sizes(n, lo, hi) if feats is not None and model._dp is None else []
+                rows = sum(sizes)
+                logs = model.run_training_block(
+                    feats[:rows], params[lo:lo + rows], sizes, BayesSim.NUM_GRAD_UPDATES,
+                    BayesSim.MINIBATCH_SIZE, BayesSim.TEST_FRACTION) if sizes else None
+                if logs is not None:
+                    pending.extend(logs)
+                    done += rows
+                    continue
+            m = BayesSim.get_n_trajs_per_batch(n, done)
             if block:
                 pending.append(self.run_training(
                     params[done:done + m], None, None, _defer=True,
@@ -210,8 +199,6 @@ class BayesSim(object):
                                                  traj_actions[done:done + m], _defer=True,
                                                  _finite_flag=flag))
             done += m
-        # one host synchronisation for the whole fit: the chunks' logs (and the
-        # isfinite asserts) are read back after the last chunk is enqueued
         logs = [p.result() for p in pending]
         assert flag is None or int(flag.item()) == 0   # summarizers.py:120
         return logs

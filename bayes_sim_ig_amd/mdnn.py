@@ -9,8 +9,11 @@ are fp32-MFMA GEMMs, the mixture head + NLL + backward is one fused kernel,
 Adam runs over the flat buffer, and ``run_training`` replays the whole update
 from a HIP graph (csrc/estimator.hip).  There is no CPU fallback.
 """
+import contextlib
 import ctypes as C
+import functools
 import os
+import warnings
 from collections import OrderedDict
 
 import numpy as np
@@ -20,6 +23,7 @@ import torch.nn as nn
 from . import _lib
 from . import pdf
 from . import dp as _dp
+from .protocol import eval_updates, split_rows
 from .summarizers import CrossCorrFactors
 
 _ACT_CODES = {nn.Tanh: _lib.ACT_TANH, nn.ReLU: _lib.ACT_RELU,
@@ -30,8 +34,6 @@ _ACT_CODES = {nn.Tanh: _lib.ACT_TANH, nn.ReLU: _lib.ACT_RELU,
 def _on_model_device(fn):
     """Run a method with the model's GPU as the current HIP device and its torch stream
     as the launch stream (a model built with device='cuda:1' must not launch on cuda:0)."""
-    import functools
-
     @functools.wraps(fn)
     def wrapped(self, *args, **kwargs):
         flat = getattr(self, '_flat', None)
@@ -114,6 +116,8 @@ class MDNN(nn.Module):
     VERBOSE = True       # print the 6 train/test losses per call like the reference
     USE_GRAPH = True     # replay the update from a HIP graph
     PAD_TRUNK_TO = 128   # hidden width the persistent update kernel is built for
+    rff = None           # the feature map of an MDRFF
+    _plan = None         # (a model whose construction failed is still finalised: __del__)
 
     def __init__(self, input_dim, output_dim, output_lows, output_highs,
                  n_gaussians, full_covariance, hidden_layers, activation, lr,
@@ -169,6 +173,10 @@ class MDNN(nn.Module):
         self._plan_key = None
         self._bufs = {}
         self._dp = None
+        # the time-out ladder (_retrying / _give_up_a_level): what this model has given up so far
+        self._no_persistent = False
+        self._no_block_launch = False
+        self._block_launches = 0
         self._flatten(device)
 
     # ------------------------------------------------------------ plumbing
@@ -245,7 +253,7 @@ class MDNN(nn.Module):
         return self
 
     def _drop_plan(self):
-        if getattr(self, '_plan', None):
+        if self._plan:
             _lib.load().bsig_fit_destroy(self._plan)
         self._plan, self._plan_key = None, None
         self._bufs = {}
@@ -268,8 +276,32 @@ class MDNN(nn.Module):
         self._flat.copy_(snap[0]); self._exp_avg.copy_(snap[1]); self._exp_avg_sq.copy_(snap[2])
         np.random.set_state(snap[3]); torch.set_rng_state(snap[4])
 
-    def _resident_calls(self):
-        return self._dp.resident_calls() if self._dp is not None else 0
+    def _may_time_out(self):
+        """Could the next call run a persistent kernel?  (Unknown before the first plan exists.)"""
+        if not self._flat.is_cuda or self._no_persistent or os.environ.get('BSIG_NO_PERSISTENT') == '1':
+            return False
+        return self._plan is None or bool(_lib.load().bsig_fit_is_persistent(self._plan))
+
+    def _retrying(self, fn):
+        """``fn()``, the work of one run_training or one BayesSim.fit whose logs it reads itself -- repeated
+        from a snapshot, one level further down (_give_up_a_level), after each of its first two time-outs;
+        a third one propagates, and so does any where no persistent kernel could have run.  A data-parallel
+        group does this TOGETHER: the time-out bit travels in the logs every call sums over the ranks
+        (bsig_fit_run_dp) and the rank that timed out keeps enqueueing its all-reduces, so every rank reads
+        the same flag in the same call, restores and repeats it with its peers."""
+        if not self._may_time_out():
+            return fn()
+        snap = self._snapshot()
+        for attempt in range(3):
+            calls0 = self._dp.resident_calls() if self._dp is not None else 0
+            blocks0 = self._block_launches
+            try:
+                return fn()
+            except PersistentTimeout:
+                if attempt == 2:
+                    raise
+                self._restore(snap)
+                self._give_up_a_level(calls0, blocks0)
 
     def _give_up_a_level(self, resident_calls_before, block_launches_before=None):
         """After a persistent launch timed out.  A data-parallel rank that stayed resident across the
@@ -277,27 +309,24 @@ class MDNN(nn.Module):
         update (the exchange stream was not served in time: the launch itself had the chip); a model that
         ran blocks of chunks in one launch since ``block_launches_before`` first goes back to one launch per
         chunk; a time-out after that, or without either: the per-phase kernels."""
-        if block_launches_before is not None and getattr(self, '_block_launches', 0) > block_launches_before:
-            import warnings
+        if block_launches_before is not None and self._block_launches > block_launches_before:
             warnings.warn('bayes_sim_ig_amd: a persistent launch over a block of chunks timed out; this model '
-                          'continues with one launch per chunk', RuntimeWarning, stacklevel=3)
+                          'continues with one launch per chunk', RuntimeWarning, stacklevel=4)
             self._no_block_launch = True
             return
         if self._dp is not None and self._dp.resident_calls() > resident_calls_before:
-            import warnings
             warnings.warn('bayes_sim_ig_amd: a data-parallel launch that stays resident across the gradient '
                           'exchange timed out waiting for the exchange; this model continues with one launch '
-                          'per update', RuntimeWarning, stacklevel=3)
+                          'per update', RuntimeWarning, stacklevel=4)
             self._dp.set_resident(False)
             return
         self._disable_persistent()
 
     def _disable_persistent(self):
         """From now on this model's plans use the per-phase kernels."""
-        import warnings
         warnings.warn('bayes_sim_ig_amd: a persistent update launch timed out waiting for another workgroup '
                       '(GPU shared with another process?); this model continues on the per-phase kernels, '
-                      'which are slower', RuntimeWarning, stacklevel=3)
+                      'which are slower', RuntimeWarning, stacklevel=4)
         self._no_persistent = True
         self._drop_plan()
 
@@ -470,23 +499,11 @@ class MDNN(nn.Module):
         'test_loss': [...]} with the same 6 logging points.  ``ids_table``
         [n_updates, batch] (optional) overrides the numpy-RNG minibatch draw
         (teacher forcing for parity tests)."""
-        if _defer or not self._flat.is_cuda:
-            # (deferred logs: the caller -- BayesSim.fit -- holds the snapshot and repeats its loop)
+        def once():
             return self._run_training_once(x_data, y_data, n_updates, batch_size, test_frac,
                                            ids_table, _defer, _feats)
-        snap = self._snapshot() if self._may_time_out() else None
-        for attempt in range(3):
-            calls0 = self._resident_calls()
-            try:
-                return self._run_training_once(x_data, y_data, n_updates, batch_size, test_frac,
-                                               ids_table, False, _feats)
-            except PersistentTimeout:
-                # (a data-parallel rank: the flag is the SUM over the ranks of the call's logs -- every
-                # rank of the group arrives here in the same call and repeats it with its peers)
-                if snap is None or attempt == 2:
-                    raise
-                self._restore(snap)
-                self._give_up_a_level(calls0)
+        # (deferred logs: the caller -- BayesSim.fit -- holds the snapshot and repeats its loop)
+        return once() if _defer else self._retrying(once)
 
     def _ensure_plan(self, lib, cfg, batch_size, n_train, n_test, n_updates):
         """The fit plan (graphs, persistent-kernel geometry), keyed by everything baked into it."""
@@ -499,7 +516,7 @@ class MDNN(nn.Module):
             handle = C.c_void_p()
             # (a model that met a persistent-launch time-out stays on the per-phase kernels: a plan
             # option, not the process-wide environment switch)
-            flags = _lib.PLAN_NO_PERSISTENT if getattr(self, '_no_persistent', False) else 0
+            flags = _lib.PLAN_NO_PERSISTENT if self._no_persistent else 0
             _lib.check(lib.bsig_fit_create_ex(C.byref(cfg), batch_size, key[7], key[1],
                                               n_updates, flags, C.byref(handle)))
             self._plan, self._plan_key = handle, key
@@ -511,10 +528,83 @@ class MDNN(nn.Module):
         held-out row (a chunk without one evaluates nothing inside a launch: it runs on its own)."""
         k = 0
         for n_tot in sizes:
-            if n_tot - max(int(n_tot * (1.0 - test_frac)), 1) < 1:
+            if split_rows(n_tot, test_frac)[1] < 1:
                 break
             k += 1
         return k
+
+    # ---- what a per-chunk call and a block launch share: staging, the pinned upload, the binding
+    def _row_capacity(self, n_tot):
+        """Rows the chunk staging buffers hold (fixed addresses across calls: graph replay), grown to
+        ``n_tot``."""
+        if n_tot > self._bufs.get('cap_rows', 0):
+            self._bufs.pop('x_stage', None), self._bufs.pop('y_stage', None)
+            self._bufs['cap_rows'] = n_tot
+        return self._bufs['cap_rows']
+
+    def _stage_targets(self, lib, ys, ldy_src, y_stage, ldy, rows, st):
+        """``y_stage`` <- the targets, normalised to the unit box where the model has one (mdnn.py:204-205)."""
+        if self.output_lows is not None:
+            _lib.check(lib.bsig_normalize_rows(
+                _lib.ptr(ys), ldy_src, _lib.ptr(self.output_lows),
+                _lib.ptr(self.output_highs), _lib.ptr(y_stage), ldy, rows, self.output_dim, st))
+        else:
+            _lib.check(lib.bsig_copy_rows(_lib.ptr(ys), ldy_src, None, _lib.ptr(y_stage),
+                                          ldy, rows, self.output_dim, st))
+
+    @contextlib.contextmanager
+    def _pinned_upload(self, ring, dst, n):
+        """Yields ``n`` pinned host int32 for the caller to fill; on exit they are on their way to
+        ``dst[:n]``.  A truly asynchronous upload: a pageable source would make the copy wait for the
+        stream to drain.  ``ring`` names the four staging slots, each reused once its last copy is done."""
+        ring = self._bufs.setdefault(ring, {'slots': [], 'next': 0})
+        if not ring['slots'] or ring['slots'][0][0].numel() < n:
+            ring['slots'] = [[torch.empty(max(n, 1), dtype=torch.int32, pin_memory=True), None]
+                             for _ in range(4)]
+        slot = ring['slots'][ring['next'] % 4]
+        ring['next'] += 1
+        if slot[1] is not None:
+            slot[1].synchronize()
+        yield slot[0].numpy()[:n]
+        # (a copy KERNEL reading the pinned buffer across PCIe instead of this DMA copy was measured:
+        # 487.5 k against 489.0 k pairs/s -- the ~20 us "gap before the next fit_begin_kernel" of the
+        # chunk timeline is not the copy engine's hand-off)
+        dst[:n].copy_(slot[0][:n], non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record()
+
+    def _bind_flags(self):
+        return (_lib.FIT_GRAPH if type(self).USE_GRAPH else 0) | \
+            (_lib.FIT_SPLIT_ADAM if self._dp is not None else 0)
+
+    def _bind(self, lib, flags, x_stage, ldx, y_stage, ldy, n_train, n_test, ids_ptr, train_loss, test_loss,
+              factors=None):
+        """Bind the plan to one chunk: ``n_train`` training rows of ``x_stage`` / ``y_stage`` with the
+        ``n_test`` held-out rows behind them, its ids and its log slots.  ``factors`` = (s_dim, a_dim,
+        x_held) when the rows of ``x_stage`` are cross-correlation factor rows: the held-out pairs are then
+        evaluated from the summary rows ``x_held``, or, without them, from their factor rows too."""
+        state = self._buf('state', 16, torch.int32)
+        ws = self._buf('fit_ws', int(lib.bsig_fit_workspace_bytes(self._plan)) // 4 + 1)
+        coeff, ldc, off = self._rff_args()
+        held_x = x_stage.data_ptr() + 4 * n_train * ldx
+        fb = _lib.FitBuffers()
+        fb.params, fb.grads = self._flat.data_ptr(), self._flat_grad.data_ptr()
+        fb.exp_avg, fb.exp_avg_sq = self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr()
+        fb.rff_coeff, fb.ld_coeff, fb.rff_offset = _lib.ptr(coeff), ldc, _lib.ptr(off)
+        fb.x_train, fb.ldx_train, fb.n_train = x_stage.data_ptr(), ldx, n_train
+        fb.y_train, fb.ldy_train = y_stage.data_ptr(), ldy
+        fb.x_test, fb.ldx_test, fb.n_test = held_x, ldx, n_test
+        fb.y_test, fb.ldy_test = y_stage.data_ptr() + 4 * n_train * ldy, ldy
+        fb.ids_table = ids_ptr
+        fb.train_loss, fb.test_loss = train_loss.data_ptr(), test_loss.data_ptr()
+        fb.state, fb.workspace, fb.workspace_bytes = state.data_ptr(), ws.data_ptr(), ws.numel() * 4
+        if factors is not None:
+            s_dim, a_dim, x_held = factors
+            fb.x_kind, fb.x_s, fb.x_a = _lib.X_CROSSCORR_FACTORS, s_dim, a_dim
+            if n_test > 0:      # the held-out pairs' factor rows lie behind the training rows
+                fb.x_test_factors, fb.ldx_test_factors = held_x, ldx
+                fb.x_test, fb.ldx_test = (None, 0) if x_held is None else (x_held.data_ptr(), x_held.stride(0))
+        _lib.check(lib.bsig_fit_bind(self._plan, C.byref(fb), flags))
 
     @_on_model_device
     def run_training_block(self, feats, y_data, sizes, n_updates, batch_size, test_frac=0.2):
@@ -524,8 +614,8 @@ class MDNN(nn.Module):
         runs one chunk per launch (the caller then calls run_training per chunk; nothing has been drawn
         from an RNG).  The minibatch ids and jitter seeds are drawn chunk by chunk with the calls of the
         per-chunk path, in its order."""
-        if (self._dp is not None or not self._flat.is_cuda or getattr(self, '_no_block_launch', False)
-                or getattr(self, 'rff', None) is None or len(sizes) < 1):
+        if (self._dp is not None or not self._flat.is_cuda or self._no_block_launch
+                or self.rff is None or len(sizes) < 1):
             return None
         lib = self._gpu()
         self.train()
@@ -533,90 +623,46 @@ class MDNN(nn.Module):
         dev = self._flat.device
         d, rows = self.output_dim, int(sum(sizes))
         assert feats.shape[0] == rows == y_data.shape[0] and feats.is_cuda and feats.dtype == torch.float32
-        split = [(max(int(n * (1.0 - test_frac)), 1), n - max(int(n * (1.0 - test_frac)), 1)) for n in sizes]
+        split = [split_rows(n, test_frac) for n in sizes]
         n_train, n_test = max(a for a, _ in split), max(b for _, b in split)
         self._ensure_plan(lib, cfg, batch_size, n_train, n_test, n_updates)
         st = _lib.stream()
         n_chunks, n_ids = len(sizes), len(sizes) * n_updates * batch_size
-        every = max(n_updates // 5, 1)
-        n_e = len([it for it in range(n_updates) if it % every == 0 or it + 1 == n_updates])
-        ldy = _lib.round_up(d, 4)
+        n_e = len(eval_updates(n_updates)[1])
+        ldx, ldy = _lib.round_up(self.input_dim, 4), _lib.round_up(d, 4)
         y_stage = self._buf('blk_y', rows * ldy)
         stage = self._buf('blk_stage', 16 * n_chunks + n_ids, torch.int32)       # [chunk table | ids]
         train_loss, test_loss = self._buf('blk_train_loss', n_chunks * n_updates), self._buf('blk_test_loss', n_chunks * n_e)
-        state = self._buf('state', 16, torch.int32)
-        ws = self._buf('fit_ws', int(lib.bsig_fit_workspace_bytes(self._plan)) // 4 + 1)
         # The binding is a complete one of the block's FIRST chunk (its rows, held-out rows, ids and log slots
         # are the first of the block's): whoever drives the plan through the per-call entry points afterwards
         # finds every buffer it reads in place.  The summary rows themselves are not staged, as in a
         # per-chunk call whose features are handed over.
-        ldx = _lib.round_up(self.input_dim, 4)
-        if sizes[0] > self._bufs.get('cap_rows', 0):
-            self._bufs.pop('x_stage', None), self._bufs.pop('y_stage', None)
-            self._bufs['cap_rows'] = sizes[0]
-        x_stage = self._buf('x_stage', self._bufs['cap_rows'] * ldx)
-        coeff, ldc, off = self._rff_args()
-        fb = _lib.FitBuffers()
-        fb.params, fb.grads = self._flat.data_ptr(), self._flat_grad.data_ptr()
-        fb.exp_avg, fb.exp_avg_sq = self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr()
-        fb.rff_coeff = None if coeff is None else coeff.data_ptr()
-        fb.ld_coeff = ldc
-        fb.rff_offset = None if off is None else off.data_ptr()
-        fb.x_train, fb.ldx_train, fb.n_train = x_stage.data_ptr(), ldx, split[0][0]
-        fb.y_train, fb.ldy_train = y_stage.data_ptr(), ldy
-        fb.x_test, fb.ldx_test, fb.n_test = x_stage.data_ptr() + 4 * split[0][0] * ldx, ldx, split[0][1]
-        fb.y_test, fb.ldy_test = y_stage.data_ptr() + 4 * split[0][0] * ldy, ldy
-        fb.ids_table = stage.data_ptr() + 64 * n_chunks
-        fb.train_loss, fb.test_loss = train_loss.data_ptr(), test_loss.data_ptr()
-        fb.state = state.data_ptr()
-        fb.workspace, fb.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-        flags = _lib.FIT_GRAPH if type(self).USE_GRAPH else 0
-        _lib.check(lib.bsig_fit_bind(self._plan, C.byref(fb), flags))
+        x_stage = self._buf('x_stage', self._row_capacity(sizes[0]) * ldx)
+        self._bind(lib, self._bind_flags(), x_stage, ldx, y_stage, ldy, *split[0],
+                   stage.data_ptr() + 64 * n_chunks, train_loss, test_loss)
         if n_chunks > int(lib.bsig_fit_block_chunks(self._plan, n_train)):
             return None
         ys, ldy_src = _lib.as_f32_rows(y_data, dev)
         assert ys.shape[1] == d
-        if self.output_lows is not None:                       # mdnn.py:204-205, once over the block's rows
-            _lib.check(lib.bsig_normalize_rows(
-                _lib.ptr(ys), ldy_src, _lib.ptr(self.output_lows),
-                _lib.ptr(self.output_highs), _lib.ptr(y_stage), ldy, rows, d, st))
-        else:
-            _lib.check(lib.bsig_copy_rows(_lib.ptr(ys), ldy_src, None, _lib.ptr(y_stage), ldy, rows, d, st))
+        self._stage_targets(lib, ys, ldy_src, y_stage, ldy, rows, st)        # once over the block's rows
         # ids (mdnn.py:219-222) and seeds: one numpy draw and one torch draw per chunk, as the per-chunk calls
-        ring = self._bufs.setdefault('blk_ring', {'slots': [], 'next': 0})
-        if not ring['slots'] or ring['slots'][0][0].numel() < 16 * n_chunks + n_ids:
-            ring['slots'] = [[torch.empty(16 * n_chunks + n_ids, dtype=torch.int32, pin_memory=True), None]
-                             for _ in range(4)]
-        slot = ring['slots'][ring['next'] % 4]
-        ring['next'] += 1
-        if slot[1] is not None:
-            slot[1].synchronize()
-        host = slot[0].numpy()
         seeds = []
-        for c, (n_tr, _) in enumerate(split):
-            lo = 16 * n_chunks + c * n_updates * batch_size
-            host[lo:lo + n_updates * batch_size] = np.random.randint(
-                0, n_tr, (n_updates, batch_size), dtype=np.int32).reshape(-1) + np.int32(sum(sizes[:c]))
-            seeds.append(self._seed())
-        table = _lib.fit_chunk_table(sizes, seeds, n_updates, batch_size, test_frac)
-        host[:16 * n_chunks] = table.view(np.int32)
-        stage[:16 * n_chunks + n_ids].copy_(slot[0][:16 * n_chunks + n_ids], non_blocking=True)
-        slot[1] = torch.cuda.Event()
-        slot[1].record()
+        with self._pinned_upload('blk_ring', stage, 16 * n_chunks + n_ids) as host:
+            for c, (n_tr, _) in enumerate(split):
+                lo = 16 * n_chunks + c * n_updates * batch_size
+                host[lo:lo + n_updates * batch_size] = np.random.randint(
+                    0, n_tr, (n_updates, batch_size), dtype=np.int32).reshape(-1) + np.int32(sum(sizes[:c]))
+                seeds.append(self._seed())
+            table = _lib.fit_chunk_table(sizes, seeds, n_updates, batch_size, test_frac)
+            host[:16 * n_chunks] = table.view(np.int32)
         packed = torch.empty(n_chunks, 2 * n_e + 1, dtype=torch.float32, device=dev)
         _lib.check(lib.bsig_fit_run_block(
             self._plan, _lib.ptr(feats), feats.stride(0), rows, _lib.ptr(y_stage), ldy,
             C.c_void_p(stage.data_ptr() + 64 * n_chunks), n_ids, C.c_void_p(table.ctypes.data),
             _lib.ptr(stage), n_chunks, _lib.ptr(train_loss), _lib.ptr(test_loss), _lib.ptr(packed),
             batch_size, st))
-        self._block_launches = getattr(self, '_block_launches', 0) + 1
+        self._block_launches += 1
         return [PendingLogs(packed[c], n_e, split[c][1], type(self).VERBOSE) for c in range(n_chunks)]
-
-    def _may_time_out(self):
-        """Could the next call run a persistent kernel?  (Unknown before the first plan exists.)"""
-        if getattr(self, '_no_persistent', False) or os.environ.get('BSIG_NO_PERSISTENT') == '1':
-            return False
-        return self._plan is None or bool(_lib.load().bsig_fit_is_persistent(self._plan))
 
     @_on_model_device
     def _run_training_once(self, x_data, y_data, n_updates, batch_size, test_frac=0.2,
@@ -627,57 +673,47 @@ class MDNN(nn.Module):
         cfg = self._cfg()
         dev = self._flat.device
         d, n_tot = self.output_dim, x_data.shape[0]
-        n_train = max(int(n_tot * (1.0 - test_frac)), 1)
-        n_test = n_tot - n_train
+        n_train, n_test = split_rows(n_tot, test_frac)
         st = _lib.stream()
         self._ensure_plan(lib, cfg, batch_size, n_train, n_test, n_updates)
+        flags = self._bind_flags()
         # a cross-correlation summary may arrive as factor rows (summarizers.CrossCorrFactors):
         # plans whose first layer lives in the persistent kernel consume them as they are
-        factored = isinstance(x_data, CrossCorrFactors)
-        if factored and not lib.bsig_fit_accepts_factor_rows(self._plan, x_data.s_dim, x_data.a_dim):
-            x_data, factored = x_data.materialize(), False
+        factors = None
+        if isinstance(x_data, CrossCorrFactors) and \
+                not lib.bsig_fit_accepts_factor_rows(self._plan, x_data.s_dim, x_data.a_dim):
+            x_data = x_data.materialize()
         ldy = _lib.round_up(d, 4)
         ys, ldy_src = _lib.as_f32_rows(y_data, dev)
         assert x_data.shape[1] == self.input_dim and ys.shape[1] == d
-        cap = self._bufs.get('cap_rows', 0)
-        if n_tot > cap:
-            self._bufs.pop('x_stage', None), self._bufs.pop('y_stage', None)
-            self._bufs['cap_rows'] = n_tot
-        if factored:
+        cap_rows = self._row_capacity(n_tot)
+        if isinstance(x_data, CrossCorrFactors):
             # bound where they lie: 1.3 KB per Ant row instead of a 47 KB summary row
             x_stage, _ = _lib.as_f32_rows(x_data.factors, dev)
             ldx = x_stage.stride(0) if n_tot > 1 else x_stage.shape[1]
             # the held-out rows, read once per evaluation, as summary rows -- unless the launch
             # evaluates from the held-out pairs' factor rows too (a streamed first layer): then no
             # [n, I] block exists at all
-            bind_flags = (_lib.FIT_GRAPH if type(self).USE_GRAPH else 0) | \
-                (_lib.FIT_SPLIT_ADAM if self._dp is not None else 0)
-            eval_fac = bool(lib.bsig_fit_evaluates_from_factors(self._plan, x_data.s_dim, x_data.a_dim, bind_flags))
+            eval_fac = bool(lib.bsig_fit_evaluates_from_factors(self._plan, x_data.s_dim, x_data.a_dim, flags))
             x_held = x_data[n_train:].materialize() if n_test > 0 and not eval_fac else None
             self._bufs['x_keepalive'] = (x_stage, x_held)
+            factors = (x_data.s_dim, x_data.a_dim, x_held)
         else:
             # chunk staging: fixed addresses (graph replay) and 16-B aligned rows
             xs, ldx_src = _lib.as_f32_rows(x_data, dev)
             ldx = _lib.round_up(self.input_dim, 4)
-            x_stage = self._buf('x_stage', self._bufs['cap_rows'] * ldx)
+            x_stage = self._buf('x_stage', cap_rows * ldx)
             # (an MDRFF whose rows' features are handed over never reads the summaries themselves)
             if _feats is None or not lib.bsig_fit_takes_features(self._plan, n_train):
                 _lib.check(lib.bsig_copy_rows(_lib.ptr(xs), ldx_src, None, _lib.ptr(x_stage), ldx,
                                               n_tot, self.input_dim, st))
-        y_stage = self._buf('y_stage', self._bufs['cap_rows'] * ldy)
-        if self.output_lows is not None:                       # mdnn.py:204-205
-            _lib.check(lib.bsig_normalize_rows(
-                _lib.ptr(ys), ldy_src, _lib.ptr(self.output_lows),
-                _lib.ptr(self.output_highs), _lib.ptr(y_stage), ldy, n_tot, d, st))
-        else:
-            _lib.check(lib.bsig_copy_rows(_lib.ptr(ys), ldy_src, None, _lib.ptr(y_stage),
-                                          ldy, n_tot, d, st))
+        y_stage = self._buf('y_stage', cap_rows * ldy)
+        self._stage_targets(lib, ys, ldy_src, y_stage, ldy, n_tot, st)
         n_ids = n_updates * batch_size
         ids_dev = self._buf('ids', max(n_ids, 1), torch.int32)
+
         def upload_ids():
-            """Minibatch ids in the reference's numpy-RNG order (mdnn.py:219-222), drawn on the host
-            and uploaded through a pinned staging ring (a pageable source would make the copy wait
-            for the stream to drain)."""
+            """Minibatch ids in the reference's numpy-RNG order (mdnn.py:219-222), drawn on the host."""
             if ids_table is None:
                 # (dtype=int32: the SAME draws from the same stream as the reference's int64 default --
                 # tests/test_ids_draw.py -- in half the host time and without the astype pass: at 122 x
@@ -686,23 +722,8 @@ class MDNN(nn.Module):
             else:
                 ids_np = np.asarray(ids_table)
                 assert ids_np.shape == (n_updates, batch_size)
-            # truly asynchronous upload: pinned staging ring (a pageable source would
-            # make the copy wait for the stream to drain)
-            ring = self._bufs.setdefault('ids_ring', {'slots': [], 'next': 0})
-            if not ring['slots'] or ring['slots'][0][0].numel() < n_ids:
-                ring['slots'] = [[torch.empty(max(n_ids, 1), dtype=torch.int32, pin_memory=True), None]
-                                 for _ in range(4)]
-            slot = ring['slots'][ring['next'] % 4]
-            ring['next'] += 1
-            if slot[1] is not None:
-                slot[1].synchronize()
-            slot[0][:n_ids].copy_(torch.from_numpy(np.ascontiguousarray(ids_np, dtype=np.int32)).reshape(-1))
-            # (a copy KERNEL reading the pinned buffer across PCIe instead of this DMA copy was measured in
-            # round 5: 487.5 k against 489.0 k pairs/s -- the ~20 us "gap before the next fit_begin_kernel"
-            # of the chunk timeline is not the copy engine's hand-off)
-            ids_dev[:n_ids].copy_(slot[0][:n_ids], non_blocking=True)
-            slot[1] = torch.cuda.Event()
-            slot[1].record()
+            with self._pinned_upload('ids_ring', ids_dev, n_ids) as host:
+                host[:] = ids_np.reshape(-1)
 
         # A large table (the scaled-batch fit: 122 x 8192 ids, 8 ms of numpy) is drawn AFTER the
         # begin call has been enqueued, so that begin's device work -- the RFF projection of the
@@ -712,40 +733,11 @@ class MDNN(nn.Module):
                                            bool(lib.bsig_fit_takes_features(self._plan, n_train)))
         if not late_ids:
             upload_ids()
-        every = max(n_updates // 5, 1)
-        eval_its = [it for it in range(n_updates)
-                    if it % every == 0 or it + 1 == n_updates]
+        eval_its = eval_updates(n_updates)[1]
         train_loss = self._buf('train_loss', n_updates)
         test_loss = self._buf('test_loss', len(eval_its))
-        state = self._buf('state', 16, torch.int32)
-        ws = self._buf('fit_ws', int(lib.bsig_fit_workspace_bytes(self._plan)) // 4 + 1)
-        coeff, ldc, off = self._rff_args()
-        fb = _lib.FitBuffers()
-        fb.params, fb.grads = self._flat.data_ptr(), self._flat_grad.data_ptr()
-        fb.exp_avg, fb.exp_avg_sq = self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr()
-        fb.rff_coeff = None if coeff is None else coeff.data_ptr()
-        fb.ld_coeff = ldc
-        fb.rff_offset = None if off is None else off.data_ptr()
-        fb.x_train, fb.ldx_train, fb.n_train = x_stage.data_ptr(), ldx, n_train
-        fb.y_train, fb.ldy_train = y_stage.data_ptr(), ldy
-        fb.x_test, fb.ldx_test, fb.n_test = x_stage.data_ptr() + 4 * n_train * ldx, ldx, n_test
-        if factored and n_test > 0:
-            if x_held is not None:
-                fb.x_test, fb.ldx_test = x_held.data_ptr(), x_held.stride(0)
-            else:
-                fb.x_test, fb.ldx_test = None, 0
-        fb.y_test, fb.ldy_test = y_stage.data_ptr() + 4 * n_train * ldy, ldy
-        fb.ids_table = ids_dev.data_ptr()
-        fb.train_loss, fb.test_loss = train_loss.data_ptr(), test_loss.data_ptr()
-        fb.state = state.data_ptr()
-        fb.workspace, fb.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-        if factored:
-            fb.x_kind, fb.x_s, fb.x_a = _lib.X_CROSSCORR_FACTORS, x_data.s_dim, x_data.a_dim
-            if n_test > 0:      # the held-out pairs' factor rows lie behind the training rows
-                fb.x_test_factors, fb.ldx_test_factors = x_stage.data_ptr() + 4 * n_train * ldx, ldx
-        flags = (_lib.FIT_GRAPH if type(self).USE_GRAPH else 0) | \
-            (_lib.FIT_SPLIT_ADAM if self._dp is not None else 0)
-        _lib.check(lib.bsig_fit_bind(self._plan, C.byref(fb), flags))
+        self._bind(lib, flags, x_stage, ldx, y_stage, ldy, n_train, n_test, ids_dev.data_ptr(),
+                   train_loss, test_loss, factors)
         if _feats is not None:
             # MDRFF: the rows' RFF features, already projected by the caller (BayesSim.fit)
             assert _feats.shape[0] == n_tot and _feats.is_cuda and _feats.dtype == torch.float32
