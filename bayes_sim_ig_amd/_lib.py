@@ -1,4 +1,4 @@
-"""ctypes binding of libbsig_hip.so (include/bsig.h).
+"""ctypes binding of libbsig_hip.so (include/bsig.h, include/bsig_f64.h).
 
 The product path has NO fallback: if the library is missing or there is no
 GPU, every compute entry point raises.  torch is used only for device memory,
@@ -26,6 +26,7 @@ X_ROWS, X_CROSSCORR_FACTORS = 0, 1
 
 i64, i32, u64, f32, vp, sz = (C.c_int64, C.c_int32, C.c_uint64, C.c_float,
                               C.c_void_p, C.c_size_t)
+f64 = C.c_double
 
 
 class HeadDims(C.Structure):
@@ -53,6 +54,25 @@ class FitBuffers(C.Structure):
                 ('state', vp), ('workspace', vp), ('workspace_bytes', sz),
                 ('x_kind', i32), ('x_s', i32), ('x_a', i32),
                 ('x_test_factors', vp), ('ldx_test_factors', i64)]
+
+
+class F64Hyper(C.Structure):
+    """bsig_f64_hyper (include/bsig_f64.h): the hyper-parameters as doubles"""
+    _fields_ = [('lr', f64), ('beta1', f64), ('beta2', f64), ('adam_eps', f64),
+                ('eps_noise', f64), ('min_weight', f64), ('ll_limit', f64), ('rff_scale', f64)]
+
+
+class Fit64Buffers(C.Structure):
+    """bsig_fit64_buffers (include/bsig_f64.h)"""
+    _fields_ = [('params', vp), ('grads', vp), ('exp_avg', vp), ('exp_avg_sq', vp),
+                ('rff_coeff', vp), ('ld_coeff', i64), ('rff_offset', vp),
+                ('x_train', vp), ('ldx_train', i64), ('n_train', i64),
+                ('y_train', vp), ('ldy_train', i64),
+                ('x_test', vp), ('ldx_test', i64), ('n_test', i64),
+                ('y_test', vp), ('ldy_test', i64),
+                ('ids_table', vp), ('train_loss', vp), ('test_loss', vp),
+                ('state', vp), ('workspace', vp), ('workspace_bytes', sz),
+                ('x_kind', i32)]
 
 
 # bsig_fit_chunk (include/bsig.h): one entry per chunk of a block launch, 64 bytes
@@ -164,6 +184,34 @@ _PROTOS = {
     'bsig_debug_block_launch': (C.c_int, [C.c_int, C.c_int, C.c_int]),
     'bsig_fit_run_dp': (C.c_int, [vp, vp, i64, vp, vp]),
 }
+# include/bsig_f64.h: the fp64 mode
+_HD, _HY, _CFG = C.POINTER(HeadDims), C.POINTER(F64Hyper), C.POINTER(MdnCfg)
+_PROTOS_F64 = {
+    'bsig_gemm_f64': (C.c_int, [vp, i64, C.c_int, vp, vp, i64, C.c_int, vp, vp, i64, i64, i64, i64,
+                                C.c_int, C.c_int, vp, vp, i64, f64, vp]),
+    'bsig_rff_project_f64': (C.c_int, [vp, i64, vp, vp, i64, vp, vp, i64, i64, i64, i64, f64, C.c_int, vp]),
+    'bsig_head_workspace_bytes_f64': (sz, [_HD, i64]),
+    'bsig_mdn_head_outputs_f64': (C.c_int, [_HD, _HY, vp, i64, i64, vp, u64, u64, vp, vp, vp, vp, vp,
+                                            vp, sz, vp]),
+    'bsig_mdn_nll_from_tuple_f64': (C.c_int, [_HD, _HY, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, sz, vp]),
+    'bsig_mdn_head_nll_f64': (C.c_int, [_HD, _HY, vp, i64, vp, i64, vp, i64, i64, vp, u64, u64, vp, vp,
+                                        vp, vp, sz, vp]),
+    'bsig_adam_flat_f64': (C.c_int, [vp, vp, vp, vp, i64, f64, f64, f64, f64, i64, vp]),
+    'bsig_normalize_rows_f64': (C.c_int, [vp, i64, vp, vp, vp, i64, i64, i64, vp]),
+    'bsig_copy_rows_f64': (C.c_int, [vp, i64, vp, vp, i64, i64, i64, vp]),
+    'bsig_mdn_workspace_bytes_f64': (sz, [_CFG, i64]),
+    'bsig_mdn_head_forward_f64': (C.c_int, [_CFG, _HY, vp, vp, i64, vp, vp, i64, vp, i64, vp, i64, vp,
+                                            sz, vp]),
+    'bsig_mdn_loss_grad_f64': (C.c_int, [_CFG, _HY, vp, vp, i64, vp, vp, i64, vp, i64, vp, i64, i64, vp,
+                                         u64, u64, vp, vp, vp, vp, sz, vp]),
+    'bsig_fit64_create': (C.c_int, [_CFG, _HY, i64, i64, i64, i64, C.POINTER(vp)]),
+    'bsig_fit64_destroy': (None, [vp]),
+    'bsig_fit64_workspace_bytes': (sz, [vp]),
+    'bsig_fit64_bind': (C.c_int, [vp, C.POINTER(Fit64Buffers), C.c_int]),
+    'bsig_fit64_begin': (C.c_int, [vp, u64, i64, vp]),
+    'bsig_fit64_run': (C.c_int, [vp, i64, vp]),
+    'bsig_fit64_pack_logs': (C.c_int, [vp, i64, i64, vp, vp]),
+}
 COMM_ID_BYTES = 128
 EXCHANGE_SUM, EXCHANGE_BROADCAST = 0, 1
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int, vp, i64, C.c_int, vp)
@@ -176,6 +224,11 @@ def exported_symbols():
     return sorted(_PROTOS)
 
 
+def exported_symbols_f64():
+    """Names every declaration of include/bsig_f64.h must resolve to."""
+    return sorted(_PROTOS_F64)
+
+
 def load():
     """Load the shared library (no GPU needed for loading)."""
     global _lib
@@ -185,7 +238,7 @@ def load():
                 'libbsig_hip.so not built (%s): run ./build.sh or '
                 '__graft_entry__.build(); there is no CPU fallback' % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in _PROTOS.items():
+        for name, (res, args) in list(_PROTOS.items()) + list(_PROTOS_F64.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _check_abi(lib)
@@ -269,6 +322,24 @@ def as_f32_rows(t, device=None):
         t = t.to(device)
     if not t.is_cuda:
         raise RuntimeError('expected a GPU tensor (no CPU fallback)')
+    if t.dim() != 2:
+        raise AssertionError('expected a 2-D tensor')
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    ld = t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
+    return t, ld
+
+
+def as_f64_rows(t, device=None):
+    """as_f32_rows for the fp64 mode: fp32 (or any other) input is widened on the device."""
+    if hasattr(t, 'materialize'):
+        t = t.materialize()
+    if device is not None and t.device != torch.device(device):
+        t = t.to(device)
+    if not t.is_cuda:
+        raise RuntimeError('expected a GPU tensor (no CPU fallback)')
+    if t.dtype != torch.float64:
+        t = t.double()
     if t.dim() != 2:
         raise AssertionError('expected a 2-D tensor')
     if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):

@@ -47,7 +47,9 @@ class BayesSim(object):
                  params_highs, prior, proposal=None, device='cpu'):
         """Arguments as in the reference (bayes_sim.py:27-52).  Optional
         ``model_cfg`` keys beyond the reference's: ``nFeat`` (RFF features,
-        default 200 as hard-coded at bayes_sim.py:81), ``sigDepth``."""
+        default 200 as hard-coded at bayes_sim.py:81), ``sigDepth``, ``dtype``
+        ('float32', the default, or 'float64': the estimator's fp64 mode, as
+        ``bs.model.double()``)."""
         self.prior = prior
         self.proposal = proposal
         model_class = model_cfg['modelClass']
@@ -82,7 +84,12 @@ class BayesSim(object):
                            'sigma': sigma, 'kernel': kernel})
         if model_class not in _MODELS:
             raise NameError("name '%s' is not defined" % model_class)
+        dtype = model_cfg.get('dtype', 'float32')
+        if dtype not in ('float32', 'float64'):
+            raise ValueError("model_cfg['dtype'] must be 'float32' or 'float64', got %r" % (dtype,))
         self.model = _MODELS[model_class](**kwargs)
+        if dtype == 'float64':
+            self.model.double()
 
     @staticmethod
     def get_n_trajs_per_batch(n_train_trajs, n_train_trajs_done):
@@ -107,7 +114,8 @@ class BayesSim(object):
         return self.summarizer_fxn(states, actions)
 
     def _lazy_summaries(self):
-        return (self.model.rff is None and self.model._flat.is_cuda and
+        # (a double model takes summary rows only: materialised in fp32 by the summarizer kernels, widened)
+        return (self.model.rff is None and self.model._flat.is_cuda and not self.model._f64 and
                 os.environ.get('BSIG_NO_FUSED_SUMMARY') != '1')
 
     def run_training(self, params, traj_states, traj_actions, _defer=False, _finite_flag=None,
@@ -177,7 +185,8 @@ class BayesSim(object):
             if block and done >= hi:
                 lo, hi = done, min(n, done + block)
                 summ = self._summarize(traj_states[lo:hi], traj_actions[lo:hi], flag, lazy=True)
-                feats = model.rff.to_features(summ) if model.rff is not None else None
+                # (a double MDRFF projects in double inside each call: chunk by chunk, no block launch)
+                feats = model.rff.to_features(summ) if model.rff is not None and not model._f64 else None
                 sizes = self._block_launch_sizes(n, lo, hi) if feats is not None and model._dp is None else []
                 rows = sum(sizes)
                 logs = model.run_training_block(
@@ -233,12 +242,14 @@ class BayesSim(object):
                      output_highs=src.output_highs.detach().cpu().numpy(),
                      n_gaussians=src.n_gaussians, hidden_layers=(128, 128), lr=src.lr,
                      activation=src.activation, full_covariance=src.L_size > 0, device=src.device)
+        if src._f64:
+            refit.double()
         share = int(BayesSim.REFIT_SAMPLES / len(mixtures))
         draws = torch.from_numpy(np.concatenate([m.gen(n_samples=share) for m in mixtures], axis=0))
-        draws = draws.float().to(src.device)
+        draws = draws.to(src._dtype).to(src.device)
         if MDNN.VERBOSE:
             print(f'Fitting posterior from {len(mixtures):d} mogs')
-        const_in = torch.zeros(draws.shape[0], 1, device=draws.device)
+        const_in = torch.zeros(draws.shape[0], 1, dtype=src._dtype, device=draws.device)
         refit.run_training(const_in, draws,
                            BayesSim.REFIT_EPOCHS * BayesSim.REFIT_SAMPLES // BayesSim.REFIT_MINIBATCH,
                            BayesSim.REFIT_MINIBATCH)

@@ -8,6 +8,10 @@ fp32 device buffer (the named ``nn.Parameter``s are views into it, so
 are fp32-MFMA GEMMs, the mixture head + NLL + backward is one fused kernel,
 Adam runs over the flat buffer, and ``run_training`` replays the whole update
 from a HIP graph (csrc/estimator.hip).  There is no CPU fallback.
+
+``model.double()`` switches the model to the fp64 mode (include/bsig_f64.h, csrc/f64/): the flat
+buffers become float64 and every entry point below runs the per-phase fp64 kernels -- the
+reference under ``torch.set_default_dtype(torch.float64)``; ``model.float()`` goes back.
 """
 import contextlib
 import ctypes as C
@@ -117,6 +121,8 @@ class MDNN(nn.Module):
     USE_GRAPH = True     # replay the update from a HIP graph
     PAD_TRUNK_TO = 128   # hidden width the persistent update kernel is built for
     rff = None           # the feature map of an MDRFF
+    _dtype = torch.float32   # torch.float64 after .double(): the fp64 mode
+    _plan64 = False      # the plan is a bsig_fit64 one
     _plan = None         # (a model whose construction failed is still finalised: __del__)
 
     def __init__(self, input_dim, output_dim, output_lows, output_highs,
@@ -206,18 +212,24 @@ class MDNN(nn.Module):
             mods.append(self.Lower)
         return mods
 
-    def _flatten(self, device):
-        """Move every parameter into one flat fp32 buffer (layout:
-        bsig_mdn_param_offsets) and re-point the nn.Parameters at views."""
+    def _flatten(self, device, dtype=None):
+        """Move every parameter into one flat buffer of the model's dtype (fp32, or fp64 after
+        .double(); layout: bsig_mdn_param_offsets) and re-point the nn.Parameters at views.  A
+        change of dtype carries the gradients and both Adam moments over; the values are widened,
+        or rounded to fp32 (exact for values an fp32 holds)."""
         lib = _lib.load()
+        dtype = dtype or self._dtype
+        carried = [getattr(self, n, None) for n in ('_flat_grad', '_exp_avg', '_exp_avg_sq')] \
+            if dtype != self._dtype else [None] * 3
+        self._dtype = dtype
         cfg = self._cfg()
         total = int(lib.bsig_mdn_param_count(C.byref(cfg)))
         assert total > 0, lib.bsig_last_error().decode()
         n_off = 2 * (len(self._hidden) + 4)
         offs = (C.c_int64 * n_off)()
         _lib.check(lib.bsig_mdn_param_offsets(C.byref(cfg), offs, n_off))
-        flat = torch.zeros(total, dtype=torch.float32, device=device)
-        grads = torch.zeros(total, dtype=torch.float32, device=device)
+        flat = torch.zeros(total, dtype=dtype, device=device)
+        grads = torch.zeros(total, dtype=dtype, device=device)
         self._param_slices = []
         # stored input width of every Linear: the (possibly padded) width of the layer below
         widths = [self.input_dim if self._rff_feats == 0 else self._rff_feats] + self._hidden_stored
@@ -232,30 +244,57 @@ class MDNN(nn.Module):
                     sub = tuple(slice(0, d) for d in real)
                     self._param_slices.append((o, full, real))
                     view = flat[o:o + int(np.prod(full))].view(full)[sub]
-                    view.copy_(prm.detach().to(dtype=torch.float32))
+                    view.copy_(prm.detach().to(dtype=dtype))
                     prm.data = view
                     prm.grad = grads[o:o + int(np.prod(full))].view(full)[sub]
         self._flat, self._flat_grad = flat, grads
         self._exp_avg = torch.zeros_like(flat)
         self._exp_avg_sq = torch.zeros_like(flat)
+        for new, old in zip((grads, self._exp_avg, self._exp_avg_sq), carried):
+            if old is not None and old.numel() == total:
+                new.copy_(old.to(device=flat.device, dtype=dtype))
         if self.output_lows is not None:
-            self.output_lows = self.output_lows.to(device)
-            self.output_highs = self.output_highs.to(device)
+            self.output_lows = self.output_lows.to(device=device, dtype=dtype)
+            self.output_highs = self.output_highs.to(device=device, dtype=dtype)
         self.device = str(device) if not isinstance(device, str) else device
         self._drop_plan()
 
     def _apply(self, fn, *args, **kwargs):
+        if self._dp is not None:
+            # refuse BEFORE converting: the model stays as it was
+            if fn(torch.empty(0, dtype=self._dtype)).dtype == torch.float64:
+                self._f64_dp_error()
         super()._apply(fn, *args, **kwargs)
         prm = next(self.parameters())
-        if prm.dtype != torch.float32:
-            raise NotImplementedError('the HIP estimator computes in fp32 only')
-        self._flatten(prm.device)
+        if prm.dtype not in (torch.float32, torch.float64):
+            raise NotImplementedError('the HIP estimator computes in fp32 or fp64 only')
+        self._flatten(prm.device, prm.dtype)
         return self
+
+    @property
+    def _f64(self):
+        return self._dtype == torch.float64
+
+    @staticmethod
+    def _f64_dp_error():
+        raise NotImplementedError('a double MDNN cannot be data-parallel: the fp64 mode has no gradient '
+                                  'exchange (include/bsig_f64.h); use .float() or a single rank')
+
+    def _check_f64_dp(self):
+        if self._f64 and self._dp is not None:
+            self._f64_dp_error()
+
+    def _hyper(self):
+        """The hyper-parameters as the Python floats (doubles) the reference computes with in fp64 mode."""
+        cls = type(self)
+        return _lib.F64Hyper(float(self.lr), 0.9, 0.999, 1e-8, float(cls.EPS_NOISE), float(cls.MIN_WEIGHT),
+                             float(cls.LL_LIMIT), float(self._rff_scale))
 
     def _drop_plan(self):
         if self._plan:
-            _lib.load().bsig_fit_destroy(self._plan)
-        self._plan, self._plan_key = None, None
+            lib = _lib.load()
+            (lib.bsig_fit64_destroy if self._plan64 else lib.bsig_fit_destroy)(self._plan)
+        self._plan, self._plan_key, self._plan64 = None, None, False
         self._bufs = {}
 
     def __del__(self):
@@ -279,6 +318,8 @@ class MDNN(nn.Module):
     def _may_time_out(self):
         """Could the next call run a persistent kernel?  (Unknown before the first plan exists.)"""
         if not self._flat.is_cuda or self._no_persistent or os.environ.get('BSIG_NO_PERSISTENT') == '1':
+            return False
+        if self._f64:        # the fp64 mode is per-phase launches only
             return False
         return self._plan is None or bool(_lib.load().bsig_fit_is_persistent(self._plan))
 
@@ -360,6 +401,19 @@ class MDNN(nn.Module):
     def _head_forward(self, x):
         lib = self._gpu()
         cfg = self._cfg()
+        if self._f64:
+            xs, ldx = _lib.as_f64_rows(x, self._flat.device)
+            assert xs.shape[1] == self.input_dim
+            b = xs.shape[0]
+            nh = int(lib.bsig_head_width(C.byref(cfg.head)))
+            out = torch.empty((b, nh), dtype=torch.float64, device=xs.device)
+            ws = self._buf('fwd_ws', int(lib.bsig_mdn_workspace_bytes_f64(C.byref(cfg), b)) // 8 + 1, torch.float64)
+            coeff, ldc, off = self._rff_args()
+            _lib.check(lib.bsig_mdn_head_forward_f64(
+                C.byref(cfg), C.byref(self._hyper()), _lib.ptr(self._flat), _lib.ptr(coeff), ldc,
+                _lib.ptr(off), _lib.ptr(xs), ldx, None, b, _lib.ptr(out), nh, _lib.ptr(ws),
+                ws.numel() * 8, _lib.stream()))
+            return cfg, out
         xs, ldx = _lib.as_f32_rows(x, self._flat.device)
         assert xs.shape[1] == self.input_dim
         b = xs.shape[0]
@@ -381,21 +435,29 @@ class MDNN(nn.Module):
         lib = self._gpu()
         cfg, out = self._head_forward(x)
         b, d, k = out.shape[0], self.output_dim, self.n_gaussians
-        dev = out.device
-        weights = torch.empty((b, k), dtype=torch.float32, device=dev)
-        mu = torch.empty((b, d, k), dtype=torch.float32, device=dev)
-        l_d = torch.empty((b, d, k), dtype=torch.float32, device=dev)
+        dev, dt = out.device, self._dtype
+        weights = torch.empty((b, k), dtype=dt, device=dev)
+        mu = torch.empty((b, d, k), dtype=dt, device=dev)
+        l_d = torch.empty((b, d, k), dtype=dt, device=dev)
         low = None
         if self.Lower is not None:
-            low = torch.empty((b, self.L_size, k), dtype=torch.float32, device=dev)
+            low = torch.empty((b, self.L_size, k), dtype=dt, device=dev)
         flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        ws = self._buf('head_ws', 64 + int(lib.bsig_head_workspace_bytes(C.byref(cfg.head), b)) // 4)
-        nz = None if noise is None else noise.to(dev, torch.float32).contiguous()
+        nz = None if noise is None else noise.to(dev, dt).contiguous()
         seed = self._seed()
-        _lib.check(lib.bsig_mdn_head_outputs(
-            C.byref(cfg.head), _lib.ptr(out), out.stride(0), b, _lib.ptr(nz),
-            seed, 0, _lib.ptr(weights), _lib.ptr(mu), _lib.ptr(l_d),
-            _lib.ptr(low), _lib.ptr(flag), _lib.ptr(ws), ws.numel() * 4, _lib.stream()))
+        if self._f64:
+            ws = self._buf('head_ws', 64 + int(lib.bsig_head_workspace_bytes_f64(C.byref(cfg.head), b)) // 8,
+                           torch.float64)
+            _lib.check(lib.bsig_mdn_head_outputs_f64(
+                C.byref(cfg.head), C.byref(self._hyper()), _lib.ptr(out), out.stride(0), b, _lib.ptr(nz),
+                seed, 0, _lib.ptr(weights), _lib.ptr(mu), _lib.ptr(l_d),
+                _lib.ptr(low), _lib.ptr(flag), _lib.ptr(ws), ws.numel() * 8, _lib.stream()))
+        else:
+            ws = self._buf('head_ws', 64 + int(lib.bsig_head_workspace_bytes(C.byref(cfg.head), b)) // 4)
+            _lib.check(lib.bsig_mdn_head_outputs(
+                C.byref(cfg.head), _lib.ptr(out), out.stride(0), b, _lib.ptr(nz),
+                seed, 0, _lib.ptr(weights), _lib.ptr(mu), _lib.ptr(l_d),
+                _lib.ptr(low), _lib.ptr(flag), _lib.ptr(ws), ws.numel() * 4, _lib.stream()))
         assert int(flag.item()) == 0      # isfinite asserts, mdnn.py:120-124
         # remembered so that mdn_loss_fn(*model(x), y).backward() works (below)
         self._fwd_ctx = (weights, x, nz, seed) if torch.is_grad_enabled() else None
@@ -408,20 +470,29 @@ class MDNN(nn.Module):
         cfg = self._cfg()
         dev = self._flat.device
         b = y.size()[0]
-        ys, ldy = _lib.as_f32_rows(y, dev)
-        w = weights.to(dev, torch.float32).contiguous()
-        m = mu.to(dev, torch.float32).contiguous()
-        s = L_d.to(dev, torch.float32).contiguous()
-        lo = None if L is None else L.to(dev, torch.float32).contiguous()
+        dt = self._dtype
+        ys, ldy = (_lib.as_f64_rows if self._f64 else _lib.as_f32_rows)(y, dev)
+        w = weights.to(dev, dt).contiguous()
+        m = mu.to(dev, dt).contiguous()
+        s = L_d.to(dev, dt).contiguous()
+        lo = None if L is None else L.to(dev, dt).contiguous()
         head = cfg.head
         head.full_cov = 0 if lo is None else 1
-        loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        loss = torch.zeros(1, dtype=dt, device=dev)
         flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        ws = self._buf('head_ws', 64 + int(lib.bsig_head_workspace_bytes(C.byref(head), b)) // 4)
-        _lib.check(lib.bsig_mdn_nll_from_tuple(
-            C.byref(head), _lib.ptr(w), _lib.ptr(m), _lib.ptr(s), _lib.ptr(lo),
-            _lib.ptr(ys), ldy, b, _lib.ptr(loss), _lib.ptr(flag), _lib.ptr(ws),
-            ws.numel() * 4, _lib.stream()))
+        if self._f64:
+            ws = self._buf('head_ws', 64 + int(lib.bsig_head_workspace_bytes_f64(C.byref(head), b)) // 8,
+                           torch.float64)
+            _lib.check(lib.bsig_mdn_nll_from_tuple_f64(
+                C.byref(head), C.byref(self._hyper()), _lib.ptr(w), _lib.ptr(m), _lib.ptr(s), _lib.ptr(lo),
+                _lib.ptr(ys), ldy, b, _lib.ptr(loss), _lib.ptr(flag), _lib.ptr(ws),
+                ws.numel() * 8, _lib.stream()))
+        else:
+            ws = self._buf('head_ws', 64 + int(lib.bsig_head_workspace_bytes(C.byref(head), b)) // 4)
+            _lib.check(lib.bsig_mdn_nll_from_tuple(
+                C.byref(head), _lib.ptr(w), _lib.ptr(m), _lib.ptr(s), _lib.ptr(lo),
+                _lib.ptr(ys), ldy, b, _lib.ptr(loss), _lib.ptr(flag), _lib.ptr(ws),
+                ws.numel() * 4, _lib.stream()))
         assert int(flag.item()) == 0      # mdnn.py:172-174
         ctx = getattr(self, '_fwd_ctx', None)
         if torch.is_grad_enabled() and ctx is not None and ctx[0] is weights:
@@ -440,19 +511,30 @@ class MDNN(nn.Module):
         lib = self._gpu()
         cfg = self._cfg()
         dev = self._flat.device
-        xs, ldx = _lib.as_f32_rows(x, dev)
-        ys, ldy = _lib.as_f32_rows(y, dev)
+        as_rows = _lib.as_f64_rows if self._f64 else _lib.as_f32_rows
+        xs, ldx = as_rows(x, dev)
+        ys, ldy = as_rows(y, dev)
         ridx = None
         b = xs.shape[0]
         if rows is not None:
             ridx = torch.as_tensor(rows, dtype=torch.int32, device=dev).contiguous()
             b = ridx.numel()
+        loss = torch.zeros(1, dtype=self._dtype, device=dev)
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        nz = None if noise is None else noise.to(dev, self._dtype).contiguous()
+        coeff, ldc, off = self._rff_args()
+        if self._f64:
+            ws = self._buf('grad_ws', int(lib.bsig_mdn_workspace_bytes_f64(C.byref(cfg), b)) // 8 + 1, torch.float64)
+            _lib.check(lib.bsig_mdn_loss_grad_f64(
+                C.byref(cfg), C.byref(self._hyper()), _lib.ptr(self._flat), _lib.ptr(coeff), ldc,
+                _lib.ptr(off), _lib.ptr(xs), ldx, _lib.ptr(ys), ldy, _lib.ptr(ridx), b,
+                int(norm_batch or b), _lib.ptr(nz), self._seed() if seed is None else int(seed), 0,
+                _lib.ptr(self._flat_grad if grads_out is None else grads_out), _lib.ptr(loss),
+                _lib.ptr(flag), _lib.ptr(ws), ws.numel() * 8, _lib.stream()))
+            assert int(flag.item()) == 0
+            return loss[0]
         ws_bytes = int(lib.bsig_mdn_workspace_bytes(C.byref(cfg), b))
         ws = self._buf('grad_ws', ws_bytes // 4 + 1)
-        loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        nz = None if noise is None else noise.to(dev, torch.float32).contiguous()
-        coeff, ldc, off = self._rff_args()
         _lib.check(lib.bsig_mdn_loss_grad(
             C.byref(cfg), _lib.ptr(self._flat), _lib.ptr(coeff), ldc, _lib.ptr(off),
             _lib.ptr(xs), ldx, _lib.ptr(ys), ldy, _lib.ptr(ridx), b,
@@ -468,6 +550,12 @@ class MDNN(nn.Module):
         """One torch.optim.Adam step (defaults) over the flat buffers; t is
         the 1-based step number since the optimizer was created."""
         lib = self._gpu()
+        if self._f64:
+            _lib.check(lib.bsig_adam_flat_f64(
+                _lib.ptr(self._flat), _lib.ptr(self._flat_grad), _lib.ptr(self._exp_avg),
+                _lib.ptr(self._exp_avg_sq), self._flat.numel(), float(self.lr), 0.9, 0.999,
+                1e-8, int(t), _lib.stream()))
+            return
         _lib.check(lib.bsig_adam_flat(
             _lib.ptr(self._flat), _lib.ptr(self._flat_grad), _lib.ptr(self._exp_avg),
             _lib.ptr(self._exp_avg_sq), self._flat.numel(), float(self.lr), 0.9, 0.999,
@@ -482,6 +570,8 @@ class MDNN(nn.Module):
         The exchange is the C ABI's communicator (bsig_comm_*: RCCL, or with
         ``transport='torch'`` the group's own collectives behind the same entry
         points) and run_training's update loop is bsig_fit_run_dp."""
+        if self._f64:
+            self._f64_dp_error()
         self._dp = _dp.DataParallel(group)
         if self._flat.is_cuda:
             with _lib.on_device(self._flat.device):
@@ -499,7 +589,12 @@ class MDNN(nn.Module):
         'test_loss': [...]} with the same 6 logging points.  ``ids_table``
         [n_updates, batch] (optional) overrides the numpy-RNG minibatch draw
         (teacher forcing for parity tests)."""
+        self._check_f64_dp()
+
         def once():
+            if self._f64:
+                return self._run_training_f64(x_data, y_data, n_updates, batch_size, test_frac,
+                                              ids_table, _defer)
             return self._run_training_once(x_data, y_data, n_updates, batch_size, test_frac,
                                            ids_table, _defer, _feats)
         # (deferred logs: the caller -- BayesSim.fit -- holds the snapshot and repeats its loop)
@@ -615,7 +710,7 @@ class MDNN(nn.Module):
         from an RNG).  The minibatch ids and jitter seeds are drawn chunk by chunk with the calls of the
         per-chunk path, in its order."""
         if (self._dp is not None or not self._flat.is_cuda or self._no_block_launch
-                or self.rff is None or len(sizes) < 1):
+                or self.rff is None or len(sizes) < 1 or self._f64):
             return None
         lib = self._gpu()
         self.train()
@@ -766,12 +861,91 @@ class MDNN(nn.Module):
                                   dp=(eval_its, n_updates, world))
         return pending if _defer else pending.result()
 
+    @_on_model_device
+    def _run_training_f64(self, x_data, y_data, n_updates, batch_size, test_frac, ids_table, _defer):
+        """run_training in the fp64 mode: the protocol of _run_training_once on bsig_fit64_* -- fp32
+        inputs widened on the device, ids drawn on the host in numpy-RNG order, plain launches, one
+        read-back."""
+        assert x_data.shape[0] == y_data.shape[0]
+        lib = self._gpu()
+        self.train()
+        cfg = self._cfg()
+        dev = self._flat.device
+        d, n_tot = self.output_dim, x_data.shape[0]
+        n_train, n_test = split_rows(n_tot, test_frac)
+        st = _lib.stream()
+        key = ('f64', batch_size, max(n_test, self._bufs.get('cap_test', 0)), n_updates,
+               cfg.head.eps_noise, cfg.lr, cfg.head.min_weight, cfg.head.ll_limit,
+               max(n_train, self._bufs.get('cap_train', 0)))
+        if self._plan is None or self._plan_key != key:
+            caps = key[2], key[8]
+            self._drop_plan()
+            handle = C.c_void_p()
+            _lib.check(lib.bsig_fit64_create(C.byref(cfg), C.byref(self._hyper()), batch_size, caps[1],
+                                             caps[0], n_updates, C.byref(handle)))
+            self._plan, self._plan_key, self._plan64 = handle, key, True
+            self._bufs['cap_test'], self._bufs['cap_train'] = caps
+        xs, ldx = _lib.as_f64_rows(x_data, dev)
+        ys, ldy_src = _lib.as_f64_rows(y_data, dev)
+        assert xs.shape[1] == self.input_dim and ys.shape[1] == d
+        y_stage = torch.empty((n_tot, d), dtype=torch.float64, device=dev)
+        if self.output_lows is not None:      # mdnn.py:204-205
+            _lib.check(lib.bsig_normalize_rows_f64(
+                _lib.ptr(ys), ldy_src, _lib.ptr(self.output_lows), _lib.ptr(self.output_highs),
+                _lib.ptr(y_stage), d, n_tot, d, st))
+        else:
+            _lib.check(lib.bsig_copy_rows_f64(_lib.ptr(ys), ldy_src, None, _lib.ptr(y_stage), d, n_tot, d, st))
+        if ids_table is None:      # mdnn.py:219-222, the draws of the fp32 path
+            ids_np = np.random.randint(0, n_train, (n_updates, batch_size), dtype=np.int32)
+        else:
+            ids_np = np.asarray(ids_table)
+            assert ids_np.shape == (n_updates, batch_size)
+        n_ids = n_updates * batch_size
+        ids_dev = self._buf('ids', max(n_ids, 1), torch.int32)
+        with self._pinned_upload('ids_ring', ids_dev, n_ids) as host:
+            host[:] = ids_np.reshape(-1)
+        eval_its = eval_updates(n_updates)[1]
+        n_e = len(eval_its)
+        train_loss = self._buf('train_loss', max(n_updates, 1), torch.float64)
+        test_loss = self._buf('test_loss', max(n_e, 1), torch.float64)
+        state = self._buf('state', 32, torch.int32)
+        ws = self._buf('fit_ws', int(lib.bsig_fit64_workspace_bytes(self._plan)) // 8 + 1, torch.float64)
+        coeff, ldc, off = self._rff_args()
+        fb = _lib.Fit64Buffers()
+        fb.params, fb.grads = self._flat.data_ptr(), self._flat_grad.data_ptr()
+        fb.exp_avg, fb.exp_avg_sq = self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr()
+        fb.rff_coeff, fb.ld_coeff, fb.rff_offset = _lib.ptr(coeff), ldc, _lib.ptr(off)
+        fb.x_train, fb.ldx_train, fb.n_train = xs.data_ptr(), ldx, n_train
+        fb.y_train, fb.ldy_train = y_stage.data_ptr(), d
+        fb.x_test, fb.ldx_test, fb.n_test = xs.data_ptr() + 8 * n_train * ldx, ldx, n_test
+        fb.y_test, fb.ldy_test = y_stage.data_ptr() + 8 * n_train * d, d
+        fb.ids_table = ids_dev.data_ptr()
+        fb.train_loss, fb.test_loss = train_loss.data_ptr(), test_loss.data_ptr()
+        fb.state, fb.workspace, fb.workspace_bytes = state.data_ptr(), ws.data_ptr(), ws.numel() * 8
+        fb.x_kind = _lib.X_ROWS
+        _lib.check(lib.bsig_fit64_bind(self._plan, C.byref(fb), 0))
+        _lib.check(lib.bsig_fit64_begin(self._plan, self._seed(), batch_size, st))
+        _lib.check(lib.bsig_fit64_run(self._plan, n_updates, st))
+        packed = torch.empty(2 * n_e + 1, dtype=torch.float64, device=dev)
+        _lib.check(lib.bsig_fit64_pack_logs(self._plan, n_updates, n_e, _lib.ptr(packed), st))
+        # (the staged rows must outlive the enqueued work: kept until the next call)
+        self._bufs['f64_keepalive'] = (xs, ys, y_stage)
+        pending = PendingLogs(packed, n_e, n_test, type(self).VERBOSE)
+        return pending if _defer else pending.result()
+
     fit = run_training   # the north-star name for the same call
 
     @_on_model_device
     def normalize_samples(self, params):
         """Reference mdnn.py:245-248."""
         lib = self._gpu()
+        if self._f64:
+            ps, ldp = _lib.as_f64_rows(params, self._flat.device)
+            out = torch.empty(ps.shape, dtype=torch.float64, device=ps.device)
+            _lib.check(lib.bsig_normalize_rows_f64(
+                _lib.ptr(ps), ldp, _lib.ptr(self.output_lows), _lib.ptr(self.output_highs),
+                _lib.ptr(out), out.stride(0), ps.shape[0], ps.shape[1], _lib.stream()))
+            return out
         ps, ldp = _lib.as_f32_rows(params, self._flat.device)
         out = torch.empty_like(ps)
         _lib.check(lib.bsig_normalize_rows(
@@ -793,6 +967,7 @@ class MDNN(nn.Module):
             lows = self.output_lows.cpu().numpy()
             rng = self.output_highs.cpu().numpy() - lows
         rows, _ = np.tril_indices(self.output_dim, -1)
+        npdt = np.float64 if self._f64 else np.float32      # the mixtures follow the model's dtype
         mogs = []
         for pt in range(ntest):
             ms, ls = [], []
@@ -804,8 +979,8 @@ class MDNN(nn.Module):
                     m = m * rng + lows
                     diag = diag * rng
                     lower = None if lower is None else lower * rng[rows]
-                ms.append(m.astype(np.float32))
+                ms.append(m.astype(npdt))
                 ls.append((diag if lower is None else np.concatenate([diag, lower]))
-                          .astype(np.float32))
+                          .astype(npdt))
             mogs.append(pdf.MoG(a=w[pt, :], ms=ms, Ls=ls))
         return mogs

@@ -41,6 +41,15 @@ class MDRFF(MDNN):
         return cfg
 
     def _rff_args(self):
+        if self._f64:
+            # fp64 mode: the widened fp32 draws, divided in double (what the reference's rff.py:130
+            # computes once freqs and sigma are doubles); features are projected in double per call
+            co = self._bufs.get('coeff64')
+            if co is None:
+                dev = self._flat.device
+                co = (self.rff.freqs.to(dev).double() / self.rff.sigma.to(dev).double()).contiguous()
+                self._bufs['coeff64'] = co
+            return co, co.stride(0), None
         co = self.rff.coeff()
         return co, co.stride(0), None
 

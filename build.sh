@@ -20,10 +20,12 @@ FLAGS="${BSIG_EXTRA_FLAGS:-} --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -W
 WIDE_TILES=""
 if [ "${BSIG_BUILD_WIDE_TILES:-0}" = "1" ]; then FLAGS="$FLAGS -DBSIG_WITH_WIDE_TILES"; WIDE_TILES="gemm_tile_128x288 gemm_tile_288x128"; fi
 COMMON=$(cat "$SRC"/*.h include/bsig.h | sha256sum | cut -d' ' -f1)
+# the fp64 mode (csrc/f64/, include/bsig_f64.h): its objects' stamps cover its own headers too
+COMMON64=$(cat "$SRC"/f64/*.h include/bsig_f64.h | sha256sum | cut -d' ' -f1)
 pids=()
-build_one() {  # name, source, extra flags
+build_one() {  # name, source, extra flags[, hash of further headers the source sees]
   local stamp="$OUT/obj/$1.stamp"
-  local want="$(echo "$FLAGS $3 $COMMON" | cat - "$2" | sha256sum | cut -d' ' -f1)"
+  local want="$(echo "$FLAGS $3 $COMMON${4:+ $4}" | cat - "$2" | sha256sum | cut -d' ' -f1)"
   if [ ! -f "$OUT/obj/$1.o" ] || [ ! -f "$stamp" ] || [ "$(cat "$stamp")" != "$want" ]; then
     ( hipcc $FLAGS $3 -c "$2" -o "$OUT/obj/$1.o" && echo "$want" > "$stamp" ) &
     pids+=($!)
@@ -36,6 +38,9 @@ for f in summarizers gemm_f32 gemm_tile_64 gemm_tile_128 gemm_tile_128x32 gemm_t
 done
 for f in api comm; do
   build_one "$f" "$SRC/$f.cpp" "-x hip"
+done
+for f in gemm_f64 mdn_head_f64 flat_ops_f64 estimator_f64; do
+  build_one "$f" "$SRC/f64/$f.hip" "" "$COMMON64"
 done
 rc=0
 for p in "${pids[@]:-}"; do [ -n "$p" ] && { wait "$p" || rc=1; }; done
