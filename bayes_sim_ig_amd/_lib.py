@@ -1,5 +1,10 @@
 """ctypes binding of libbsig_hip.so (include/bsig.h, include/bsig_f64.h).
 
+Whether a call computes in fp32 or fp64 is decided in ONE place, the two ``Precision`` objects ``F32`` and
+``F64`` below: they carry the dtype, the sizes and the entry points that exist in both modes under one
+signature, and ``as_rows`` converts a caller's rows to either.  What exists in fp32 only (data parallel, block
+launches, debug entry points) is called on the library directly.
+
 The product path has NO fallback: if the library is missing or there is no
 GPU, every compute entry point raises.  torch is used only for device memory,
 streams and torch.distributed.
@@ -297,6 +302,113 @@ def check(rc):
     raise RuntimeError('libbsig_hip: %s (code %d)' % (msg, rc))
 
 
+class Precision:
+    """The one place where "fp32 or fp64" is decided: the dtype and its sizes, the buffers struct of a fit
+    plan and every entry point that exists in both precisions, under ONE signature per operation -- the
+    fp64 one, with the bsig_f64_hyper* behind the dims / cfg argument (include/bsig_f64.h); F32 drops it
+    and calls the unsuffixed symbol.  Calls that return a code are checked.  The entry points are resolved
+    together, on the first use of any, and then are plain attributes of the instance.
+
+    What an fp64 plan cannot do (persistent kernels, factor rows, handed-over features, block launches) it
+    answers here, WITHOUT calling the library: no bsig_fit_* function ever sees a plan that
+    bsig_fit64_create made."""
+    # operation -> (fp32 symbol, fp64 symbol)
+    OPS = {
+        'head_workspace_bytes': ('bsig_head_workspace_bytes', 'bsig_head_workspace_bytes_f64'),
+        'mdn_workspace_bytes': ('bsig_mdn_workspace_bytes', 'bsig_mdn_workspace_bytes_f64'),
+        'head_forward': ('bsig_mdn_head_forward', 'bsig_mdn_head_forward_f64'),
+        'head_outputs': ('bsig_mdn_head_outputs', 'bsig_mdn_head_outputs_f64'),
+        'nll_from_tuple': ('bsig_mdn_nll_from_tuple', 'bsig_mdn_nll_from_tuple_f64'),
+        'loss_grad': ('bsig_mdn_loss_grad', 'bsig_mdn_loss_grad_f64'),
+        'adam_flat': ('bsig_adam_flat', 'bsig_adam_flat_f64'),
+        'normalize_rows': ('bsig_normalize_rows', 'bsig_normalize_rows_f64'),
+        'copy_rows': ('bsig_copy_rows', 'bsig_copy_rows_f64'),
+    }
+    HYPER_OPS = ('head_forward', 'head_outputs', 'nll_from_tuple', 'loss_grad')    # take the hyper in fp64
+    # the plan lifecycle
+    FIT_OPS = {
+        'fit_create': ('bsig_fit_create_ex', 'bsig_fit64_create'),
+        'fit_destroy': ('bsig_fit_destroy', 'bsig_fit64_destroy'),
+        'fit_workspace_bytes': ('bsig_fit_workspace_bytes', 'bsig_fit64_workspace_bytes'),
+        'fit_bind': ('bsig_fit_bind', 'bsig_fit64_bind'),
+        'fit_begin': ('bsig_fit_begin', 'bsig_fit64_begin'),
+        'fit_run': ('bsig_fit_run', 'bsig_fit64_run'),
+        'fit_pack_logs': ('bsig_fit_pack_logs', 'bsig_fit64_pack_logs'),
+    }
+    # what a plan can do -> (the fp32 symbol, what an fp64 plan answers); fit_set_features: an fp64 plan
+    # declines, as an fp32 plan without a feature cache does
+    QUERIES = {
+        'is_persistent': ('bsig_fit_is_persistent', 0),
+        'accepts_factor_rows': ('bsig_fit_accepts_factor_rows', 0),
+        'evaluates_from_factors': ('bsig_fit_evaluates_from_factors', 0),
+        'takes_features': ('bsig_fit_takes_features', 0),
+        'block_chunks': ('bsig_fit_block_chunks', 0),
+        'fit_set_features': ('bsig_fit_set_features', BSIG_EUNSUPPORTED),
+    }
+
+    def __init__(self, dtype):
+        self.dtype = dtype
+        self.itemsize = 8 if dtype == torch.float64 else 4
+        self.np_dtype = np.float64 if self.itemsize == 8 else np.float32
+        self.Buffers, self.state_words = (Fit64Buffers, 32) if self.itemsize == 8 else (FitBuffers, 16)
+        # fp32 replays an update from a HIP graph, so a call's rows are staged at fixed addresses; fp64
+        # has no graphs: it binds the rows where they lie and is never asked for one (FIT_GRAPH)
+        self.replays_graphs = self.itemsize == 4
+        self._protos = _PROTOS_F64 if self.itemsize == 8 else _PROTOS
+        for op in list(self.OPS) + list(self.FIT_OPS) + list(self.QUERIES):      # (a typo fails the import)
+            assert self.symbol(op) is None or self.symbol(op) in self._protos, op
+
+    def __repr__(self):
+        return 'Precision(%s)' % (self.dtype,)
+
+    def symbol(self, op):
+        """The library symbol behind ``op``; None where this precision answers without the library."""
+        if op in self.QUERIES:
+            return None if self.itemsize == 8 else self.QUERIES[op][0]
+        return (self.OPS.get(op) or self.FIT_OPS[op])[self.itemsize == 8]
+
+    def __getattr__(self, op):       # the first use of an entry point
+        if op not in self.OPS and op not in self.FIT_OPS and op not in self.QUERIES:
+            raise AttributeError(op)
+        self._resolve()
+        return vars(self)[op]
+
+    def _resolve(self):
+        lib, is64 = load(), self.itemsize == 8
+
+        def checked(fn, drop_hyper=False):
+            if drop_hyper:
+                return lambda first, hyper, *rest: check(fn(first, *rest))
+            return lambda *args: check(fn(*args))
+
+        for op in list(self.OPS) + list(self.FIT_OPS):
+            name = self.symbol(op)
+            fn = getattr(lib, name)
+            if self._protos[name][0] is C.c_int:      # a return code (the others: a size, nothing)
+                fn = checked(fn, drop_hyper=op in self.HYPER_OPS and not is64)
+            setattr(self, op, fn)
+        for op, (name, answer) in self.QUERIES.items():
+            setattr(self, op, (lambda *args, answer=answer: answer) if is64 else getattr(lib, name))
+        create, pack = self.fit_create, self.fit_pack_logs
+
+        def fit_create(cfg, hyper, batch, max_train, max_test, n_updates, flags):
+            handle = C.c_void_p()
+            if is64:
+                # (an fp64 plan IS per-phase launches: that option holds by itself; there is no other)
+                if flags & ~PLAN_NO_PERSISTENT:
+                    raise NotImplementedError('bsig_fit64_create takes no plan flags (%d)' % flags)
+                create(cfg, hyper, batch, max_train, max_test, n_updates, C.byref(handle))
+            else:
+                create(cfg, batch, max_train, max_test, n_updates, flags, C.byref(handle))
+            return handle
+        self.fit_create = fit_create
+        if not is64:
+            self.fit_pack_logs = lambda plan, n_updates, n_evals, out, st: pack(plan, n_updates, out, st)
+
+
+F32, F64 = Precision(torch.float32), Precision(torch.float64)
+
+
 def ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -312,16 +424,19 @@ def on_device(device):
     return torch.cuda.device(device)
 
 
-def as_f32_rows(t, device=None):
-    """fp32, last dim contiguous, on the GPU.  Returns (tensor, ld)."""
+def as_rows(t, device=None, dtype=torch.float32):
+    """``dtype`` (fp32 or fp64), last dim contiguous, on the GPU.  Returns (tensor, ld).  The smaller form
+    crosses the bus: an input is narrowed to fp32 before the move to the device, widened to fp64 after it."""
     if hasattr(t, 'materialize'):      # a lazy summary handle (summarizers.CrossCorrFactors)
         t = t.materialize()
-    if t.dtype != torch.float32:
-        t = t.float()
+    if dtype != torch.float64 and t.dtype != dtype:
+        t = t.to(dtype)
     if device is not None and t.device != torch.device(device):
         t = t.to(device)
     if not t.is_cuda:
         raise RuntimeError('expected a GPU tensor (no CPU fallback)')
+    if t.dtype != dtype:
+        t = t.to(dtype)
     if t.dim() != 2:
         raise AssertionError('expected a 2-D tensor')
     if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
@@ -330,22 +445,7 @@ def as_f32_rows(t, device=None):
     return t, ld
 
 
-def as_f64_rows(t, device=None):
-    """as_f32_rows for the fp64 mode: fp32 (or any other) input is widened on the device."""
-    if hasattr(t, 'materialize'):
-        t = t.materialize()
-    if device is not None and t.device != torch.device(device):
-        t = t.to(device)
-    if not t.is_cuda:
-        raise RuntimeError('expected a GPU tensor (no CPU fallback)')
-    if t.dtype != torch.float64:
-        t = t.double()
-    if t.dim() != 2:
-        raise AssertionError('expected a 2-D tensor')
-    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        t = t.contiguous()
-    ld = t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
-    return t, ld
+as_f32_rows = as_rows      # (the fp32-only callers: rff.py, the block launch, factor rows)
 
 
 def round_up(x, m):

@@ -10,8 +10,9 @@ Adam runs over the flat buffer, and ``run_training`` replays the whole update
 from a HIP graph (csrc/estimator.hip).  There is no CPU fallback.
 
 ``model.double()`` switches the model to the fp64 mode (include/bsig_f64.h, csrc/f64/): the flat
-buffers become float64 and every entry point below runs the per-phase fp64 kernels -- the
-reference under ``torch.set_default_dtype(torch.float64)``; ``model.float()`` goes back.
+buffers become float64 -- the reference under ``torch.set_default_dtype(torch.float64)``;
+``model.float()`` goes back.  Every entry point below is written once: which library functions, struct
+and sizes it uses comes from ``self._prec``, one of ``_lib.F32`` / ``_lib.F64``, and nowhere else.
 """
 import contextlib
 import ctypes as C
@@ -122,8 +123,8 @@ class MDNN(nn.Module):
     PAD_TRUNK_TO = 128   # hidden width the persistent update kernel is built for
     rff = None           # the feature map of an MDRFF
     _dtype = torch.float32   # torch.float64 after .double(): the fp64 mode
-    _plan64 = False      # the plan is a bsig_fit64 one
     _plan = None         # (a model whose construction failed is still finalised: __del__)
+    _plan_prec = None    # the _lib.Precision that created _plan: the one that may destroy it
 
     def __init__(self, input_dim, output_dim, output_lows, output_highs,
                  n_gaussians, full_covariance, hidden_layers, activation, lr,
@@ -275,6 +276,11 @@ class MDNN(nn.Module):
     def _f64(self):
         return self._dtype == torch.float64
 
+    @property
+    def _prec(self):
+        """The precision seam (_lib.Precision) of the model's dtype."""
+        return _lib.F64 if self._f64 else _lib.F32
+
     @staticmethod
     def _f64_dp_error():
         raise NotImplementedError('a double MDNN cannot be data-parallel: the fp64 mode has no gradient '
@@ -290,12 +296,13 @@ class MDNN(nn.Module):
         return _lib.F64Hyper(float(self.lr), 0.9, 0.999, 1e-8, float(cls.EPS_NOISE), float(cls.MIN_WEIGHT),
                              float(cls.LL_LIMIT), float(self._rff_scale))
 
-    def _drop_plan(self):
+    def _drop_plan(self, bufs=True):
+        """Release the plan through the precision that created it; with ``bufs`` the call buffers too."""
         if self._plan:
-            lib = _lib.load()
-            (lib.bsig_fit64_destroy if self._plan64 else lib.bsig_fit_destroy)(self._plan)
-        self._plan, self._plan_key, self._plan64 = None, None, False
-        self._bufs = {}
+            self._plan_prec.fit_destroy(self._plan)
+        self._plan, self._plan_key, self._plan_prec = None, None, None
+        if bufs:
+            self._bufs = {}
 
     def __del__(self):
         try:
@@ -321,7 +328,7 @@ class MDNN(nn.Module):
             return False
         if self._f64:        # the fp64 mode is per-phase launches only
             return False
-        return self._plan is None or bool(_lib.load().bsig_fit_is_persistent(self._plan))
+        return self._plan is None or bool(self._plan_prec.is_persistent(self._plan))
 
     def _retrying(self, fn):
         """``fn()``, the work of one run_training or one BayesSim.fit whose logs it reads itself -- repeated
@@ -379,7 +386,8 @@ class MDNN(nn.Module):
                                "(no CPU fallback)" % (self.device,))
         return lib
 
-    def _buf(self, name, numel, dtype=torch.float32):
+    def _buf(self, name, numel, dtype=None):
+        dtype = dtype or self._dtype
         t = self._bufs.get(name)
         if t is None or t.numel() < numel or t.dtype != dtype:
             t = torch.empty(max(int(numel), 1), dtype=dtype, device=self._flat.device)
@@ -399,40 +407,27 @@ class MDNN(nn.Module):
     # ----------------------------------------------------------- forward
     @_on_model_device
     def _head_forward(self, x):
-        lib = self._gpu()
+        lib, prec = self._gpu(), self._prec
         cfg = self._cfg()
-        if self._f64:
-            xs, ldx = _lib.as_f64_rows(x, self._flat.device)
-            assert xs.shape[1] == self.input_dim
-            b = xs.shape[0]
-            nh = int(lib.bsig_head_width(C.byref(cfg.head)))
-            out = torch.empty((b, nh), dtype=torch.float64, device=xs.device)
-            ws = self._buf('fwd_ws', int(lib.bsig_mdn_workspace_bytes_f64(C.byref(cfg), b)) // 8 + 1, torch.float64)
-            coeff, ldc, off = self._rff_args()
-            _lib.check(lib.bsig_mdn_head_forward_f64(
-                C.byref(cfg), C.byref(self._hyper()), _lib.ptr(self._flat), _lib.ptr(coeff), ldc,
-                _lib.ptr(off), _lib.ptr(xs), ldx, None, b, _lib.ptr(out), nh, _lib.ptr(ws),
-                ws.numel() * 8, _lib.stream()))
-            return cfg, out
-        xs, ldx = _lib.as_f32_rows(x, self._flat.device)
+        xs, ldx = _lib.as_rows(x, self._flat.device, prec.dtype)
         assert xs.shape[1] == self.input_dim
         b = xs.shape[0]
         nh = int(lib.bsig_head_width(C.byref(cfg.head)))
-        out = torch.empty((b, nh), dtype=torch.float32, device=xs.device)
-        ws_bytes = int(lib.bsig_mdn_workspace_bytes(C.byref(cfg), b))
-        ws = self._buf('fwd_ws', ws_bytes // 4 + 1)
+        out = torch.empty((b, nh), dtype=prec.dtype, device=xs.device)
+        ws = self._buf('fwd_ws', int(prec.mdn_workspace_bytes(C.byref(cfg), b)) // prec.itemsize + 1)
         coeff, ldc, off = self._rff_args()
-        _lib.check(lib.bsig_mdn_head_forward(
-            C.byref(cfg), _lib.ptr(self._flat), _lib.ptr(coeff), ldc, _lib.ptr(off),
+        prec.head_forward(
+            C.byref(cfg), C.byref(self._hyper()), _lib.ptr(self._flat), _lib.ptr(coeff), ldc, _lib.ptr(off),
             _lib.ptr(xs), ldx, None, b, _lib.ptr(out), nh, _lib.ptr(ws),
-            ws.numel() * 4, _lib.stream()))
+            ws.numel() * prec.itemsize, _lib.stream())
         return cfg, out
 
     @_on_model_device
     def forward(self, x, noise=None):
         """Reference mdnn.py:89-125 -> (weights[B,K], mu[B,D,K], L_d[B,D,K],
         L[B,L_size,K] | None).  ``noise`` injects the rand_like draw."""
-        lib = self._gpu()
+        self._gpu()
+        prec = self._prec
         cfg, out = self._head_forward(x)
         b, d, k = out.shape[0], self.output_dim, self.n_gaussians
         dev, dt = out.device, self._dtype
@@ -445,19 +440,11 @@ class MDNN(nn.Module):
         flag = torch.zeros(1, dtype=torch.int32, device=dev)
         nz = None if noise is None else noise.to(dev, dt).contiguous()
         seed = self._seed()
-        if self._f64:
-            ws = self._buf('head_ws', 64 + int(lib.bsig_head_workspace_bytes_f64(C.byref(cfg.head), b)) // 8,
-                           torch.float64)
-            _lib.check(lib.bsig_mdn_head_outputs_f64(
-                C.byref(cfg.head), C.byref(self._hyper()), _lib.ptr(out), out.stride(0), b, _lib.ptr(nz),
-                seed, 0, _lib.ptr(weights), _lib.ptr(mu), _lib.ptr(l_d),
-                _lib.ptr(low), _lib.ptr(flag), _lib.ptr(ws), ws.numel() * 8, _lib.stream()))
-        else:
-            ws = self._buf('head_ws', 64 + int(lib.bsig_head_workspace_bytes(C.byref(cfg.head), b)) // 4)
-            _lib.check(lib.bsig_mdn_head_outputs(
-                C.byref(cfg.head), _lib.ptr(out), out.stride(0), b, _lib.ptr(nz),
-                seed, 0, _lib.ptr(weights), _lib.ptr(mu), _lib.ptr(l_d),
-                _lib.ptr(low), _lib.ptr(flag), _lib.ptr(ws), ws.numel() * 4, _lib.stream()))
+        ws = self._buf('head_ws', 64 + int(prec.head_workspace_bytes(C.byref(cfg.head), b)) // prec.itemsize)
+        prec.head_outputs(
+            C.byref(cfg.head), C.byref(self._hyper()), _lib.ptr(out), out.stride(0), b, _lib.ptr(nz),
+            seed, 0, _lib.ptr(weights), _lib.ptr(mu), _lib.ptr(l_d),
+            _lib.ptr(low), _lib.ptr(flag), _lib.ptr(ws), ws.numel() * prec.itemsize, _lib.stream())
         assert int(flag.item()) == 0      # isfinite asserts, mdnn.py:120-124
         # remembered so that mdn_loss_fn(*model(x), y).backward() works (below)
         self._fwd_ctx = (weights, x, nz, seed) if torch.is_grad_enabled() else None
@@ -466,12 +453,13 @@ class MDNN(nn.Module):
     @_on_model_device
     def mdn_loss_fn(self, weights, mu, L_d, L, y):
         """Reference mdnn.py:127-178 -> 0-dim loss tensor."""
-        lib = self._gpu()
+        self._gpu()
+        prec = self._prec
         cfg = self._cfg()
         dev = self._flat.device
         b = y.size()[0]
         dt = self._dtype
-        ys, ldy = (_lib.as_f64_rows if self._f64 else _lib.as_f32_rows)(y, dev)
+        ys, ldy = _lib.as_rows(y, dev, dt)
         w = weights.to(dev, dt).contiguous()
         m = mu.to(dev, dt).contiguous()
         s = L_d.to(dev, dt).contiguous()
@@ -480,19 +468,11 @@ class MDNN(nn.Module):
         head.full_cov = 0 if lo is None else 1
         loss = torch.zeros(1, dtype=dt, device=dev)
         flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        if self._f64:
-            ws = self._buf('head_ws', 64 + int(lib.bsig_head_workspace_bytes_f64(C.byref(head), b)) // 8,
-                           torch.float64)
-            _lib.check(lib.bsig_mdn_nll_from_tuple_f64(
-                C.byref(head), C.byref(self._hyper()), _lib.ptr(w), _lib.ptr(m), _lib.ptr(s), _lib.ptr(lo),
-                _lib.ptr(ys), ldy, b, _lib.ptr(loss), _lib.ptr(flag), _lib.ptr(ws),
-                ws.numel() * 8, _lib.stream()))
-        else:
-            ws = self._buf('head_ws', 64 + int(lib.bsig_head_workspace_bytes(C.byref(head), b)) // 4)
-            _lib.check(lib.bsig_mdn_nll_from_tuple(
-                C.byref(head), _lib.ptr(w), _lib.ptr(m), _lib.ptr(s), _lib.ptr(lo),
-                _lib.ptr(ys), ldy, b, _lib.ptr(loss), _lib.ptr(flag), _lib.ptr(ws),
-                ws.numel() * 4, _lib.stream()))
+        ws = self._buf('head_ws', 64 + int(prec.head_workspace_bytes(C.byref(head), b)) // prec.itemsize)
+        prec.nll_from_tuple(
+            C.byref(head), C.byref(self._hyper()), _lib.ptr(w), _lib.ptr(m), _lib.ptr(s), _lib.ptr(lo),
+            _lib.ptr(ys), ldy, b, _lib.ptr(loss), _lib.ptr(flag), _lib.ptr(ws),
+            ws.numel() * prec.itemsize, _lib.stream())
         assert int(flag.item()) == 0      # mdnn.py:172-174
         ctx = getattr(self, '_fwd_ctx', None)
         if torch.is_grad_enabled() and ctx is not None and ctx[0] is weights:
@@ -508,12 +488,12 @@ class MDNN(nn.Module):
         (mdnn.py:229-233): returns the 0-dim loss; gradients land in every
         parameter's ``.grad`` (views of the flat gradient buffer).  ``y`` is
         already normalised."""
-        lib = self._gpu()
+        self._gpu()
+        prec = self._prec
         cfg = self._cfg()
         dev = self._flat.device
-        as_rows = _lib.as_f64_rows if self._f64 else _lib.as_f32_rows
-        xs, ldx = as_rows(x, dev)
-        ys, ldy = as_rows(y, dev)
+        xs, ldx = _lib.as_rows(x, dev, prec.dtype)
+        ys, ldy = _lib.as_rows(y, dev, prec.dtype)
         ridx = None
         b = xs.shape[0]
         if rows is not None:
@@ -523,25 +503,13 @@ class MDNN(nn.Module):
         flag = torch.zeros(1, dtype=torch.int32, device=dev)
         nz = None if noise is None else noise.to(dev, self._dtype).contiguous()
         coeff, ldc, off = self._rff_args()
-        if self._f64:
-            ws = self._buf('grad_ws', int(lib.bsig_mdn_workspace_bytes_f64(C.byref(cfg), b)) // 8 + 1, torch.float64)
-            _lib.check(lib.bsig_mdn_loss_grad_f64(
-                C.byref(cfg), C.byref(self._hyper()), _lib.ptr(self._flat), _lib.ptr(coeff), ldc,
-                _lib.ptr(off), _lib.ptr(xs), ldx, _lib.ptr(ys), ldy, _lib.ptr(ridx), b,
-                int(norm_batch or b), _lib.ptr(nz), self._seed() if seed is None else int(seed), 0,
-                _lib.ptr(self._flat_grad if grads_out is None else grads_out), _lib.ptr(loss),
-                _lib.ptr(flag), _lib.ptr(ws), ws.numel() * 8, _lib.stream()))
-            assert int(flag.item()) == 0
-            return loss[0]
-        ws_bytes = int(lib.bsig_mdn_workspace_bytes(C.byref(cfg), b))
-        ws = self._buf('grad_ws', ws_bytes // 4 + 1)
-        _lib.check(lib.bsig_mdn_loss_grad(
-            C.byref(cfg), _lib.ptr(self._flat), _lib.ptr(coeff), ldc, _lib.ptr(off),
+        ws = self._buf('grad_ws', int(prec.mdn_workspace_bytes(C.byref(cfg), b)) // prec.itemsize + 1)
+        prec.loss_grad(
+            C.byref(cfg), C.byref(self._hyper()), _lib.ptr(self._flat), _lib.ptr(coeff), ldc, _lib.ptr(off),
             _lib.ptr(xs), ldx, _lib.ptr(ys), ldy, _lib.ptr(ridx), b,
             int(norm_batch or b), _lib.ptr(nz), self._seed() if seed is None else int(seed), 0,
             _lib.ptr(self._flat_grad if grads_out is None else grads_out), _lib.ptr(loss),
-            _lib.ptr(flag), _lib.ptr(ws),
-            ws.numel() * 4, _lib.stream()))
+            _lib.ptr(flag), _lib.ptr(ws), ws.numel() * prec.itemsize, _lib.stream())
         assert int(flag.item()) == 0
         return loss[0]
 
@@ -549,17 +517,11 @@ class MDNN(nn.Module):
     def adam_step(self, t):
         """One torch.optim.Adam step (defaults) over the flat buffers; t is
         the 1-based step number since the optimizer was created."""
-        lib = self._gpu()
-        if self._f64:
-            _lib.check(lib.bsig_adam_flat_f64(
-                _lib.ptr(self._flat), _lib.ptr(self._flat_grad), _lib.ptr(self._exp_avg),
-                _lib.ptr(self._exp_avg_sq), self._flat.numel(), float(self.lr), 0.9, 0.999,
-                1e-8, int(t), _lib.stream()))
-            return
-        _lib.check(lib.bsig_adam_flat(
+        self._gpu()
+        self._prec.adam_flat(
             _lib.ptr(self._flat), _lib.ptr(self._flat_grad), _lib.ptr(self._exp_avg),
             _lib.ptr(self._exp_avg_sq), self._flat.numel(), float(self.lr), 0.9, 0.999,
-            1e-8, int(t), _lib.stream()))
+            1e-8, int(t), _lib.stream())
 
     # ---------------------------------------------------------- training
     def enable_data_parallel(self, group=None, transport=None):
@@ -592,29 +554,25 @@ class MDNN(nn.Module):
         self._check_f64_dp()
 
         def once():
-            if self._f64:
-                return self._run_training_f64(x_data, y_data, n_updates, batch_size, test_frac,
-                                              ids_table, _defer)
             return self._run_training_once(x_data, y_data, n_updates, batch_size, test_frac,
                                            ids_table, _defer, _feats)
         # (deferred logs: the caller -- BayesSim.fit -- holds the snapshot and repeats its loop)
         return once() if _defer else self._retrying(once)
 
-    def _ensure_plan(self, lib, cfg, batch_size, n_train, n_test, n_updates):
+    def _ensure_plan(self, cfg, batch_size, n_train, n_test, n_updates):
         """The fit plan (graphs, persistent-kernel geometry), keyed by everything baked into it."""
+        prec = self._prec
         key = (batch_size, max(n_test, self._bufs.get('cap_test', 0)), n_updates,
                cfg.head.eps_noise, cfg.lr, cfg.head.min_weight, cfg.head.ll_limit,
-               max(n_train, self._bufs.get('cap_train', 0)))
+               max(n_train, self._bufs.get('cap_train', 0)), prec.dtype)
         if self._plan is None or self._plan_key != key:
-            if self._plan:
-                lib.bsig_fit_destroy(self._plan)
-            handle = C.c_void_p()
+            self._drop_plan(bufs=False)
             # (a model that met a persistent-launch time-out stays on the per-phase kernels: a plan
             # option, not the process-wide environment switch)
             flags = _lib.PLAN_NO_PERSISTENT if self._no_persistent else 0
-            _lib.check(lib.bsig_fit_create_ex(C.byref(cfg), batch_size, key[7], key[1],
-                                              n_updates, flags, C.byref(handle)))
-            self._plan, self._plan_key = handle, key
+            self._plan = prec.fit_create(C.byref(cfg), C.byref(self._hyper()), batch_size, key[7], key[1],
+                                         n_updates, flags)
+            self._plan_key, self._plan_prec = key, prec
             self._bufs['cap_test'], self._bufs['cap_train'] = key[1], key[7]
 
     @staticmethod
@@ -637,15 +595,14 @@ class MDNN(nn.Module):
             self._bufs['cap_rows'] = n_tot
         return self._bufs['cap_rows']
 
-    def _stage_targets(self, lib, ys, ldy_src, y_stage, ldy, rows, st):
+    def _stage_targets(self, ys, ldy_src, y_stage, ldy, rows, st):
         """``y_stage`` <- the targets, normalised to the unit box where the model has one (mdnn.py:204-205)."""
         if self.output_lows is not None:
-            _lib.check(lib.bsig_normalize_rows(
+            self._prec.normalize_rows(
                 _lib.ptr(ys), ldy_src, _lib.ptr(self.output_lows),
-                _lib.ptr(self.output_highs), _lib.ptr(y_stage), ldy, rows, self.output_dim, st))
+                _lib.ptr(self.output_highs), _lib.ptr(y_stage), ldy, rows, self.output_dim, st)
         else:
-            _lib.check(lib.bsig_copy_rows(_lib.ptr(ys), ldy_src, None, _lib.ptr(y_stage),
-                                          ldy, rows, self.output_dim, st))
+            self._prec.copy_rows(_lib.ptr(ys), ldy_src, None, _lib.ptr(y_stage), ldy, rows, self.output_dim, st)
 
     @contextlib.contextmanager
     def _pinned_upload(self, ring, dst, n):
@@ -669,37 +626,39 @@ class MDNN(nn.Module):
         slot[1].record()
 
     def _bind_flags(self):
-        return (_lib.FIT_GRAPH if type(self).USE_GRAPH else 0) | \
+        return (_lib.FIT_GRAPH if type(self).USE_GRAPH and self._prec.replays_graphs else 0) | \
             (_lib.FIT_SPLIT_ADAM if self._dp is not None else 0)
 
-    def _bind(self, lib, flags, x_stage, ldx, y_stage, ldy, n_train, n_test, ids_ptr, train_loss, test_loss,
+    def _bind(self, flags, x_stage, ldx, y_stage, ldy, n_train, n_test, ids_ptr, train_loss, test_loss,
               factors=None):
         """Bind the plan to one chunk: ``n_train`` training rows of ``x_stage`` / ``y_stage`` with the
         ``n_test`` held-out rows behind them, its ids and its log slots.  ``factors`` = (s_dim, a_dim,
         x_held) when the rows of ``x_stage`` are cross-correlation factor rows: the held-out pairs are then
         evaluated from the summary rows ``x_held``, or, without them, from their factor rows too."""
-        state = self._buf('state', 16, torch.int32)
-        ws = self._buf('fit_ws', int(lib.bsig_fit_workspace_bytes(self._plan)) // 4 + 1)
+        prec = self._prec
+        state = self._buf('state', prec.state_words, torch.int32)
+        ws = self._buf('fit_ws', int(prec.fit_workspace_bytes(self._plan)) // prec.itemsize + 1)
         coeff, ldc, off = self._rff_args()
-        held_x = x_stage.data_ptr() + 4 * n_train * ldx
-        fb = _lib.FitBuffers()
+        held_x = x_stage.data_ptr() + prec.itemsize * n_train * ldx
+        fb = prec.Buffers()
         fb.params, fb.grads = self._flat.data_ptr(), self._flat_grad.data_ptr()
         fb.exp_avg, fb.exp_avg_sq = self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr()
         fb.rff_coeff, fb.ld_coeff, fb.rff_offset = _lib.ptr(coeff), ldc, _lib.ptr(off)
         fb.x_train, fb.ldx_train, fb.n_train = x_stage.data_ptr(), ldx, n_train
         fb.y_train, fb.ldy_train = y_stage.data_ptr(), ldy
         fb.x_test, fb.ldx_test, fb.n_test = held_x, ldx, n_test
-        fb.y_test, fb.ldy_test = y_stage.data_ptr() + 4 * n_train * ldy, ldy
+        fb.y_test, fb.ldy_test = y_stage.data_ptr() + prec.itemsize * n_train * ldy, ldy
         fb.ids_table = ids_ptr
         fb.train_loss, fb.test_loss = train_loss.data_ptr(), test_loss.data_ptr()
-        fb.state, fb.workspace, fb.workspace_bytes = state.data_ptr(), ws.data_ptr(), ws.numel() * 4
+        fb.state, fb.workspace, fb.workspace_bytes = state.data_ptr(), ws.data_ptr(), ws.numel() * prec.itemsize
+        fb.x_kind = _lib.X_ROWS
         if factors is not None:
             s_dim, a_dim, x_held = factors
             fb.x_kind, fb.x_s, fb.x_a = _lib.X_CROSSCORR_FACTORS, s_dim, a_dim
             if n_test > 0:      # the held-out pairs' factor rows lie behind the training rows
                 fb.x_test_factors, fb.ldx_test_factors = held_x, ldx
                 fb.x_test, fb.ldx_test = (None, 0) if x_held is None else (x_held.data_ptr(), x_held.stride(0))
-        _lib.check(lib.bsig_fit_bind(self._plan, C.byref(fb), flags))
+        prec.fit_bind(self._plan, C.byref(fb), flags)
 
     @_on_model_device
     def run_training_block(self, feats, y_data, sizes, n_updates, batch_size, test_frac=0.2):
@@ -720,7 +679,7 @@ class MDNN(nn.Module):
         assert feats.shape[0] == rows == y_data.shape[0] and feats.is_cuda and feats.dtype == torch.float32
         split = [split_rows(n, test_frac) for n in sizes]
         n_train, n_test = max(a for a, _ in split), max(b for _, b in split)
-        self._ensure_plan(lib, cfg, batch_size, n_train, n_test, n_updates)
+        self._ensure_plan(cfg, batch_size, n_train, n_test, n_updates)
         st = _lib.stream()
         n_chunks, n_ids = len(sizes), len(sizes) * n_updates * batch_size
         n_e = len(eval_updates(n_updates)[1])
@@ -733,13 +692,13 @@ class MDNN(nn.Module):
         # finds every buffer it reads in place.  The summary rows themselves are not staged, as in a
         # per-chunk call whose features are handed over.
         x_stage = self._buf('x_stage', self._row_capacity(sizes[0]) * ldx)
-        self._bind(lib, self._bind_flags(), x_stage, ldx, y_stage, ldy, *split[0],
+        self._bind(self._bind_flags(), x_stage, ldx, y_stage, ldy, *split[0],
                    stage.data_ptr() + 64 * n_chunks, train_loss, test_loss)
-        if n_chunks > int(lib.bsig_fit_block_chunks(self._plan, n_train)):
+        if n_chunks > int(self._prec.block_chunks(self._plan, n_train)):
             return None
         ys, ldy_src = _lib.as_f32_rows(y_data, dev)
         assert ys.shape[1] == d
-        self._stage_targets(lib, ys, ldy_src, y_stage, ldy, rows, st)        # once over the block's rows
+        self._stage_targets(ys, ldy_src, y_stage, ldy, rows, st)        # once over the block's rows
         # ids (mdnn.py:219-222) and seeds: one numpy draw and one torch draw per chunk, as the per-chunk calls
         seeds = []
         with self._pinned_upload('blk_ring', stage, 16 * n_chunks + n_ids) as host:
@@ -763,23 +722,23 @@ class MDNN(nn.Module):
     def _run_training_once(self, x_data, y_data, n_updates, batch_size, test_frac=0.2,
                            ids_table=None, _defer=False, _feats=None):
         assert x_data.shape[0] == y_data.shape[0]
-        lib = self._gpu()
+        lib, prec = self._gpu(), self._prec
         self.train()
         cfg = self._cfg()
         dev = self._flat.device
         d, n_tot = self.output_dim, x_data.shape[0]
         n_train, n_test = split_rows(n_tot, test_frac)
         st = _lib.stream()
-        self._ensure_plan(lib, cfg, batch_size, n_train, n_test, n_updates)
+        self._ensure_plan(cfg, batch_size, n_train, n_test, n_updates)
         flags = self._bind_flags()
         # a cross-correlation summary may arrive as factor rows (summarizers.CrossCorrFactors):
         # plans whose first layer lives in the persistent kernel consume them as they are
         factors = None
         if isinstance(x_data, CrossCorrFactors) and \
-                not lib.bsig_fit_accepts_factor_rows(self._plan, x_data.s_dim, x_data.a_dim):
+                not prec.accepts_factor_rows(self._plan, x_data.s_dim, x_data.a_dim):
             x_data = x_data.materialize()
         ldy = _lib.round_up(d, 4)
-        ys, ldy_src = _lib.as_f32_rows(y_data, dev)
+        ys, ldy_src = _lib.as_rows(y_data, dev, prec.dtype)
         assert x_data.shape[1] == self.input_dim and ys.shape[1] == d
         cap_rows = self._row_capacity(n_tot)
         if isinstance(x_data, CrossCorrFactors):
@@ -789,21 +748,24 @@ class MDNN(nn.Module):
             # the held-out rows, read once per evaluation, as summary rows -- unless the launch
             # evaluates from the held-out pairs' factor rows too (a streamed first layer): then no
             # [n, I] block exists at all
-            eval_fac = bool(lib.bsig_fit_evaluates_from_factors(self._plan, x_data.s_dim, x_data.a_dim, flags))
+            eval_fac = bool(prec.evaluates_from_factors(self._plan, x_data.s_dim, x_data.a_dim, flags))
             x_held = x_data[n_train:].materialize() if n_test > 0 and not eval_fac else None
             self._bufs['x_keepalive'] = (x_stage, x_held)
             factors = (x_data.s_dim, x_data.a_dim, x_held)
+        elif not prec.replays_graphs:
+            # no graph to replay in this precision: the (widened) rows are bound where they lie
+            x_stage, ldx = _lib.as_rows(x_data, dev, prec.dtype)
+            self._bufs['x_keepalive'] = (x_stage, None)
         else:
             # chunk staging: fixed addresses (graph replay) and 16-B aligned rows
-            xs, ldx_src = _lib.as_f32_rows(x_data, dev)
+            xs, ldx_src = _lib.as_rows(x_data, dev, prec.dtype)
             ldx = _lib.round_up(self.input_dim, 4)
             x_stage = self._buf('x_stage', cap_rows * ldx)
             # (an MDRFF whose rows' features are handed over never reads the summaries themselves)
-            if _feats is None or not lib.bsig_fit_takes_features(self._plan, n_train):
-                _lib.check(lib.bsig_copy_rows(_lib.ptr(xs), ldx_src, None, _lib.ptr(x_stage), ldx,
-                                              n_tot, self.input_dim, st))
+            if _feats is None or not prec.takes_features(self._plan, n_train):
+                prec.copy_rows(_lib.ptr(xs), ldx_src, None, _lib.ptr(x_stage), ldx, n_tot, self.input_dim, st)
         y_stage = self._buf('y_stage', cap_rows * ldy)
-        self._stage_targets(lib, ys, ldy_src, y_stage, ldy, n_tot, st)
+        self._stage_targets(ys, ldy_src, y_stage, ldy, n_tot, st)
         n_ids = n_updates * batch_size
         ids_dev = self._buf('ids', max(n_ids, 1), torch.int32)
 
@@ -825,32 +787,33 @@ class MDNN(nn.Module):
         # chunk's rows, 7 ms at 100k rows -- runs under it.  Only where begin does not read the table
         # (a plan that projects the gathered minibatch rows instead of each row once does).
         late_ids = n_ids >= (1 << 16) and (cfg.rff_feats == 0 or
-                                           bool(lib.bsig_fit_takes_features(self._plan, n_train)))
+                                           bool(prec.takes_features(self._plan, n_train)))
         if not late_ids:
             upload_ids()
         eval_its = eval_updates(n_updates)[1]
         train_loss = self._buf('train_loss', n_updates)
         test_loss = self._buf('test_loss', len(eval_its))
-        self._bind(lib, flags, x_stage, ldx, y_stage, ldy, n_train, n_test, ids_dev.data_ptr(),
+        self._bind(flags, x_stage, ldx, y_stage, ldy, n_train, n_test, ids_dev.data_ptr(),
                    train_loss, test_loss, factors)
         if _feats is not None:
             # MDRFF: the rows' RFF features, already projected by the caller (BayesSim.fit)
             assert _feats.shape[0] == n_tot and _feats.is_cuda and _feats.dtype == torch.float32
             # (a plan without a per-row feature cache declines: bsig_fit_begin then projects)
-            lib.bsig_fit_set_features(self._plan, _lib.ptr(_feats), _feats.stride(0), n_tot, st)
+            prec.fit_set_features(self._plan, _lib.ptr(_feats), _feats.stride(0), n_tot, st)
         world = 1 if self._dp is None else self._dp.world
-        _lib.check(lib.bsig_fit_begin(self._plan, self._seed(), batch_size * world, st))
+        prec.fit_begin(self._plan, self._seed(), batch_size * world, st)
         if late_ids:
             upload_ids()
         if self._dp is None:
-            _lib.check(lib.bsig_fit_run(self._plan, n_updates, st))
+            prec.fit_run(self._plan, n_updates, st)
             # single read-back per call: 6+6 losses and the isfinite flag
             # (a fresh allocation per call -- no kernel: BayesSim.fit reads all chunks' logs at the end)
-            packed = torch.empty(2 * len(eval_its) + 1, dtype=torch.float32, device=dev)
-            _lib.check(lib.bsig_fit_pack_logs(self._plan, n_updates, _lib.ptr(packed), st))
+            packed = torch.empty(2 * len(eval_its) + 1, dtype=prec.dtype, device=dev)
+            prec.fit_pack_logs(self._plan, n_updates, len(eval_its), _lib.ptr(packed), st)
             pending = PendingLogs(packed, len(eval_its), n_test, type(self).VERBOSE)
         else:
-            # data parallel: grad -> all-reduce -> apply per update, driven from C
+            # data parallel (fp32 only: refused for a double model): grad -> all-reduce -> apply per update,
+            # driven from C
             self._dp._on_gpu = True
             logs = torch.empty(n_updates + len(eval_its) + 3, dtype=torch.float32, device=dev)
             _lib.check(lib.bsig_fit_run_dp(self._plan, self._dp.comm, n_updates, _lib.ptr(logs), st))
@@ -861,96 +824,17 @@ class MDNN(nn.Module):
                                   dp=(eval_its, n_updates, world))
         return pending if _defer else pending.result()
 
-    @_on_model_device
-    def _run_training_f64(self, x_data, y_data, n_updates, batch_size, test_frac, ids_table, _defer):
-        """run_training in the fp64 mode: the protocol of _run_training_once on bsig_fit64_* -- fp32
-        inputs widened on the device, ids drawn on the host in numpy-RNG order, plain launches, one
-        read-back."""
-        assert x_data.shape[0] == y_data.shape[0]
-        lib = self._gpu()
-        self.train()
-        cfg = self._cfg()
-        dev = self._flat.device
-        d, n_tot = self.output_dim, x_data.shape[0]
-        n_train, n_test = split_rows(n_tot, test_frac)
-        st = _lib.stream()
-        key = ('f64', batch_size, max(n_test, self._bufs.get('cap_test', 0)), n_updates,
-               cfg.head.eps_noise, cfg.lr, cfg.head.min_weight, cfg.head.ll_limit,
-               max(n_train, self._bufs.get('cap_train', 0)))
-        if self._plan is None or self._plan_key != key:
-            caps = key[2], key[8]
-            self._drop_plan()
-            handle = C.c_void_p()
-            _lib.check(lib.bsig_fit64_create(C.byref(cfg), C.byref(self._hyper()), batch_size, caps[1],
-                                             caps[0], n_updates, C.byref(handle)))
-            self._plan, self._plan_key, self._plan64 = handle, key, True
-            self._bufs['cap_test'], self._bufs['cap_train'] = caps
-        xs, ldx = _lib.as_f64_rows(x_data, dev)
-        ys, ldy_src = _lib.as_f64_rows(y_data, dev)
-        assert xs.shape[1] == self.input_dim and ys.shape[1] == d
-        y_stage = torch.empty((n_tot, d), dtype=torch.float64, device=dev)
-        if self.output_lows is not None:      # mdnn.py:204-205
-            _lib.check(lib.bsig_normalize_rows_f64(
-                _lib.ptr(ys), ldy_src, _lib.ptr(self.output_lows), _lib.ptr(self.output_highs),
-                _lib.ptr(y_stage), d, n_tot, d, st))
-        else:
-            _lib.check(lib.bsig_copy_rows_f64(_lib.ptr(ys), ldy_src, None, _lib.ptr(y_stage), d, n_tot, d, st))
-        if ids_table is None:      # mdnn.py:219-222, the draws of the fp32 path
-            ids_np = np.random.randint(0, n_train, (n_updates, batch_size), dtype=np.int32)
-        else:
-            ids_np = np.asarray(ids_table)
-            assert ids_np.shape == (n_updates, batch_size)
-        n_ids = n_updates * batch_size
-        ids_dev = self._buf('ids', max(n_ids, 1), torch.int32)
-        with self._pinned_upload('ids_ring', ids_dev, n_ids) as host:
-            host[:] = ids_np.reshape(-1)
-        eval_its = eval_updates(n_updates)[1]
-        n_e = len(eval_its)
-        train_loss = self._buf('train_loss', max(n_updates, 1), torch.float64)
-        test_loss = self._buf('test_loss', max(n_e, 1), torch.float64)
-        state = self._buf('state', 32, torch.int32)
-        ws = self._buf('fit_ws', int(lib.bsig_fit64_workspace_bytes(self._plan)) // 8 + 1, torch.float64)
-        coeff, ldc, off = self._rff_args()
-        fb = _lib.Fit64Buffers()
-        fb.params, fb.grads = self._flat.data_ptr(), self._flat_grad.data_ptr()
-        fb.exp_avg, fb.exp_avg_sq = self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr()
-        fb.rff_coeff, fb.ld_coeff, fb.rff_offset = _lib.ptr(coeff), ldc, _lib.ptr(off)
-        fb.x_train, fb.ldx_train, fb.n_train = xs.data_ptr(), ldx, n_train
-        fb.y_train, fb.ldy_train = y_stage.data_ptr(), d
-        fb.x_test, fb.ldx_test, fb.n_test = xs.data_ptr() + 8 * n_train * ldx, ldx, n_test
-        fb.y_test, fb.ldy_test = y_stage.data_ptr() + 8 * n_train * d, d
-        fb.ids_table = ids_dev.data_ptr()
-        fb.train_loss, fb.test_loss = train_loss.data_ptr(), test_loss.data_ptr()
-        fb.state, fb.workspace, fb.workspace_bytes = state.data_ptr(), ws.data_ptr(), ws.numel() * 8
-        fb.x_kind = _lib.X_ROWS
-        _lib.check(lib.bsig_fit64_bind(self._plan, C.byref(fb), 0))
-        _lib.check(lib.bsig_fit64_begin(self._plan, self._seed(), batch_size, st))
-        _lib.check(lib.bsig_fit64_run(self._plan, n_updates, st))
-        packed = torch.empty(2 * n_e + 1, dtype=torch.float64, device=dev)
-        _lib.check(lib.bsig_fit64_pack_logs(self._plan, n_updates, n_e, _lib.ptr(packed), st))
-        # (the staged rows must outlive the enqueued work: kept until the next call)
-        self._bufs['f64_keepalive'] = (xs, ys, y_stage)
-        pending = PendingLogs(packed, n_e, n_test, type(self).VERBOSE)
-        return pending if _defer else pending.result()
-
     fit = run_training   # the north-star name for the same call
 
     @_on_model_device
     def normalize_samples(self, params):
         """Reference mdnn.py:245-248."""
-        lib = self._gpu()
-        if self._f64:
-            ps, ldp = _lib.as_f64_rows(params, self._flat.device)
-            out = torch.empty(ps.shape, dtype=torch.float64, device=ps.device)
-            _lib.check(lib.bsig_normalize_rows_f64(
-                _lib.ptr(ps), ldp, _lib.ptr(self.output_lows), _lib.ptr(self.output_highs),
-                _lib.ptr(out), out.stride(0), ps.shape[0], ps.shape[1], _lib.stream()))
-            return out
-        ps, ldp = _lib.as_f32_rows(params, self._flat.device)
+        self._gpu()
+        ps, ldp = _lib.as_rows(params, self._flat.device, self._dtype)
         out = torch.empty_like(ps)
-        _lib.check(lib.bsig_normalize_rows(
+        self._prec.normalize_rows(
             _lib.ptr(ps), ldp, _lib.ptr(self.output_lows), _lib.ptr(self.output_highs),
-            _lib.ptr(out), out.stride(0), ps.shape[0], ps.shape[1], _lib.stream()))
+            _lib.ptr(out), out.stride(0), ps.shape[0], ps.shape[1], _lib.stream())
         return out
 
     def predict_MoGs(self, xs, noise=None):
@@ -967,7 +851,7 @@ class MDNN(nn.Module):
             lows = self.output_lows.cpu().numpy()
             rng = self.output_highs.cpu().numpy() - lows
         rows, _ = np.tril_indices(self.output_dim, -1)
-        npdt = np.float64 if self._f64 else np.float32      # the mixtures follow the model's dtype
+        npdt = self._prec.np_dtype      # the mixtures follow the model's dtype
         mogs = []
         for pt in range(ntest):
             ms, ls = [], []
