@@ -192,6 +192,9 @@ _PROTOS = {
 # include/bsig_f64.h: the fp64 mode
 _HD, _HY, _CFG = C.POINTER(HeadDims), C.POINTER(F64Hyper), C.POINTER(MdnCfg)
 _PROTOS_F64 = {
+    'bsig_summary_start_f64': (C.c_int, [vp, vp, vp, i64] + [C.c_int] * 5 + [i64, vp]),
+    'bsig_crosscorr_f64': (C.c_int, [vp, vp, vp, i64] + [C.c_int] * 5 + [i64, vp, vp]),
+    'bsig_signature_f64': (C.c_int, [vp, vp, vp, i64] + [C.c_int] * 4 + [i64, vp]),
     'bsig_gemm_f64': (C.c_int, [vp, i64, C.c_int, vp, vp, i64, C.c_int, vp, vp, i64, i64, i64, i64,
                                 C.c_int, C.c_int, vp, vp, i64, f64, vp]),
     'bsig_rff_project_f64': (C.c_int, [vp, i64, vp, vp, i64, vp, vp, i64, i64, i64, i64, f64, C.c_int, vp]),
@@ -314,6 +317,9 @@ class Precision:
     bsig_fit64_create made."""
     # operation -> (fp32 symbol, fp64 symbol)
     OPS = {
+        'summary_start': ('bsig_summary_start', 'bsig_summary_start_f64'),
+        'crosscorr': ('bsig_crosscorr', 'bsig_crosscorr_f64'),
+        'signature': ('bsig_signature', 'bsig_signature_f64'),
         'head_workspace_bytes': ('bsig_head_workspace_bytes', 'bsig_head_workspace_bytes_f64'),
         'mdn_workspace_bytes': ('bsig_mdn_workspace_bytes', 'bsig_mdn_workspace_bytes_f64'),
         'head_forward': ('bsig_mdn_head_forward', 'bsig_mdn_head_forward_f64'),

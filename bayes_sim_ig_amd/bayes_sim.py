@@ -49,7 +49,11 @@ class BayesSim(object):
         ``model_cfg`` keys beyond the reference's: ``nFeat`` (RFF features,
         default 200 as hard-coded at bayes_sim.py:81), ``sigDepth``, ``dtype``
         ('float32', the default, or 'float64': the estimator's fp64 mode, as
-        ``bs.model.double()``)."""
+        ``bs.model.double()``), ``summaryDtype`` ('float32', the default in both
+        modes: the summaries are made in fp32 and a double model gets them
+        widened; 'float64', only with ``'dtype': 'float64'``: the summarizers
+        compute in double too, so nothing between the trajectories and the
+        posterior is rounded to fp32)."""
         self.prior = prior
         self.proposal = proposal
         model_class = model_cfg['modelClass']
@@ -87,6 +91,13 @@ class BayesSim(object):
         dtype = model_cfg.get('dtype', 'float32')
         if dtype not in ('float32', 'float64'):
             raise ValueError("model_cfg['dtype'] must be 'float32' or 'float64', got %r" % (dtype,))
+        summary_dtype = model_cfg.get('summaryDtype', 'float32')
+        if summary_dtype not in ('float32', 'float64'):
+            raise ValueError("model_cfg['summaryDtype'] must be 'float32' or 'float64', got %r" % (summary_dtype,))
+        if summary_dtype == 'float64' and dtype != 'float64':
+            raise ValueError("model_cfg['summaryDtype'] = 'float64' needs model_cfg['dtype'] = 'float64' "
+                             "(an fp32 estimator would round the double summaries)")
+        self._summary_dtype = torch.float64 if summary_dtype == 'float64' else None
         self.model = _MODELS[model_class](**kwargs)
         if dtype == 'float64':
             self.model.double()
@@ -99,10 +110,11 @@ class BayesSim(object):
         return n
 
     def _summarize(self, states, actions, finite_flag=None, lazy=False):
+        # ('summaryDtype': 'float64' -- the summarizers' fp64 kernels; else no keyword: the fp32 path)
+        kw = {} if self._summary_dtype is None else {'dtype': self._summary_dtype}
         if self.summarizer_name == 'summary_signatory' and self._sig_depth:
-            return self.summarizer_fxn(states, actions, depth=self._sig_depth)
+            return self.summarizer_fxn(states, actions, depth=self._sig_depth, **kw)
         if self.summarizer_name in ('summary_corr', 'summary_corrdiff'):
-            kw = {}
             if finite_flag is not None:
                 # the isfinite assert of summarizers.py:120, deferred with the chunk's logs
                 kw['check_finite'] = finite_flag
@@ -111,10 +123,11 @@ class BayesSim(object):
             if lazy and self._lazy_summaries():
                 kw['lazy'] = True
             return self.summarizer_fxn(states, actions, **kw)
-        return self.summarizer_fxn(states, actions)
+        return self.summarizer_fxn(states, actions, **kw)
 
     def _lazy_summaries(self):
-        # (a double model takes summary rows only: materialised in fp32 by the summarizer kernels, widened)
+        # (a double model takes summary rows only: materialised by the summarizer kernels -- in fp32 and
+        # widened, or in double with 'summaryDtype': 'float64')
         return (self.model.rff is None and self.model._flat.is_cuda and not self.model._f64 and
                 os.environ.get('BSIG_NO_FUSED_SUMMARY') != '1')
 
@@ -155,7 +168,9 @@ class BayesSim(object):
         """Pairs per block of fit(): the summaries (and an MDRFF's RFF features, rff.py:128-132) are pure
         functions of the row, so both are computed for a block of chunks at once -- one summarizer launch
         over up to 32000 trajectories (and one large MFMA GEMM) instead of one small one per chunk."""
-        row_bytes = 4 * (self.model.input_dim + (self.model.rff.n_feat if self.model.rff is not None else 0))
+        summary_bytes = 8 if self._summary_dtype == torch.float64 else 4
+        row_bytes = summary_bytes * self.model.input_dim + \
+            4 * (self.model.rff.n_feat if self.model.rff is not None else 0)
         chunks = max(min(BayesSim.FIT_BLOCK_CHUNKS,
                          BayesSim.FIT_BLOCK_BYTES // (row_bytes * BayesSim.NUM_TRAIN_TRAJ_PER_BATCH)), 1)
         return chunks * BayesSim.NUM_TRAIN_TRAJ_PER_BATCH

@@ -6,6 +6,13 @@ Every function maps states[N,T,sd], actions[N,Ta,ad] (fp32) to a [N,F]
 tensor on the inputs' device.  The rows live in HBM with a 16-byte aligned
 pitch (ld = F rounded up to 4 floats) and the returned tensor is the [:, :F]
 view, so the estimator's GEMM loaders can use 128-bit loads.
+
+``dtype=torch.float64`` on any of them computes the summary in double instead
+(csrc/f64/summarizers_f64.hip): the inputs are widened -- exact for fp32 data --
+or taken as they are, the rows are float64 at a pitch of F rounded up to 2
+doubles.  ``None`` / ``torch.float32`` is the fp32 path, which narrows a
+float64 input.  Which library entry point a call reaches is decided by the
+precision seam (``_lib.F32`` / ``_lib.F64``).
 """
 import ctypes as C
 
@@ -16,25 +23,38 @@ from . import _lib
 KIND_START, KIND_CORR, KIND_CORRDIFF, KIND_SIGNATURE = 0, 1, 2, 3
 
 
-def _prep(states, actions):
+def _precision(dtype):
+    """The precision a summarizer call computes in: ``_lib.F32`` for ``None`` / float32, ``_lib.F64``."""
+    if dtype is None or dtype == torch.float32:
+        return _lib.F32
+    if dtype == torch.float64:
+        return _lib.F64
+    raise ValueError('summarizers compute in torch.float32 or torch.float64, got dtype=%r' % (dtype,))
+
+
+def _prep(states, actions, prec=_lib.F32):
     assert len(states.shape) == 3, 'Need states: ntraj x n_steps x state_dim'
     assert len(actions.shape) == 3, 'Need actions: ntraj x n_steps x state_dim'
     assert states.shape[0] == actions.shape[0]
     _lib.require_gpu()
     home = states.device
     dev = home if states.is_cuda else torch.device('cuda', torch.cuda.current_device())
-    s = states.to(device=dev, dtype=torch.float32).contiguous()
-    a = actions.to(device=dev, dtype=torch.float32).contiguous()
+    if prec.itemsize == 8:      # the smaller form crosses the bus: widened (exactly) on the device
+        s = states.to(device=dev).to(prec.dtype).contiguous()
+        a = actions.to(device=dev).to(prec.dtype).contiguous()
+    else:
+        s = states.to(device=dev, dtype=prec.dtype).contiguous()
+        a = actions.to(device=dev, dtype=prec.dtype).contiguous()
     return s, a, home
 
 
-def _alloc(n, width, device, out):
-    ld = _lib.round_up(width, 4)
+def _alloc(n, width, device, out, prec=_lib.F32):
+    ld = _lib.round_up(width, 16 // prec.itemsize)
     if out is not None:
-        assert out.is_cuda and out.dtype == torch.float32 and out.dim() == 2
+        assert out.is_cuda and out.dtype == prec.dtype and out.dim() == 2
         assert out.shape[0] >= n and out.stride(1) == 1 and out.stride(0) >= width
         return out, out.stride(0)
-    return torch.empty((n, ld), dtype=torch.float32, device=device), ld
+    return torch.empty((n, ld), dtype=prec.dtype, device=device), ld
 
 
 def _finish(buf, n, width, home, out):
@@ -71,22 +91,23 @@ def pad_states_actions(states, actions, tgt_actions_len=None):
     return states, actions
 
 
-def summary_start(states, actions, max_t=10, out=None):
+def summary_start(states, actions, max_t=10, out=None, dtype=None):
     """Reference summarizers.py:65-70."""
-    s, a, home = _prep(states, actions)
+    prec = _precision(dtype)
+    s, a, home = _prep(states, actions, prec)
     n, sd, ad = s.shape[0], s.shape[2], a.shape[2]
     width = max_t * (sd + ad)
-    buf, ld = _alloc(n, width, s.device, out)
-    _lib.check(_lib.load().bsig_summary_start(
+    buf, ld = _alloc(n, width, s.device, out, prec)
+    prec.summary_start(
         _lib.ptr(s), _lib.ptr(a), _lib.ptr(buf), n, s.shape[1], a.shape[1],
-        sd, ad, max_t, ld, _lib.stream()))
+        sd, ad, max_t, ld, _lib.stream())
     return _finish(buf, n, width, home, out)
 
 
-def summary_waypts(states, actions, n_waypts=10, out=None):
+def summary_waypts(states, actions, n_waypts=10, out=None, dtype=None):
     """Reference summarizers.py:73-87: the crop to ``n_waypts`` precedes the
     stride computation, so the waypoints are the first ``n_waypts`` steps."""
-    return summary_start(states, actions, max_t=n_waypts, out=out)
+    return summary_start(states, actions, max_t=n_waypts, out=out, dtype=dtype)
 
 
 class CrossCorrFactors:
@@ -173,26 +194,31 @@ class CrossCorrFactors:
 
 
 def cross_correlation(states, actions, use_state_diff=False, out=None,
-                      check_finite=True, lazy=False):
+                      check_finite=True, lazy=False, dtype=None):
     """Reference summarizers.py:90-122.  ``lazy=True`` returns a CrossCorrFactors handle
-    instead of the materialised ``[N, S*A + 2]`` tensor."""
+    instead of the materialised ``[N, S*A + 2]`` tensor (fp32 only)."""
+    prec = _precision(dtype)
     if lazy:
+        if prec is _lib.F64:
+            raise NotImplementedError(
+                'lazy=True with dtype=torch.float64: there are no factor rows in double -- the fp64 fit '
+                'refuses them (bsig_fit64_bind: BSIG_X_CROSSCORR_FACTORS is BSIG_EUNSUPPORTED)')
         return _cross_correlation_factors(states, actions, use_state_diff, check_finite)
-    s, a, home = _prep(states, actions)
+    s, a, home = _prep(states, actions, prec)
     n, t, sd = s.shape
     ad = a.shape[2]
     assert t > 1                      # summarizers.py:94
     width = summary_dim('summary_corrdiff' if use_state_diff else 'summary_corr',
                         t, sd, ad)
-    buf, ld = _alloc(n, width, s.device, out)
+    buf, ld = _alloc(n, width, s.device, out, prec)
     # check_finite may be a 1-element int32 device tensor: the kernel raises its flag there
     # and the caller asserts later (BayesSim.fit: one read-back for all chunks)
     deferred = torch.is_tensor(check_finite)
     flag = check_finite if deferred else (
         torch.zeros(1, dtype=torch.int32, device=s.device) if check_finite else None)
-    _lib.check(_lib.load().bsig_crosscorr(
+    prec.crosscorr(
         _lib.ptr(s), _lib.ptr(a), _lib.ptr(buf), n, t, a.shape[1], sd, ad,
-        1 if use_state_diff else 0, ld, _lib.ptr(flag), _lib.stream()))
+        1 if use_state_diff else 0, ld, _lib.ptr(flag), _lib.stream())
     if check_finite is not None and check_finite is not False and not deferred:
         assert int(flag.item()) == 0  # summarizers.py:120
     return _finish(buf, n, width, home, out)
@@ -220,14 +246,14 @@ def _cross_correlation_factors(states, actions, use_state_diff, check_finite):
     return CrossCorrFactors(fac, s_dim.value, a_dim.value)
 
 
-def summary_corrdiff(states, actions, out=None, check_finite=True, lazy=False):
+def summary_corrdiff(states, actions, out=None, check_finite=True, lazy=False, dtype=None):
     return cross_correlation(states, actions, use_state_diff=True, out=out,
-                             check_finite=check_finite, lazy=lazy)
+                             check_finite=check_finite, lazy=lazy, dtype=dtype)
 
 
-def summary_corr(states, actions, out=None, check_finite=True, lazy=False):
+def summary_corr(states, actions, out=None, check_finite=True, lazy=False, dtype=None):
     return cross_correlation(states, actions, use_state_diff=False, out=out,
-                             check_finite=check_finite, lazy=lazy)
+                             check_finite=check_finite, lazy=lazy, dtype=dtype)
 
 
 def signature_depth(ndim):
@@ -239,20 +265,21 @@ def signature_depth(ndim):
     return 1
 
 
-def summary_signatory(states, actions, depth=None, out=None):
+def summary_signatory(states, actions, depth=None, out=None, dtype=None):
     """Reference summarizers.py:144-168 with the signature computed by
     csrc/summarizers.hip instead of ``signatory``.  All N rows are returned
     (the reference drops N % 10 rows when N > 10000)."""
+    prec = _precision(dtype)
     assert len(states.shape) == 3, 'states should be batch x time x state_dim'
-    s, a, home = _prep(states, actions)
+    s, a, home = _prep(states, actions, prec)
     n, length, sd = s.shape
     ad = a.shape[2]
     assert a.shape[1] == length
     if depth is None:
         depth = signature_depth(1 + sd + ad)
     width = summary_dim('summary_signatory', length, sd, ad, depth)
-    buf, ld = _alloc(n, width, s.device, out)
-    _lib.check(_lib.load().bsig_signature(
+    buf, ld = _alloc(n, width, s.device, out, prec)
+    prec.signature(
         _lib.ptr(s), _lib.ptr(a), _lib.ptr(buf), n, length, sd, ad, depth, ld,
-        _lib.stream()))
+        _lib.stream())
     return _finish(buf, n, width, home, out)

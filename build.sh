@@ -39,7 +39,7 @@ done
 for f in api comm; do
   build_one "$f" "$SRC/$f.cpp" "-x hip"
 done
-for f in gemm_f64 mdn_head_f64 flat_ops_f64 estimator_f64; do
+for f in gemm_f64 mdn_head_f64 flat_ops_f64 estimator_f64 summarizers_f64; do
   build_one "$f" "$SRC/f64/$f.hip" "" "$COMMON64"
 done
 rc=0

@@ -1,7 +1,7 @@
 /*
  * bsig_f64.h — the fp64 mode of libbsig_hip.so: a second, self-contained PER-PHASE update path
  * (GEMMs on v_mfma_f64_16x16x4_f64, mixture-density head, Adam, fit loop) behind MDNN.double() /
- * MDRFF.double().  Companion of bsig.h, whose rules hold here too: raw DEVICE pointers (to fp64 /
+ * MDRFF.double(), and the trajectory summarizers in double (summarizers' dtype=torch.float64).  Companion of bsig.h, whose rules hold here too: raw DEVICE pointers (to fp64 /
  * int32 unless stated), leading dimensions in elements, every call asynchronous on `stream`, no
  * allocation, no synchronisation, BSIG_OK or a negative code, the thread-local message of bsig.h.
  *
@@ -34,6 +34,39 @@ typedef struct bsig_f64_hyper {
   double eps_noise, min_weight, ll_limit;
   double rff_scale;
 } bsig_f64_hyper;
+
+/* ------------------------------------------------------------------ */
+/* Trajectory summarizers in double: the fp32 entry points of bsig.h    */
+/* with double pointers -- same argument lists, same row layouts, same  */
+/* widths (the shared width function of bsig.h), ld_out in doubles.     */
+/* states [N,T,sd], actions [N,Ta,ad] contiguous doubles in, [N,ld_out] */
+/* double rows out: what the reference's torch ops give on double       */
+/* trajectories.  One workgroup per trajectory, at most                 */
+/* BSIG_F64_SUMMARY_GRID_CAP workgroups (they stride over the rest).    */
+/* ------------------------------------------------------------------ */
+#define BSIG_F64_SUMMARY_GRID_CAP 4096
+
+/* summary_start / summary_waypts, summarizers.py:65-87 after the crop / pad of :20-62 (a copy). */
+int bsig_summary_start_f64(const double* states, const double* actions, double* out, int64_t n,
+                           int t_states, int t_actions, int sd, int ad, int max_t, int64_t ld_out,
+                           bsig_stream_t stream);
+
+/* cross_correlation, summarizers.py:90-122: out[i*A + j] = sf[i] * af[j] -- ONE double multiply
+ * per element, the state features one subtraction (use_state_diff) or a copy -- then mean and
+ * unbiased std of the state features, two passes (:114-119), std = 0 for fewer than two features.
+ * `nonfinite` (int32, may be NULL) is OR-ed with 1 where the reference asserts isfinite (:120).
+ * BSIG_EUNSUPPORTED when the features of a row exceed a workgroup's LDS. */
+int bsig_crosscorr_f64(const double* states, const double* actions, double* out, int64_t n,
+                       int t_states, int t_actions, int sd, int ad, int use_state_diff,
+                       int64_t ld_out, int32_t* nonfinite, bsig_stream_t stream);
+
+/* summary_signatory, summarizers.py:144-168: the signature of [t | s | a], levels 1..depth
+ * (depth <= 0: the reference's choice, :133-141) by Chen's identity in double.  Depth 3 covers
+ * every path dimension the reference takes at depth 3 (d = 1 + sd + ad <= 22); a wider forced
+ * depth 3, or a path whose points, increments and d^3 level-3 terms exceed a workgroup's 160 KB
+ * of LDS, is BSIG_EUNSUPPORTED. */
+int bsig_signature_f64(const double* states, const double* actions, double* out, int64_t n,
+                       int length, int sd, int ad, int depth, int64_t ld_out, bsig_stream_t stream);
 
 /* ------------------------------------------------------------------ */
 /* fp64 MFMA GEMM with the epilogues of the fp32 GEMM of bsig.h: same  */
