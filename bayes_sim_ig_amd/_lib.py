@@ -1,4 +1,4 @@
-"""ctypes binding of libbsig_hip.so (include/bsig.h, include/bsig_f64.h).
+"""ctypes binding of libbsig_hip.so (include/bsig.h, include/bsig_f64.h, include/bsig_matmul.h).
 
 Whether a call computes in fp32 or fp64 is decided in ONE place, the two ``Precision`` objects ``F32`` and
 ``F64`` below: they carry the dtype, the sizes and the entry points that exist in both modes under one
@@ -27,6 +27,10 @@ ACT_TANH, ACT_RELU, ACT_LEAKY_RELU, ACT_SIGMOID, ACT_IDENTITY = range(5)
 MAX_HIDDEN = 8
 FIT_GRAPH, FIT_SPLIT_ADAM = 1, 2
 PLAN_NO_PERSISTENT = 1
+PLAN_SPLIT_BF16 = 2        # include/bsig_matmul.h
+MATMUL_FP32, MATMUL_SPLIT_BF16 = 0, 1
+MATMUL_PRECISIONS = {'float32': MATMUL_FP32, 'split_bf16': MATMUL_SPLIT_BF16}
+GEMM_PATH_SPLIT_BF16 = 10
 X_ROWS, X_CROSSCORR_FACTORS = 0, 1
 
 i64, i32, u64, f32, vp, sz = (C.c_int64, C.c_int32, C.c_uint64, C.c_float,
@@ -220,6 +224,13 @@ _PROTOS_F64 = {
     'bsig_fit64_run': (C.c_int, [vp, i64, vp]),
     'bsig_fit64_pack_logs': (C.c_int, [vp, i64, i64, vp, vp]),
 }
+# include/bsig_matmul.h: the matmul precision of the fp32 products
+_PROTOS_MATMUL = {
+    'bsig_gemm_f32_ex': (C.c_int, _PROTOS['bsig_gemm_f32'][1] + [C.c_int]),
+    'bsig_rff_project_ex': (C.c_int, _PROTOS['bsig_rff_project'][1] + [C.c_int]),
+    'bsig_debug_gemm_path': (C.c_int, [i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, sz, C.c_int,
+                                       C.POINTER(C.c_int32)]),
+}
 COMM_ID_BYTES = 128
 EXCHANGE_SUM, EXCHANGE_BROADCAST = 0, 1
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int, vp, i64, C.c_int, vp)
@@ -237,6 +248,25 @@ def exported_symbols_f64():
     return sorted(_PROTOS_F64)
 
 
+def exported_symbols_matmul():
+    """Names every declaration of include/bsig_matmul.h must resolve to."""
+    return sorted(_PROTOS_MATMUL)
+
+
+def matmul_precision(name):
+    """'float32' | 'split_bf16' -> BSIG_MATMUL_* (include/bsig_matmul.h); ValueError on anything else."""
+    if name not in MATMUL_PRECISIONS:
+        raise ValueError("matmul precision must be 'float32' or 'split_bf16', not %r" % (name,))
+    return MATMUL_PRECISIONS[name]
+
+
+def default_matmul_precision():
+    """The process default: the environment variable BSIG_MATMUL_PRECISION, else 'float32'."""
+    name = os.environ.get('BSIG_MATMUL_PRECISION') or 'float32'
+    matmul_precision(name)
+    return name
+
+
 def load():
     """Load the shared library (no GPU needed for loading)."""
     global _lib
@@ -246,7 +276,7 @@ def load():
                 'libbsig_hip.so not built (%s): run ./build.sh or '
                 '__graft_entry__.build(); there is no CPU fallback' % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(_PROTOS.items()) + list(_PROTOS_F64.items()):
+        for name, (res, args) in list(_PROTOS.items()) + list(_PROTOS_F64.items()) + list(_PROTOS_MATMUL.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _check_abi(lib)

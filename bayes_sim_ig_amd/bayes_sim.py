@@ -98,7 +98,15 @@ class BayesSim(object):
             raise ValueError("model_cfg['summaryDtype'] = 'float64' needs model_cfg['dtype'] = 'float64' "
                              "(an fp32 estimator would round the double summaries)")
         self._summary_dtype = torch.float64 if summary_dtype == 'float64' else None
+        matmul = model_cfg.get('matmulPrecision', None)
+        if matmul is not None and matmul not in ('float32', 'split_bf16'):
+            raise ValueError("model_cfg['matmulPrecision'] must be 'float32' or 'split_bf16', got %r" % (matmul,))
+        if matmul == 'split_bf16' and dtype == 'float64':
+            raise ValueError("model_cfg['matmulPrecision'] = 'split_bf16' applies to an fp32 estimator, "
+                             "not to model_cfg['dtype'] = 'float64'")
         self.model = _MODELS[model_class](**kwargs)
+        if matmul is not None:
+            self.model.set_matmul_precision(matmul)
         if dtype == 'float64':
             self.model.double()
 

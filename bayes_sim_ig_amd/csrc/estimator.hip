@@ -28,6 +28,7 @@
 // all-reduces it, then one flat Adam kernel runs (bsig_fit_grad / _apply).
 #include "comm.h"
 #include "gemm.h"
+#include "../../include/bsig_matmul.h"
 #include "head.h"
 #include "persist.h"
 #include "persist_mdnn.h"
@@ -98,6 +99,7 @@ struct Scratch {
   float* gemm_ws; size_t gemm_ws_bytes;
   float* colsum_ws; size_t colsum_ws_bytes;
   size_t total_bytes;
+  int math;                         // matmul precision of every product issued on this scratch (gemm.h; a plan's: plan_mem)
 };
 
 constexpr int kWideTickets = 1024;
@@ -121,6 +123,7 @@ static size_t gemm_ws_need(const bsig_mdn_cfg* c, const Layout& L, int64_t B) {
 
 static void carve(const bsig_mdn_cfg* c, const Layout& L, int64_t B, void* base, Scratch* s) {
   size_t off = 0;
+  s->math = BSIG_MATMUL_FP32;
   auto take = [&](size_t floats) {
     float* p = base ? reinterpret_cast<float*>(reinterpret_cast<char*>(base) + off) : nullptr;
     off += round_up<size_t>(floats * sizeof(float), 256);
@@ -184,7 +187,7 @@ static void set_src_b_kmajor(GemmParams& g, const float* x, int64_t ld, const In
 }
 
 static int rff_project(const bsig_mdn_cfg* c, const Inputs& in, int64_t rows, float* feats,
-                       void* ws, size_t ws_bytes, hipStream_t st) {
+                       void* ws, size_t ws_bytes, int math, hipStream_t st) {
   BSIG_REQUIRE(in.rff_coeff, "MDRFF needs rff_coeff");
   BSIG_REQUIRE(!(c->rff_cos_only && !in.rff_offset), "cos-only RFF needs an offset");
   GemmParams g;
@@ -193,7 +196,7 @@ static int rff_project(const bsig_mdn_cfg* c, const Inputs& in, int64_t rows, fl
   g.c = feats; g.ldc = c->rff_feats;
   g.m = (int)rows; g.n = c->rff_cos_only ? c->rff_feats : c->rff_feats / 2; g.k = c->input_dim;
   g.epilogue = c->rff_cos_only ? BSIG_EPI_COS_OFF : BSIG_EPI_COS_SIN;
-  g.bias = in.rff_offset; g.alpha = c->rff_scale;
+  g.bias = in.rff_offset; g.alpha = c->rff_scale; g.math = math;
   return gemm_run(g, ws, ws_bytes, st);
 }
 
@@ -203,7 +206,7 @@ static int forward_pass(const bsig_mdn_cfg* c, const Layout& L, const float* par
                         hipStream_t st, int* n_sig = nullptr) {
   const float* feat = in.x; int64_t ldf = in.ldx; const Inputs* src = &in;
   if (c->rff_feats > 0 && !in.is_feat) {
-    BSIG_TRY(rff_project(c, in, B, s.feat, s.gemm_ws, s.gemm_ws_bytes, st));
+    BSIG_TRY(rff_project(c, in, B, s.feat, s.gemm_ws, s.gemm_ws_bytes, s.math, st));
     feat = s.feat; ldf = c->rff_feats; src = nullptr;
   }
   for (int l = 0; l < L.n_layers; ++l) {
@@ -212,7 +215,7 @@ static int forward_pass(const bsig_mdn_cfg* c, const Layout& L, const float* par
     g.b = params + L.w_off[l]; g.ldb = L.in_dim[l];
     g.c = s.h[l]; g.ldc = c->hidden[l];
     g.m = (int)B; g.n = c->hidden[l]; g.k = (int)L.in_dim[l];
-    g.epilogue = BSIG_EPI_BIAS_ACT; g.act = c->activation; g.bias = params + L.b_off[l];
+    g.epilogue = BSIG_EPI_BIAS_ACT; g.act = c->activation; g.bias = params + L.b_off[l]; g.math = s.math;
     BSIG_TRY(gemm_run(g, s.gemm_ws, s.gemm_ws_bytes, st));
     feat = s.h[l]; ldf = c->hidden[l]; src = nullptr;
   }
@@ -221,7 +224,7 @@ static int forward_pass(const bsig_mdn_cfg* c, const Layout& L, const float* par
   g.b = params + L.head_w_off; g.ldb = L.feat_dim;
   g.c = o; g.ldc = ldo;
   g.m = (int)B; g.n = (int)L.nh; g.k = (int)L.feat_dim;
-  g.epilogue = BSIG_EPI_BIAS; g.bias = params + L.head_b_off;
+  g.epilogue = BSIG_EPI_BIAS; g.bias = params + L.head_b_off; g.math = s.math;
   if (o == s.o) { g.combine_tickets = s.tickets; g.combine_capacity = kWideTickets; }   // (the scratch buffer has the padded pitch the combine stores)
   if (n_sig && c->head.eps_noise != 0.f) {   // sum(exp(pre_diag)) partials for the jitter scale
     g.expsum = s.head_ws;
@@ -243,7 +246,7 @@ static int weight_grad(const float* dy, int64_t nout, int64_t ld_dy, const float
   GemmParams g;
   g.a = dy; g.lda = ld_dy; g.a_kmajor = 1;
   set_src_b_kmajor(g, xin, ldin, src, delta);
-  g.m = (int)nout; g.n = (int)nin; g.k = (int)B; g.ldc = nin;
+  g.m = (int)nout; g.n = (int)nin; g.k = (int)B; g.ldc = nin; g.math = s.math;
   if (fuse) {
     g.epilogue = EPI_ADAM;
     g.c = params + w_off; g.adam_m = fuse->m + w_off; g.adam_v = fuse->v + w_off;
@@ -278,7 +281,7 @@ static int backward_pass(const bsig_mdn_cfg* c, const Layout& L, float* params,
     g.b = params + L.head_w_off; g.ldb = L.feat_dim; g.b_kmajor = 1;
     g.c = s.dz[cur]; g.ldc = L.feat_dim;
     g.m = (int)B; g.n = (int)L.feat_dim; g.k = (int)L.nh;
-    g.epilogue = BSIG_EPI_MUL_DACT; g.act = c->activation; g.aux = feat; g.ldaux = ldf;
+    g.epilogue = BSIG_EPI_MUL_DACT; g.act = c->activation; g.aux = feat; g.ldaux = ldf; g.math = s.math;
     BSIG_TRY(gemm_run(g, s.gemm_ws, s.gemm_ws_bytes, st));
   }
   // heads: dW = dO^T feat (bias gradient = column sums of dO, from the finish kernel)
@@ -297,7 +300,7 @@ static int backward_pass(const bsig_mdn_cfg* c, const Layout& L, float* params,
       g.b = params + L.w_off[l]; g.ldb = L.in_dim[l]; g.b_kmajor = 1;
       g.c = s.dz[cur ^ 1]; g.ldc = L.in_dim[l];
       g.m = (int)B; g.n = (int)L.in_dim[l]; g.k = (int)hw;
-      g.epilogue = BSIG_EPI_MUL_DACT; g.act = c->activation; g.aux = xin; g.ldaux = ldin;
+      g.epilogue = BSIG_EPI_MUL_DACT; g.act = c->activation; g.aux = xin; g.ldaux = ldin; g.math = s.math;
       BSIG_TRY(gemm_run(g, s.gemm_ws, s.gemm_ws_bytes, st));
     }
     BSIG_TRY(weight_grad(s.dz[cur], hw, hw, xin, ldin, xsrc, delta, L.in_dim[l], B, params, grads,
@@ -384,6 +387,7 @@ struct bsig_fit_plan {
   int64_t norm_batch;
   size_t train_ws_bytes, test_ws_bytes, feats_bytes, big_gemm_ws_bytes, iota_bytes;
   bool use_graph, split_adam;
+  int matmul;                  // BSIG_PLAN_SPLIT_BF16: the matmul precision of every gemm_run product of this plan
 
   PersistEngine eng;           // the persistent update engine resolved at creation (persist.h) ...
   UGeom ug; MdnnGeom mg;       // ... its geometry (linear heads / two-layer MDNN)
@@ -451,6 +455,7 @@ static void plan_mem(const bsig_fit_plan* p, PlanMem* m) {
   m->iota = reinterpret_cast<int32_t*>(base); base += p->iota_bytes;
   m->persist_ws = base;
   if (!tickets_zeroed(p)) m->tr.tickets = m->te.tickets = nullptr;
+  m->tr.math = m->te.math = p->matmul;
 }
 
 static PersistShape persist_shape(const bsig_fit_plan* p) {
@@ -629,12 +634,12 @@ static int enqueue_hoisted_rff(bsig_fit_plan* p, hipStream_t st) {
   // 512 workgroups, two per CU, where 800 + 200 rows were 416 + 128 in two launches
   if (p->feat_unique && b.n_test > 0 && b.ldx_test == b.ldx_train &&
       b.x_test == b.x_train + (size_t)b.n_train * b.ldx_train)
-    return rff_project(&p->cfg, in, train_rows + b.n_test, m.feats, m.big_ws, p->big_gemm_ws_bytes, st);
-  BSIG_TRY(rff_project(&p->cfg, in, train_rows, m.feats, m.big_ws, p->big_gemm_ws_bytes, st));
+    return rff_project(&p->cfg, in, train_rows + b.n_test, m.feats, m.big_ws, p->big_gemm_ws_bytes, p->matmul, st);
+  BSIG_TRY(rff_project(&p->cfg, in, train_rows, m.feats, m.big_ws, p->big_gemm_ws_bytes, p->matmul, st));
   if (b.n_test > 0) {
     in.x = b.x_test; in.ldx = b.ldx_test; in.rows = nullptr;
     BSIG_TRY(rff_project(&p->cfg, in, b.n_test, m.feats + (size_t)train_rows * p->cfg.rff_feats,
-                         m.big_ws, p->big_gemm_ws_bytes, st));
+                         m.big_ws, p->big_gemm_ws_bytes, p->matmul, st));
   }
   return BSIG_OK;
 }
@@ -796,6 +801,7 @@ extern "C" int bsig_fit_create_ex(const bsig_mdn_cfg* cfg, int64_t batch,
   if (rc != BSIG_OK) { delete p; return rc; }
   p->batch = batch; p->max_test = max_test_rows; p->norm_batch = batch;
   p->n_updates = n_updates; p->n_evals = count_evals(n_updates);
+  p->matmul = (plan_flags & BSIG_PLAN_SPLIT_BF16) ? BSIG_MATMUL_SPLIT_BF16 : BSIG_MATMUL_FP32;
   Scratch s;
   carve(cfg, p->L, batch, nullptr, &s); p->train_ws_bytes = s.total_bytes;
   carve(cfg, p->L, std::max<int64_t>(max_test_rows, 1), nullptr, &s);

@@ -15,6 +15,9 @@ struct GemmParams {
   float* c = nullptr; int64_t ldc = 0;
   int m = 0, n = 0, k = 0, k_chunk = 0, splits = 1;
   int epilogue = BSIG_EPI_NONE, act = 0;
+  // matmul precision (include/bsig_matmul.h): 0 = the fp32 MFMAs; BSIG_MATMUL_SPLIT_BF16 PERMITS the
+  // split-bf16 kernel (gemm_split_bf16.hip) where it covers the call -- else the call runs as with 0
+  int math = 0;
   const float* bias = nullptr; const float* aux = nullptr; int64_t ldaux = 0; float alpha = 1.f;
   float* partial = nullptr;
   int64_t partial_ld = 0, partial_slab = 0;   // split-K slabs with a row pitch (0: dense [m, n])

@@ -21,6 +21,8 @@
 #include <cstdlib>
 #include "gemm_kernel.h"
 #include "gemm_lean.h"
+#include "gemm_split_bf16.h"
+#include "../../include/bsig_matmul.h"
 #include "gemm_wide.h"
 
 namespace bsig {
@@ -325,6 +327,19 @@ bool gemm_wide_gradient_applies(int64_t m, int64_t n, int64_t k, int64_t lda, in
          lda == ceil_div<int64_t>(m, 16) * 16 && n % 64 == 0 && pick_vec(a, lda) == 4 && pick_vec(b, ldb) == 4;
 }
 
+// The one class of shapes the split-bf16 mode leaves on the fp32 kernels (profiles/split_bf16_NOTES.md): the
+// two head products of a LARGE minibatch -- a few-hundred-wide head the whole-width kernels are built for,
+// against thousands of rows.  Measured at 8192 x 260 x 4096: the split kernel's 64 x 64 tiles spend more
+// vector-ALU time on splitting the operands than the whole-width fp32 kernels spend on their MFMAs
+// (forward 255 us against 168, gradient 344 against 162).  bsig_debug_gemm_path reports the rule (out[6] = 2).
+// (BSIG_SPLIT_BF16_EVERYWHERE=1 switches the rule off: tools/split_bf16_timing.py measures what it rests on)
+static bool split_bf16_leaves_to_fp32(int64_t m, int64_t n, int64_t k, bool akm, bool bkm) {
+  if (env_int("BSIG_SPLIT_BF16_EVERYWHERE", 0)) return false;
+  if (!akm && !bkm) return m >= 4096 && k >= 1024 && gemm_wide_covers((int)n);
+  if (akm && bkm) return k >= 4096 && n >= 1024 && gemm_wide_covers((int)m);
+  return false;
+}
+
 int gemm_run(GemmParams p, void* workspace, size_t workspace_bytes, hipStream_t st,
              int* n_expsum) {
   BSIG_REQUIRE(p.a && p.b && p.c, "gemm: null pointer");
@@ -350,6 +365,26 @@ int gemm_run(GemmParams p, void* workspace, size_t workspace_bytes, hipStream_t 
       hipLaunchKernelGGL(gemm_f64acc_kernel, dim3(blocks), dim3(256), 0, st, p);
       BSIG_CHECK_LAUNCH("gemm_f64acc");
       if (n_expsum && p.expsum) *n_expsum = blocks;
+      return BSIG_OK;
+    }
+  }
+  // The opt-in matmul precision (include/bsig_matmul.h): the split-bf16 kernel wherever it covers the
+  // call -- every operand form; a fused Adam step needs room for its slabs.  No size threshold; one
+  // measured class of shapes stays on the fp32 kernels (split_bf16_leaves_to_fp32).
+  if (p.math == BSIG_MATMUL_SPLIT_BF16 && !split_bf16_leaves_to_fp32(p.m, p.n, p.k, p.a_kmajor != 0, p.b_kmajor != 0)) {
+    SplitBf16Plan sp;
+    // (an unsplit launch writes one exp partial per workgroup; the reduce at most 2048: a product of more
+    // tiles than that with the side output and no K slices -- a head on a narrow trunk over tens of
+    // thousands of rows -- keeps the fp32 kernels, whose planner the callers' partial arrays are sized for)
+    if (split_bf16_plan(p.m, p.n, p.k, p.epilogue, p.bias_g_n > 1, workspace ? workspace_bytes : 0, &sp) &&
+        !(p.expsum && !sp.slabs && sp.workgroups > 2048)) {
+      static const int xcd = [] { const char* e = getenv("BSIG_GEMM_XCD"); return e ? atoi(e) : 1; }();
+      p.xcd_swz = xcd;
+      p.splits = sp.splits; p.k_chunk = sp.k_chunk;
+      p.partial = reinterpret_cast<float*>(workspace);
+      BSIG_TRY(launch_split_bf16(p, sp, st));
+      if (sp.slabs) return launch_reduce(p, st, n_expsum);
+      if (n_expsum && p.expsum) *n_expsum = ceil_div(p.m, sp.tile) * ceil_div(p.n, sp.tile);
       return BSIG_OK;
     }
   }
@@ -489,7 +524,8 @@ int gemm_f32(const float* a, int64_t lda, int a_kmajor, const int32_t* a_rows,
              const float* b, int64_t ldb, int b_kmajor, const int32_t* b_rows, float* c,
              int64_t ldc, int64_t m, int64_t n, int64_t k, int epilogue, int act,
              const float* bias, const float* aux, int64_t ldaux, float alpha,
-             void* workspace, size_t workspace_bytes, hipStream_t st) {
+             void* workspace, size_t workspace_bytes, hipStream_t st, int math = 0) {
+  BSIG_REQUIRE(math == BSIG_MATMUL_FP32 || math == BSIG_MATMUL_SPLIT_BF16, "gemm: unknown matmul precision %d", math);
   BSIG_REQUIRE(m >= 0 && n >= 0 && k >= 0 && m < (1 << 30) && n < (1 << 30) && k < (1 << 30),
                "gemm: bad dims");
   BSIG_REQUIRE(epilogue >= BSIG_EPI_NONE && epilogue <= BSIG_EPI_MUL_DACT, "gemm: bad epilogue");
@@ -499,7 +535,7 @@ int gemm_f32(const float* a, int64_t lda, int a_kmajor, const int32_t* a_rows,
   p.c = c; p.ldc = ldc;
   p.m = (int)m; p.n = (int)n; p.k = (int)k;
   p.epilogue = epilogue; p.act = act; p.bias = bias; p.aux = aux; p.ldaux = ldaux;
-  p.alpha = alpha;
+  p.alpha = alpha; p.math = math;
   return gemm_run(p, workspace, workspace_bytes, st);
 }
 
@@ -567,4 +603,94 @@ extern "C" int bsig_rff_project(const float* x, int64_t ldx, const int32_t* x_ro
   return gemm_f32(x, ldx, 0, x_rows, coeff, ld_coeff, 0, nullptr, feats, ld_feats, batch,
                   m_feat, in_dim, cos_only ? BSIG_EPI_COS_OFF : BSIG_EPI_COS_SIN, 0, offset,
                   nullptr, 0, a, workspace, workspace_bytes, as_stream(stream));
+}
+
+// ---- include/bsig_matmul.h
+extern "C" int bsig_gemm_f32_ex(const float* a, int64_t lda, int a_kmajor,
+                                const int32_t* a_rows, const float* b, int64_t ldb,
+                                int b_kmajor, const int32_t* b_rows, float* c, int64_t ldc,
+                                int64_t m, int64_t n, int64_t k, int epilogue, int act,
+                                const float* bias, const float* aux, int64_t ldaux, float alpha,
+                                void* workspace, size_t workspace_bytes, bsig_stream_t stream, int matmul) {
+  return gemm_f32(a, lda, a_kmajor, a_rows, b, ldb, b_kmajor, b_rows, c, ldc, m, n, k,
+                  epilogue, act, bias, aux, ldaux, alpha, workspace, workspace_bytes,
+                  as_stream(stream), matmul);
+}
+
+extern "C" int bsig_rff_project_ex(const float* x, int64_t ldx, const int32_t* x_rows,
+                                   const float* coeff, int64_t ld_coeff, const float* offset,
+                                   float* feats, int64_t ld_feats, int64_t batch,
+                                   int64_t in_dim, int64_t m_feat, float a, int cos_only,
+                                   void* workspace, size_t workspace_bytes,
+                                   bsig_stream_t stream, int matmul) {
+  bsig::Range roctx_range("bsig_rff_project");
+  BSIG_REQUIRE(!(cos_only && !offset), "rff_project: cos-only features need an offset");
+  return gemm_f32(x, ldx, 0, x_rows, coeff, ld_coeff, 0, nullptr, feats, ld_feats, batch,
+                  m_feat, in_dim, cos_only ? BSIG_EPI_COS_OFF : BSIG_EPI_COS_SIN, 0, offset,
+                  nullptr, 0, a, workspace, workspace_bytes, as_stream(stream), matmul);
+}
+
+// gemm_run's routing as host arithmetic (no pointers: operands taken as dense and 16-byte aligned,
+// A [m, k] or k-major [k, ceil16(m)], B [n, k] or k-major [k, n]; the environment switches as gemm_run reads them)
+extern "C" int bsig_debug_gemm_path(int64_t m, int64_t n, int64_t k, int a_kmajor, int b_kmajor,
+                                    int gathered, int epilogue, size_t workspace_bytes, int matmul,
+                                    int32_t* out) {
+  BSIG_REQUIRE(out, "gemm path: null pointer");
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  BSIG_REQUIRE(m >= 1 && n >= 1 && k >= 0 && m < (1 << 30) && n < (1 << 30) && k < (1 << 30), "gemm path: bad dims");
+  BSIG_REQUIRE((epilogue >= BSIG_EPI_NONE && epilogue <= BSIG_EPI_MUL_DACT) || epilogue == EPI_ADAM,
+               "gemm path: bad epilogue %d", epilogue);
+  BSIG_REQUIRE(matmul == BSIG_MATMUL_FP32 || matmul == BSIG_MATMUL_SPLIT_BF16,
+               "gemm path: unknown matmul precision %d", matmul);
+  auto put = [&](int kernel, int tm, int tn, int splits, int k_chunk, int64_t wgs) {
+    out[0] = kernel; out[1] = tm; out[2] = tn; out[3] = splits; out[4] = k_chunk;
+    out[5] = (int32_t)std::min<int64_t>(wgs, INT32_MAX);
+    return BSIG_OK;
+  };
+  const int f64_min_k = env_int("BSIG_DEBUG_F64_ACC_MIN_K", 0);
+  if (f64_min_k > 0 && k >= f64_min_k)
+    return put(GEMM_PATH_F64ACC, 0, 0, 1, (int)k, std::min<int64_t>(ceil_div<int64_t>(m * n, 256), 2048));
+  if (matmul == BSIG_MATMUL_SPLIT_BF16 && split_bf16_leaves_to_fp32(m, n, k, a_kmajor != 0, b_kmajor != 0)) {
+    out[6] = 2;   // the large-minibatch head products stay on the fp32 kernels (measured slower)
+  } else if (matmul == BSIG_MATMUL_SPLIT_BF16) {
+    SplitBf16Plan sp;
+    if (split_bf16_plan(m, n, k, epilogue, false, workspace_bytes, &sp))
+      return put(GEMM_PATH_SPLIT_BF16, sp.tile, sp.tile, sp.splits, sp.k_chunk, sp.workgroups);
+    out[6] = 1;   // the mode was asked for and the kernel does not cover the call
+  }
+  if (env_int("BSIG_GEMM_WIDE", 1) && workspace_bytes > 0 && k >= 1024 && k % BK == 0) {
+    auto slices = [&](int64_t tiles, int64_t slab_floats) {   // (gemm_run's `split`)
+      const int64_t smax = std::min<int64_t>(std::min<int64_t>(8, std::max<int64_t>(k / (8 * BK), 1)),
+                                             (int64_t)(workspace_bytes / (sizeof(float) * (size_t)slab_floats)));
+      int64_t s = 0;
+      double best = 1e30;
+      for (int64_t c = 1; c <= smax; ++c) {
+        const double cost = (double)ceil_div<int64_t>(tiles * c, 256) / (double)c + 0.02 * (double)c;
+        if (cost < best - 1e-9) { best = cost; s = c; }
+      }
+      return s;
+    };
+    if (!a_kmajor && !b_kmajor && m >= 2048 && gemm_wide_covers((int)n) && k % 4 == 0 &&
+        (epilogue == BSIG_EPI_NONE || epilogue == BSIG_EPI_BIAS)) {
+      const int64_t s = slices(ceil_div<int64_t>(m, 64), m * round_up<int64_t>(n, 16));
+      if (s >= 1) {
+        const int64_t chunk = round_up<int64_t>(ceil_div<int64_t>(k, s), BK);
+        return put(GEMM_PATH_WIDE_FORWARD, 64, (int)round_up<int64_t>(n, 16), (int)ceil_div<int64_t>(k, chunk),
+                   (int)chunk, ceil_div<int64_t>(m, 64) * ceil_div<int64_t>(k, chunk));
+      }
+    } else if (a_kmajor && b_kmajor && gathered && k >= 2048 && gemm_wide_covers((int)m) && n % 64 == 0) {
+      const int64_t s = slices(n / 64, m * n);
+      if (s >= 1) {
+        const int64_t chunk = round_up<int64_t>(ceil_div<int64_t>(k, s), BK);
+        return put(GEMM_PATH_WIDE_GRADIENT, (int)round_up<int64_t>(m, 16), 64, (int)ceil_div<int64_t>(k, chunk),
+                   (int)chunk, (n / 64) * ceil_div<int64_t>(k, chunk));
+      }
+    }
+  }
+  const bool lean_ok = (a_kmajor ? round_up<int64_t>(m, 16) : k) % 4 == 0 && (b_kmajor ? n : k) % 4 == 0;
+  const GemmPlan pl = plan_gemm(m, n, k, workspace_bytes, lean_ok);
+  const int t = pl.tile % N_TILES;
+  const bool lean = env_int("BSIG_GEMM_LEAN", 1) && lean_ok && t <= TILE_96x128;
+  return put(lean ? GEMM_PATH_LEAN : GEMM_PATH_MFMA, kTileM[t], kTileN[t], pl.splits, pl.k_chunk,
+             ceil_div<int64_t>(m, kTileM[t]) * ceil_div<int64_t>(n, kTileN[t]) * pl.splits);
 }

@@ -13,6 +13,11 @@ from a HIP graph (csrc/estimator.hip).  There is no CPU fallback.
 buffers become float64 -- the reference under ``torch.set_default_dtype(torch.float64)``;
 ``model.float()`` goes back.  Every entry point below is written once: which library functions, struct
 and sizes it uses comes from ``self._prec``, one of ``_lib.F32`` / ``_lib.F64``, and nowhere else.
+
+``model.set_matmul_precision('split_bf16')`` (include/bsig_matmul.h; the process default comes from the
+environment variable BSIG_MATMUL_PRECISION, read when a model is constructed) lets the fit plan's products
+run on the bf16 matrix pipes with every fp32 operand split into three bf16 pieces: fp32-grade results that
+are not bitwise the reference's fp32 arithmetic.  The default, 'float32', is.
 """
 import contextlib
 import ctypes as C
@@ -125,6 +130,8 @@ class MDNN(nn.Module):
     _dtype = torch.float32   # torch.float64 after .double(): the fp64 mode
     _plan = None         # (a model whose construction failed is still finalised: __del__)
     _plan_prec = None    # the _lib.Precision that created _plan: the one that may destroy it
+    _matmul = 'float32'  # matmul precision of the fit plan's products (set_matmul_precision)
+    _matmul_set = False  # ... chosen by set_matmul_precision (else: the process default of BSIG_MATMUL_PRECISION)
 
     def __init__(self, input_dim, output_dim, output_lows, output_highs,
                  n_gaussians, full_covariance, hidden_layers, activation, lr,
@@ -184,6 +191,7 @@ class MDNN(nn.Module):
         self._no_persistent = False
         self._no_block_launch = False
         self._block_launches = 0
+        self._matmul = _lib.default_matmul_precision()      # (BSIG_MATMUL_PRECISION; ValueError on a bad value)
         self._flatten(device)
 
     # ------------------------------------------------------------ plumbing
@@ -261,6 +269,16 @@ class MDNN(nn.Module):
         self._drop_plan()
 
     def _apply(self, fn, *args, **kwargs):
+        if self._matmul != 'float32' and fn(torch.empty(0, dtype=self._dtype)).dtype == torch.float64:
+            if not self._matmul_set:
+                # the process default is for fp32 models: a model that goes double leaves it behind
+                self._matmul = 'float32'
+                if self.rff is not None:
+                    self.rff.matmul_precision = 'float32'
+        if self._matmul != 'float32' and fn(torch.empty(0, dtype=self._dtype)).dtype == torch.float64:
+            # refuse BEFORE converting: the model stays as it was
+            raise ValueError("a model set to matmul precision %r cannot become double: the fp64 mode has one "
+                             "arithmetic; set_matmul_precision('float32') first" % (self._matmul,))
         if self._dp is not None:
             # refuse BEFORE converting: the model stays as it was
             if fn(torch.empty(0, dtype=self._dtype)).dtype == torch.float64:
@@ -280,6 +298,37 @@ class MDNN(nn.Module):
     def _prec(self):
         """The precision seam (_lib.Precision) of the model's dtype."""
         return _lib.F64 if self._f64 else _lib.F32
+
+    @property
+    def matmul_precision(self):
+        """'float32' or 'split_bf16': see set_matmul_precision."""
+        return self._matmul
+
+    def set_matmul_precision(self, name):
+        """'float32' (the default: the reference's fp32 arithmetic on the fp32 MFMAs, bit for bit) or
+        'split_bf16': every product of the fit plan -- ``run_training`` / ``fit``: forward and backward
+        passes, weight gradients with the fused Adam step, the feature cache and the held-out evaluations
+        -- may run on the bf16 matrix pipes, each fp32 operand element split into three bf16 pieces and six
+        of the nine piece products kept (include/bsig_matmul.h).  fp32-grade (the error against the fp64
+        product is about that of an fp32 chain) and bitwise reproducible, but not bitwise the 'float32'
+        results.  A plan that a persistent update kernel covers keeps that kernel, which computes in fp32.
+        An MDRFF's ``rff`` follows its model in every projection it makes (``to_features``, the block
+        pre-projection of ``BayesSim.fit``, ``predict_MoGs``).  ``forward``, ``loss_and_grad`` and the head
+        products of ``predict_MoGs`` take no plan: they stay fp32.
+        Edge behaviour of 'split_bf16': a non-finite operand element gives non-finite outputs (NaN where
+        fp32 gives inf); |x| above the largest bf16 (3.39e38) becomes inf; an element below 2^-100 in
+        magnitude may carry fewer than 24 bits.
+        Drops the plan.  ValueError on any other value, and on a double model; ``.double()`` on a model SET
+        to 'split_bf16' raises too (one that only took the process default goes back to 'float32')."""
+        _lib.matmul_precision(name)
+        if name != 'float32' and self._f64:
+            raise ValueError('a double model has one arithmetic (include/bsig_f64.h): matmul precision %r '
+                             'applies to fp32 models only' % (name,))
+        self._matmul, self._matmul_set = name, True
+        if self.rff is not None:
+            self.rff.matmul_precision = name
+        self._drop_plan()
+        return self
 
     @staticmethod
     def _f64_dp_error():
@@ -406,16 +455,20 @@ class MDNN(nn.Module):
 
     # ----------------------------------------------------------- forward
     @_on_model_device
-    def _head_forward(self, x):
+    def _head_forward(self, x, is_feat=False):
+        """The raw head outputs of rows ``x`` -- or, with ``is_feat``, of an MDRFF's already projected
+        feature rows (the heads are a linear-head estimator over them: same parameter layout)."""
         lib, prec = self._gpu(), self._prec
         cfg = self._cfg()
+        if is_feat:
+            cfg.input_dim, cfg.rff_feats = self._rff_feats, 0
         xs, ldx = _lib.as_rows(x, self._flat.device, prec.dtype)
-        assert xs.shape[1] == self.input_dim
+        assert xs.shape[1] == cfg.input_dim
         b = xs.shape[0]
         nh = int(lib.bsig_head_width(C.byref(cfg.head)))
         out = torch.empty((b, nh), dtype=prec.dtype, device=xs.device)
         ws = self._buf('fwd_ws', int(prec.mdn_workspace_bytes(C.byref(cfg), b)) // prec.itemsize + 1)
-        coeff, ldc, off = self._rff_args()
+        coeff, ldc, off = (None, 0, None) if is_feat else self._rff_args()
         prec.head_forward(
             C.byref(cfg), C.byref(self._hyper()), _lib.ptr(self._flat), _lib.ptr(coeff), ldc, _lib.ptr(off),
             _lib.ptr(xs), ldx, None, b, _lib.ptr(out), nh, _lib.ptr(ws),
@@ -423,12 +476,13 @@ class MDNN(nn.Module):
         return cfg, out
 
     @_on_model_device
-    def forward(self, x, noise=None):
+    def forward(self, x, noise=None, _is_feat=False):
         """Reference mdnn.py:89-125 -> (weights[B,K], mu[B,D,K], L_d[B,D,K],
-        L[B,L_size,K] | None).  ``noise`` injects the rand_like draw."""
+        L[B,L_size,K] | None).  ``noise`` injects the rand_like draw.  Takes no plan: its products
+        are fp32 whatever the model's matmul precision."""
         self._gpu()
         prec = self._prec
-        cfg, out = self._head_forward(x)
+        cfg, out = self._head_forward(x, _is_feat)
         b, d, k = out.shape[0], self.output_dim, self.n_gaussians
         dev, dt = out.device, self._dtype
         weights = torch.empty((b, k), dtype=dt, device=dev)
@@ -447,7 +501,7 @@ class MDNN(nn.Module):
             _lib.ptr(low), _lib.ptr(flag), _lib.ptr(ws), ws.numel() * prec.itemsize, _lib.stream())
         assert int(flag.item()) == 0      # isfinite asserts, mdnn.py:120-124
         # remembered so that mdn_loss_fn(*model(x), y).backward() works (below)
-        self._fwd_ctx = (weights, x, nz, seed) if torch.is_grad_enabled() else None
+        self._fwd_ctx = (weights, x, nz, seed) if torch.is_grad_enabled() and not _is_feat else None
         return weights, mu, l_d, low
 
     @_on_model_device
@@ -564,12 +618,14 @@ class MDNN(nn.Module):
         prec = self._prec
         key = (batch_size, max(n_test, self._bufs.get('cap_test', 0)), n_updates,
                cfg.head.eps_noise, cfg.lr, cfg.head.min_weight, cfg.head.ll_limit,
-               max(n_train, self._bufs.get('cap_train', 0)), prec.dtype)
+               max(n_train, self._bufs.get('cap_train', 0)), prec.dtype, self._matmul)
         if self._plan is None or self._plan_key != key:
             self._drop_plan(bufs=False)
             # (a model that met a persistent-launch time-out stays on the per-phase kernels: a plan
             # option, not the process-wide environment switch)
             flags = _lib.PLAN_NO_PERSISTENT if self._no_persistent else 0
+            if self._matmul == 'split_bf16':
+                flags |= _lib.PLAN_SPLIT_BF16
             self._plan = prec.fit_create(C.byref(cfg), C.byref(self._hyper()), batch_size, key[7], key[1],
                                          n_updates, flags)
             self._plan_key, self._plan_prec = key, prec
@@ -843,7 +899,11 @@ class MDNN(nn.Module):
         full-covariance row indexing bug of mdnn.py:281 (``L[:, :, comp_id]``
         instead of ``L[pt, :, comp_id]``) is not reproduced."""
         ntest, dim = xs.size()
-        w, mu, l_d, low = self.forward(xs, noise=noise)
+        if self.rff is not None and self._matmul != 'float32':
+            # the projection follows the model's matmul precision; the head products stay fp32
+            w, mu, l_d, low = self.forward(self.rff.to_features(xs), noise=noise, _is_feat=True)
+        else:
+            w, mu, l_d, low = self.forward(xs, noise=noise)
         w, mu, l_d = w.cpu().numpy(), mu.cpu().numpy(), l_d.cpu().numpy()
         low = None if low is None else low.cpu().numpy()
         normalize = self.output_lows is not None

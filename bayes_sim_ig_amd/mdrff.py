@@ -31,6 +31,7 @@ class MDRFF(MDNN):
                        quasi_random=False if input_dim > 100 else True,
                        kernel=kernel, device=device, freqs=freqs)
         self._rff_scale = float(self.rff.a)
+        self.rff.matmul_precision = self._matmul     # the feature map follows its model (set_matmul_precision)
         if MDNN.VERBOSE:
             print('MDRFF n_feat', n_feat, 'sigma', sigma)
             print(self)

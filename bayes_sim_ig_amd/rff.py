@@ -97,6 +97,8 @@ class RFF:
             self.to_features = self._to_cos_sin_features
         self.freqs = torch.from_numpy(np.asarray(f)).float().to(device)
         self._coeff = None       # freqs / sigma, [m, ld] device, built lazily
+        # 'float32' | 'split_bf16' (include/bsig_matmul.h): an MDRFF's feature map follows its model
+        self.matmul_precision = 'float32'
         self._ws = None
 
     # -- device-side state -------------------------------------------------
@@ -134,11 +136,14 @@ class RFF:
             self._ws = torch.empty(max(need // 4 + 1, 1), dtype=torch.float32,
                                    device=co.device)
         off = self.offset.to(co.device).contiguous() if cos_only else None
-        _lib.check(lib.bsig_rff_project(
-            _lib.ptr(xs), ldx, None, _lib.ptr(co), co.stride(0), _lib.ptr(off),
-            _lib.ptr(feats), feats.stride(0), b, self.d, self.m_feat,
-            float(self.a), 1 if cos_only else 0, _lib.ptr(self._ws),
-            self._ws.numel() * 4, _lib.stream()))
+        args = (_lib.ptr(xs), ldx, None, _lib.ptr(co), co.stride(0), _lib.ptr(off),
+                _lib.ptr(feats), feats.stride(0), b, self.d, self.m_feat,
+                float(self.a), 1 if cos_only else 0, _lib.ptr(self._ws),
+                self._ws.numel() * 4, _lib.stream())
+        if self.matmul_precision == 'float32':
+            _lib.check(lib.bsig_rff_project(*args))
+        else:
+            _lib.check(lib.bsig_rff_project_ex(*args, _lib.matmul_precision(self.matmul_precision)))
         return feats if home == feats.device else feats.to(home)
 
     def _to_cos_only_features(self, x, sigma=None):

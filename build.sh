@@ -1,6 +1,6 @@
 #!/usr/bin/env bash
 # Build libbsig_hip.so (gfx950) in-tree.  hipcc cross-compiles without a GPU.
-# An object is rebuilt when the CONTENT of its source, of any csrc header, of include/bsig.h or the
+# An object is rebuilt when the CONTENT of its source, of any csrc header, of include/bsig.h, include/bsig_matmul.h or the
 # flags changed (a stamp next to the object; file times do not survive every transport).
 set -euo pipefail
 cd "$(dirname "$0")"
@@ -19,7 +19,7 @@ FLAGS="${BSIG_EXTRA_FLAGS:-} --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -W
 # compile time each) are built on request only: BSIG_BUILD_WIDE_TILES=1 ./build.sh, then BSIG_GEMM_WIDE_TILE=1
 WIDE_TILES=""
 if [ "${BSIG_BUILD_WIDE_TILES:-0}" = "1" ]; then FLAGS="$FLAGS -DBSIG_WITH_WIDE_TILES"; WIDE_TILES="gemm_tile_128x288 gemm_tile_288x128"; fi
-COMMON=$(cat "$SRC"/*.h include/bsig.h | sha256sum | cut -d' ' -f1)
+COMMON=$(cat "$SRC"/*.h include/bsig.h include/bsig_matmul.h | sha256sum | cut -d' ' -f1)
 # the fp64 mode (csrc/f64/, include/bsig_f64.h): its objects' stamps cover its own headers too
 COMMON64=$(cat "$SRC"/f64/*.h include/bsig_f64.h | sha256sum | cut -d' ' -f1)
 pids=()
@@ -33,7 +33,7 @@ build_one() {  # name, source, extra flags[, hash of further headers the source 
 }
 [ -n "$WIDE_TILES" ] || rm -f "$OUT"/obj/gemm_tile_128x288.* "$OUT"/obj/gemm_tile_288x128.*
 rm -f "$OUT"/obj/fit_persistent_v1.*      # (retired in round 6: an object of an older build must not be linked)
-for f in summarizers gemm_f32 gemm_tile_64 gemm_tile_128 gemm_tile_128x32 gemm_tile_128x64 gemm_tile_128x96 gemm_tile_96x128 gemm_lean_64 gemm_lean_128 gemm_lean_128x32 gemm_lean_128x64 gemm_lean_128x96 gemm_lean_96x128 gemm_wide $WIDE_TILES mdn_head flat_ops estimator fit_persistent fit_persistent_mdnn fit_persistent_mdnn_stream; do
+for f in summarizers gemm_f32 gemm_tile_64 gemm_tile_128 gemm_tile_128x32 gemm_tile_128x64 gemm_tile_128x96 gemm_tile_96x128 gemm_lean_64 gemm_lean_128 gemm_lean_128x32 gemm_lean_128x64 gemm_lean_128x96 gemm_lean_96x128 gemm_wide gemm_split_bf16 $WIDE_TILES mdn_head flat_ops estimator fit_persistent fit_persistent_mdnn fit_persistent_mdnn_stream; do
   build_one "$f" "$SRC/$f.hip" ""
 done
 for f in api comm; do
