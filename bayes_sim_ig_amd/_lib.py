@@ -1,4 +1,5 @@
-"""ctypes binding of libbsig_hip.so (include/bsig.h, include/bsig_f64.h, include/bsig_matmul.h).
+"""ctypes binding of libbsig_hip.so (include/bsig.h, include/bsig_f64.h, include/bsig_matmul.h,
+include/bsig_signature.h).
 
 Whether a call computes in fp32 or fp64 is decided in ONE place, the two ``Precision`` objects ``F32`` and
 ``F64`` below: they carry the dtype, the sizes and the entry points that exist in both modes under one
@@ -231,6 +232,14 @@ _PROTOS_MATMUL = {
     'bsig_debug_gemm_path': (C.c_int, [i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, sz, C.c_int,
                                        C.POINTER(C.c_int32)]),
 }
+# include/bsig_signature.h: signatures beyond depth 3 and on a chosen subset of channels
+SIGNATURE_MAX_DEPTH = 6
+_PROTOS_SIGNATURE = {
+    'bsig_signature_ex_dim': (i64, [C.c_int, C.c_int]),
+    'bsig_signature_ex_fits': (C.c_int, [C.c_int] * 4),
+    'bsig_signature_ex': (C.c_int, [vp, vp, vp, C.c_int, vp, i64] + [C.c_int] * 4 + [i64, vp]),
+    'bsig_signature_ex_f64': (C.c_int, [vp, vp, vp, C.c_int, vp, i64] + [C.c_int] * 4 + [i64, vp]),
+}
 COMM_ID_BYTES = 128
 EXCHANGE_SUM, EXCHANGE_BROADCAST = 0, 1
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int, vp, i64, C.c_int, vp)
@@ -251,6 +260,11 @@ def exported_symbols_f64():
 def exported_symbols_matmul():
     """Names every declaration of include/bsig_matmul.h must resolve to."""
     return sorted(_PROTOS_MATMUL)
+
+
+def exported_symbols_signature():
+    """Names every declaration of include/bsig_signature.h must resolve to."""
+    return sorted(_PROTOS_SIGNATURE)
 
 
 def matmul_precision(name):
@@ -276,7 +290,8 @@ def load():
                 'libbsig_hip.so not built (%s): run ./build.sh or '
                 '__graft_entry__.build(); there is no CPU fallback' % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(_PROTOS.items()) + list(_PROTOS_F64.items()) + list(_PROTOS_MATMUL.items()):
+        for name, (res, args) in (list(_PROTOS.items()) + list(_PROTOS_F64.items()) + list(_PROTOS_MATMUL.items()) +
+                                  list(_PROTOS_SIGNATURE.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _check_abi(lib)
@@ -360,6 +375,10 @@ class Precision:
         'normalize_rows': ('bsig_normalize_rows', 'bsig_normalize_rows_f64'),
         'copy_rows': ('bsig_copy_rows', 'bsig_copy_rows_f64'),
     }
+    # include/bsig_signature.h (the general signature kernel): resolved like OPS, from _PROTOS_SIGNATURE
+    SIGNATURE_OPS = {
+        'signature_ex': ('bsig_signature_ex', 'bsig_signature_ex_f64'),
+    }
     HYPER_OPS = ('head_forward', 'head_outputs', 'nll_from_tuple', 'loss_grad')    # take the hyper in fp64
     # the plan lifecycle
     FIT_OPS = {
@@ -390,8 +409,9 @@ class Precision:
         # fp32 replays an update from a HIP graph, so a call's rows are staged at fixed addresses; fp64
         # has no graphs: it binds the rows where they lie and is never asked for one (FIT_GRAPH)
         self.replays_graphs = self.itemsize == 4
-        self._protos = _PROTOS_F64 if self.itemsize == 8 else _PROTOS
-        for op in list(self.OPS) + list(self.FIT_OPS) + list(self.QUERIES):      # (a typo fails the import)
+        self._protos = dict(_PROTOS_F64 if self.itemsize == 8 else _PROTOS, **_PROTOS_SIGNATURE)
+        for op in (list(self.OPS) + list(self.SIGNATURE_OPS) + list(self.FIT_OPS) +
+                   list(self.QUERIES)):                                          # (a typo fails the import)
             assert self.symbol(op) is None or self.symbol(op) in self._protos, op
 
     def __repr__(self):
@@ -401,10 +421,10 @@ class Precision:
         """The library symbol behind ``op``; None where this precision answers without the library."""
         if op in self.QUERIES:
             return None if self.itemsize == 8 else self.QUERIES[op][0]
-        return (self.OPS.get(op) or self.FIT_OPS[op])[self.itemsize == 8]
+        return (self.OPS.get(op) or self.SIGNATURE_OPS.get(op) or self.FIT_OPS[op])[self.itemsize == 8]
 
     def __getattr__(self, op):       # the first use of an entry point
-        if op not in self.OPS and op not in self.FIT_OPS and op not in self.QUERIES:
+        if op not in self.OPS and op not in self.SIGNATURE_OPS and op not in self.FIT_OPS and op not in self.QUERIES:
             raise AttributeError(op)
         self._resolve()
         return vars(self)[op]
@@ -417,7 +437,7 @@ class Precision:
                 return lambda first, hyper, *rest: check(fn(first, *rest))
             return lambda *args: check(fn(*args))
 
-        for op in list(self.OPS) + list(self.FIT_OPS):
+        for op in list(self.OPS) + list(self.SIGNATURE_OPS) + list(self.FIT_OPS):
             name = self.symbol(op)
             fn = getattr(lib, name)
             if self._protos[name][0] is C.c_int:      # a return code (the others: a size, nothing)

@@ -13,6 +13,7 @@ import os
 import numpy as np
 import torch
 
+from . import _lib
 from . import pdf
 from . import summarizers as _summ
 from .mdnn import MDNN
@@ -47,7 +48,15 @@ class BayesSim(object):
                  params_highs, prior, proposal=None, device='cpu'):
         """Arguments as in the reference (bayes_sim.py:27-52).  Optional
         ``model_cfg`` keys beyond the reference's: ``nFeat`` (RFF features,
-        default 200 as hard-coded at bayes_sim.py:81), ``sigDepth``, ``dtype``
+        default 200 as hard-coded at bayes_sim.py:81), ``sigDepth`` (1..6: the
+        truncation depth of ``summary_signatory``; default: the reference's rule,
+        at most 3) and ``sigChannels`` (``summary_signatory`` only: the channels
+        of ``[states | actions]`` that make up the path after the time channel,
+        in any order -- index ``c < obs_dim`` is a state channel, any other action
+        channel ``c - obs_dim``; they are gathered by the kernel, the trajectories
+        are not sliced; ``input_dim`` follows from both keys, and a shape whose
+        levels do not fit a workgroup's LDS at ``trainTrajLen`` is a
+        NotImplementedError here, include/bsig_signature.h), ``dtype``
         ('float32', the default, or 'float64': the estimator's fp64 mode, as
         ``bs.model.double()``), ``summaryDtype`` ('float32', the default in both
         modes: the summaries are made in fp32 and a double model gets them
@@ -63,11 +72,27 @@ class BayesSim(object):
         self.summarizer_name = name
         self.summarizer_fxn = _SUMMARIZERS[name]
         self._sig_depth = model_cfg.get('sigDepth', None)
+        self._sig_channels = model_cfg.get('sigChannels', None)
+        if self._sig_depth is not None and not 1 <= self._sig_depth <= _lib.SIGNATURE_MAX_DEPTH:
+            raise ValueError("model_cfg['sigDepth'] must be in 1..%d, got %r"
+                             % (_lib.SIGNATURE_MAX_DEPTH, self._sig_depth))
+        if self._sig_channels is not None:
+            if name != 'summary_signatory':
+                raise ValueError("model_cfg['sigChannels'] applies to 'summary_signatory', not to %r" % name)
+            self._sig_channels = _summ.signature_channels(self._sig_channels, obs_dim, act_dim)
         # the reference pushes a zero trajectory through the summarizer to get
         # the width (bayes_sim.py:57-60); the width is a closed form
-        traj_summaries_dim = _summ.summary_dim(
-            name, model_cfg['trainTrajLen'], obs_dim, act_dim,
-            self._sig_depth or 0)
+        if name == 'summary_signatory' and (self._sig_channels is not None or (self._sig_depth or 0) > 3):
+            # include/bsig_signature.h: the general kernel; whether it covers the shape is host arithmetic
+            path_dim = 1 + (obs_dim + act_dim if self._sig_channels is None else len(self._sig_channels))
+            depth = self._sig_depth or _summ.signature_depth(path_dim)
+            traj_summaries_dim = _summ.signature_dim(path_dim, depth)
+            itemsize = 8 if model_cfg.get('summaryDtype', 'float32') == 'float64' else 4
+            _lib.check(_lib.load().bsig_signature_ex_fits(path_dim, model_cfg['trainTrajLen'], depth, itemsize))
+        else:
+            traj_summaries_dim = _summ.summary_dim(
+                name, model_cfg['trainTrajLen'], obs_dim, act_dim,
+                self._sig_depth or 0)
         full_covariance = bool(model_cfg.get('fullCovariance', False))
         kwargs = {'input_dim': traj_summaries_dim, 'output_dim': params_dim,
                   'output_lows': params_lows, 'output_highs': params_highs,
@@ -120,8 +145,9 @@ class BayesSim(object):
     def _summarize(self, states, actions, finite_flag=None, lazy=False):
         # ('summaryDtype': 'float64' -- the summarizers' fp64 kernels; else no keyword: the fp32 path)
         kw = {} if self._summary_dtype is None else {'dtype': self._summary_dtype}
-        if self.summarizer_name == 'summary_signatory' and self._sig_depth:
-            return self.summarizer_fxn(states, actions, depth=self._sig_depth, **kw)
+        if self.summarizer_name == 'summary_signatory' and (self._sig_depth or self._sig_channels is not None):
+            return self.summarizer_fxn(states, actions, depth=self._sig_depth or None,
+                                       channels=self._sig_channels, **kw)
         if self.summarizer_name in ('summary_corr', 'summary_corrdiff'):
             if finite_flag is not None:
                 # the isfinite assert of summarizers.py:120, deferred with the chunk's logs

@@ -570,6 +570,8 @@ static int grid_for(int64_t n) {
   return (int)(n < cap ? n : cap);
 }
 
+int summary_grid_for(int64_t n) { return grid_for(n); }   // (csrc/signature_ex.hip launches as many)
+
 static int ref_signature_depth(int64_t d) {  // summarizers.py:133-141
   for (int depth = 3; depth >= 0; --depth) {
     int64_t p = 1;

@@ -15,6 +15,7 @@ float64 input.  Which library entry point a call reaches is decided by the
 precision seam (``_lib.F32`` / ``_lib.F64``).
 """
 import ctypes as C
+import operator
 
 import torch
 
@@ -265,21 +266,82 @@ def signature_depth(ndim):
     return 1
 
 
-def summary_signatory(states, actions, depth=None, out=None, dtype=None):
+def signature_dim(path_dim, depth):
+    """Width of a signature row, ``sum(path_dim ** k for k in 1..depth)``, without touching the GPU
+    (bsig_signature_ex_dim, include/bsig_signature.h).  ValueError for ``path_dim < 2``, a depth outside
+    1..6 or a width past 2^31 - 1."""
+    width = int(_lib.load().bsig_signature_ex_dim(int(path_dim), int(depth)))
+    if width < 0:
+        raise ValueError('no signature row for path_dim=%r, depth=%r (path_dim >= 2, depth in 1..%d, width '
+                         'below 2^31)' % (path_dim, depth, _lib.SIGNATURE_MAX_DEPTH))
+    return width
+
+
+def signature_channels(channels, sd, ad):
+    """``channels`` of summary_signatory as a tuple of ints, checked on the host (the library cannot
+    range-check a device array): ValueError if it is empty, not integers, or out of ``[0, sd + ad)``."""
+    try:
+        picked = tuple(operator.index(c) for c in channels)
+    except TypeError:
+        raise ValueError('channels must be a sequence of ints, got %r' % (channels,)) from None
+    if not picked:
+        raise ValueError('channels is empty: pick at least one of the %d channels' % (sd + ad))
+    for c in picked:
+        if not 0 <= c < sd + ad:
+            raise ValueError('channel %d is out of [0, %d): %d state and %d action channels'
+                             % (c, sd + ad, sd, ad))
+    return picked
+
+
+_channel_vectors = {}      # (picked channels, device) -> their int32 vector on that device
+
+
+def _channel_vector(picked, device):
+    """The index vector of a channel list on ``device``: uploaded once per distinct list."""
+    key = (picked, str(device))
+    vec = _channel_vectors.get(key)
+    if vec is None:
+        vec = _channel_vectors[key] = torch.tensor(picked, dtype=torch.int32).to(device)
+    return vec
+
+
+def summary_signatory(states, actions, depth=None, out=None, dtype=None, channels=None):
     """Reference summarizers.py:144-168 with the signature computed by
     csrc/summarizers.hip instead of ``signatory``.  All N rows are returned
-    (the reference drops N % 10 rows when N > 10000)."""
+    (the reference drops N % 10 rows when N > 10000).
+
+    ``depth`` up to 6 and ``channels`` (include/bsig_signature.h): ``channels`` is a sequence of ints
+    that picks the path's columns after the time channel -- ``c < sd`` is ``states[..., c]``, any other
+    ``actions[..., c - sd]``; any order, repeats allowed -- so the path is ``[t | picked channels]`` and
+    the default depth is ``signature_depth(1 + len(channels))``.  The channels are gathered by the
+    kernel's loader: no sliced copy of the trajectories is made.  ``channels=None`` at depth <= 3 is the
+    call it always was (signature3_kernel / signature12_kernel); anything else, the identity list
+    included, runs the general kernel of csrc/signature_ex.h.  ValueError (before any GPU call) for a
+    bad channel list or a depth above 6; NotImplementedError when the levels do not fit a workgroup's LDS."""
     prec = _precision(dtype)
     assert len(states.shape) == 3, 'states should be batch x time x state_dim'
+    assert len(actions.shape) == 3, 'Need actions: ntraj x n_steps x state_dim'
+    picked = None if channels is None else signature_channels(channels, states.shape[2], actions.shape[2])
+    if depth is not None and depth > _lib.SIGNATURE_MAX_DEPTH:
+        raise ValueError('depth %r is above %d' % (depth, _lib.SIGNATURE_MAX_DEPTH))
     s, a, home = _prep(states, actions, prec)
     n, length, sd = s.shape
     ad = a.shape[2]
     assert a.shape[1] == length
+    path_dim = 1 + (sd + ad if picked is None else len(picked))
     if depth is None:
-        depth = signature_depth(1 + sd + ad)
-    width = summary_dim('summary_signatory', length, sd, ad, depth)
+        depth = signature_depth(path_dim)
+    if picked is None and depth <= 3:
+        width = summary_dim('summary_signatory', length, sd, ad, depth)
+        buf, ld = _alloc(n, width, s.device, out, prec)
+        prec.signature(
+            _lib.ptr(s), _lib.ptr(a), _lib.ptr(buf), n, length, sd, ad, depth, ld,
+            _lib.stream())
+        return _finish(buf, n, width, home, out)
+    width = signature_dim(path_dim, depth)
     buf, ld = _alloc(n, width, s.device, out, prec)
-    prec.signature(
-        _lib.ptr(s), _lib.ptr(a), _lib.ptr(buf), n, length, sd, ad, depth, ld,
-        _lib.stream())
+    vec = None if picked is None else _channel_vector(picked, s.device)
+    prec.signature_ex(
+        _lib.ptr(s), _lib.ptr(a), _lib.ptr(vec), len(picked or ()), _lib.ptr(buf), n, length, sd, ad,
+        depth, ld, _lib.stream())
     return _finish(buf, n, width, home, out)

@@ -1,7 +1,8 @@
 #!/usr/bin/env bash
 # Build libbsig_hip.so (gfx950) in-tree.  hipcc cross-compiles without a GPU.
 # An object is rebuilt when the CONTENT of its source, of any csrc header, of include/bsig.h, include/bsig_matmul.h or the
-# flags changed (a stamp next to the object; file times do not survive every transport).
+# flags changed (a stamp next to the object; file times do not survive every transport).  The objects of the fp64 mode
+# and of the general signature kernel also cover include/bsig_f64.h and include/bsig_signature.h.
 set -euo pipefail
 cd "$(dirname "$0")"
 SRC=bayes_sim_ig_amd/csrc
@@ -22,6 +23,8 @@ if [ "${BSIG_BUILD_WIDE_TILES:-0}" = "1" ]; then FLAGS="$FLAGS -DBSIG_WITH_WIDE_
 COMMON=$(cat "$SRC"/*.h include/bsig.h include/bsig_matmul.h | sha256sum | cut -d' ' -f1)
 # the fp64 mode (csrc/f64/, include/bsig_f64.h): its objects' stamps cover its own headers too
 COMMON64=$(cat "$SRC"/f64/*.h include/bsig_f64.h | sha256sum | cut -d' ' -f1)
+# the general signature kernel (csrc/signature_ex.h, include/bsig_signature.h), in both precisions
+SIGEX=$(sha256sum < include/bsig_signature.h | cut -d' ' -f1)
 pids=()
 build_one() {  # name, source, extra flags[, hash of further headers the source sees]
   local stamp="$OUT/obj/$1.stamp"
@@ -36,6 +39,8 @@ rm -f "$OUT"/obj/fit_persistent_v1.*      # (retired in round 6: an object of an
 for f in summarizers gemm_f32 gemm_tile_64 gemm_tile_128 gemm_tile_128x32 gemm_tile_128x64 gemm_tile_128x96 gemm_tile_96x128 gemm_lean_64 gemm_lean_128 gemm_lean_128x32 gemm_lean_128x64 gemm_lean_128x96 gemm_lean_96x128 gemm_wide gemm_split_bf16 $WIDE_TILES mdn_head flat_ops estimator fit_persistent fit_persistent_mdnn fit_persistent_mdnn_stream; do
   build_one "$f" "$SRC/$f.hip" ""
 done
+build_one signature_ex "$SRC/signature_ex.hip" "" "$SIGEX"
+build_one signature_ex_f64 "$SRC/f64/signature_ex_f64.hip" "" "$COMMON64 $SIGEX"
 for f in api comm; do
   build_one "$f" "$SRC/$f.cpp" "-x hip"
 done
