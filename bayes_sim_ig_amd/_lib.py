@@ -33,6 +33,7 @@ MATMUL_FP32, MATMUL_SPLIT_BF16 = 0, 1
 MATMUL_PRECISIONS = {'float32': MATMUL_FP32, 'split_bf16': MATMUL_SPLIT_BF16}
 GEMM_PATH_SPLIT_BF16 = 10
 X_ROWS, X_CROSSCORR_FACTORS = 0, 1
+FLAG_NONFINITE, FLAG_TIMEOUT = 1, 2      # the state block's flag word (csrc/fit_protocol.h)
 
 i64, i32, u64, f32, vp, sz = (C.c_int64, C.c_int32, C.c_uint64, C.c_float,
                               C.c_void_p, C.c_size_t)
@@ -192,6 +193,7 @@ _PROTOS = {
     'bsig_fit_block_chunks': (C.c_int, [vp, i64]),
     'bsig_fit_run_block': (C.c_int, [vp, vp, i64, i64, vp, i64, vp, i64, vp, vp, C.c_int, vp, vp, vp, i64, vp]),
     'bsig_debug_block_launch': (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    'bsig_debug_fit_schedule': (C.c_int, [C.c_int, C.c_int, C.c_int, vp, C.c_int]),
     'bsig_fit_run_dp': (C.c_int, [vp, vp, i64, vp, vp]),
 }
 # include/bsig_f64.h: the fp64 mode

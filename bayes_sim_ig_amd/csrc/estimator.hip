@@ -32,6 +32,7 @@
 #include "head.h"
 #include "persist.h"
 #include "persist_mdnn.h"
+#include "fit_protocol.h"
 
 #include <algorithm>
 #include <chrono>
@@ -326,10 +327,7 @@ static int head_nll(const bsig_mdn_cfg* c, const Layout& L, const Scratch& s, co
 }
 
 // ---- fit engine -----------------------------------------------------------
-// device state block (int32 words)
-enum { ST_STEP = 0, ST_EVAL = 1, ST_NONFINITE = 2, ST_ADAM0 = 4, ST_ADAM1 = 5,
-       ST_RNG = 8 /* 4 words: seed, counter (uint64 x2) */,
-       ST_BETA_POW = 12 /* 4 words: beta1^t, beta2^t (double x2) */, ST_WORDS = 16 };
+// (the device state block, the logging schedule and the stream numbering: fit_protocol.h)
 
 // Start of a run_training call: reset the state block and clear what the call needs cleared
 // (a fresh optimizer's moments, mdnn.py:203, unless the persistent kernels start them in
@@ -339,12 +337,7 @@ __global__ __launch_bounds__(256) void fit_begin_kernel(int32_t* state, uint64_t
   if (blockIdx.x == 0) {
     if (threadIdx.x < ST_WORDS) state[threadIdx.x] = 0;
     __syncthreads();
-    if (threadIdx.x == 0) {
-      reinterpret_cast<uint64_t*>(state + ST_RNG)[0] = seed;
-      reinterpret_cast<uint64_t*>(state + ST_RNG)[1] = 1;
-      reinterpret_cast<double*>(state + ST_BETA_POW)[0] = 1.0;   // beta1^0, beta2^0
-      reinterpret_cast<double*>(state + ST_BETA_POW)[1] = 1.0;
-    }
+    if (threadIdx.x == 0) st_begin(state, seed);
   }
   const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
@@ -357,14 +350,6 @@ __global__ __launch_bounds__(256) void fit_begin_kernel(int32_t* state, uint64_t
 __global__ void iota_mod_kernel(int32_t* out, int n, int mod) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
     out[i] = i % mod;
-}
-
-static int64_t count_evals(int64_t n_updates) {   // mdnn.py:235
-  const int64_t every = std::max<int64_t>(n_updates / 5, 1);
-  int64_t n = 0;
-  for (int64_t it = 0; it < n_updates; ++it)
-    if (it % every == 0 || it + 1 == n_updates) ++n;
-  return n;
 }
 
 }  // namespace bsig
@@ -495,7 +480,7 @@ static int enqueue_persistent(bsig_fit_plan* p, int n, hipStream_t st, int eval_
   }
   if (xr) { c.xr_ready = xr->ready; c.xr_done = xr->done; c.xr_base = xr->base; c.n_total = n; }
   if (eval_total > 0) {
-    c.do_eval = 1; c.n_total = eval_total; c.eval_every = std::max(eval_total / 5, 1);   // mdnn.py:235
+    c.do_eval = 1; c.n_total = eval_total; c.eval_every = eval_every(eval_total);
     c.n_test = (int)b.n_test;
     c.y_test = b.y_test; c.ldy_test = b.ldy_test; c.test_loss = b.test_loss;
   }
@@ -569,9 +554,8 @@ static int enqueue_grad(bsig_fit_plan* p, hipStream_t st, bool fuse_adam) {
   hd.y_dyn = b.state + ST_STEP; hd.y_dyn_stride = p->batch;
   hd.hook.state = b.state; hd.hook.kind = 1;
   hd.hook.lr = p->cfg.lr; hd.hook.beta1 = p->cfg.beta1; hd.hook.beta2 = p->cfg.beta2;
-  AdamFuse fuse{b.exp_avg, b.exp_avg_sq, reinterpret_cast<const float*>(b.state) + ST_ADAM0,
-                p->cfg.beta1, p->cfg.beta2, p->cfg.adam_eps};
-  const uint64_t* rng = reinterpret_cast<const uint64_t*>(b.state + ST_RNG);
+  AdamFuse fuse{b.exp_avg, b.exp_avg_sq, st_adam(b.state), p->cfg.beta1, p->cfg.beta2, p->cfg.adam_eps};
+  const uint64_t* rng = st_rng(b.state);
   int n_sig = 0;
   BSIG_TRY(forward_pass(&p->cfg, p->L, b.params, in, p->batch, m.tr, m.tr.o, m.tr.ld_o, st,
                         &n_sig));
@@ -583,7 +567,7 @@ static int enqueue_grad(bsig_fit_plan* p, hipStream_t st, bool fuse_adam) {
       gemm_wide_gradient_applies(p->L.nh, p->L.feat_dim, p->batch, m.tr.ld_o, in.ldx, m.tr.d_o, in.x, true);
   BSIG_TRY(head_nll(&p->cfg, p->L, m.tr, b.y_train, b.ldy_train, b.ids_table, p->batch,
                     p->norm_batch, nullptr, 0, 0, rng, b.train_loss, b.state + ST_STEP, true,
-                    b.grads + p->L.head_b_off, b.state + ST_NONFINITE, &hd, st,
+                    b.grads + p->L.head_b_off, b.state + ST_FLAGS, &hd, st,
                     partial_bias ? &bp : nullptr));
   return backward_pass(&p->cfg, p->L, b.params, in, -1, p->batch, m.tr, b.grads,
                        fuse_adam ? &fuse : nullptr, st, partial_bias ? &bp : nullptr);
@@ -592,8 +576,7 @@ static int enqueue_grad(bsig_fit_plan* p, hipStream_t st, bool fuse_adam) {
 static int enqueue_apply(bsig_fit_plan* p, hipStream_t st) {
   const bsig_fit_buffers& b = p->buf;
   return adam_launch(b.params, b.grads, b.exp_avg, b.exp_avg_sq, p->L.total, p->cfg.lr,
-                     p->cfg.beta1, p->cfg.beta2, p->cfg.adam_eps, 1,
-                     reinterpret_cast<const float*>(b.state) + ST_ADAM0, st);
+                     p->cfg.beta1, p->cfg.beta2, p->cfg.adam_eps, 1, st_adam(b.state), st);
 }
 
 static int enqueue_eval(bsig_fit_plan* p, hipStream_t st) {
@@ -612,8 +595,8 @@ static int enqueue_eval(bsig_fit_plan* p, hipStream_t st) {
                         &n_sig));
   hd.n_sig_ready = n_sig;
   return head_nll(&p->cfg, p->L, m.te, b.y_test, b.ldy_test, nullptr, b.n_test, b.n_test,
-                  nullptr, 0, 0, reinterpret_cast<const uint64_t*>(b.state + ST_RNG),
-                  b.test_loss, b.state + ST_EVAL, false, nullptr, b.state + ST_NONFINITE, &hd,
+                  nullptr, 0, 0, st_rng(b.state),
+                  b.test_loss, b.state + ST_EVAL, false, nullptr, b.state + ST_FLAGS, &hd,
                   st);
 }
 
@@ -800,7 +783,7 @@ extern "C" int bsig_fit_create_ex(const bsig_mdn_cfg* cfg, int64_t batch,
   const int rc = make_layout(cfg, &p->L);
   if (rc != BSIG_OK) { delete p; return rc; }
   p->batch = batch; p->max_test = max_test_rows; p->norm_batch = batch;
-  p->n_updates = n_updates; p->n_evals = count_evals(n_updates);
+  p->n_updates = n_updates; p->n_evals = count_logging_points(n_updates);
   p->matmul = (plan_flags & BSIG_PLAN_SPLIT_BF16) ? BSIG_MATMUL_SPLIT_BF16 : BSIG_MATMUL_FP32;
   Scratch s;
   carve(cfg, p->L, batch, nullptr, &s); p->train_ws_bytes = s.total_bytes;
@@ -1080,7 +1063,7 @@ extern "C" int bsig_fit_eval(bsig_fit_plan* p, bsig_stream_t stream) {
   BSIG_REQUIRE(p && p->bound, "fit_eval: plan not bound");
   if (const int total = dp_eval_total(p)) {
     // evaluations inside the launches: all but the last are already under way
-    if (++p->dp_evals_done < count_evals(total)) return BSIG_OK;
+    if (++p->dp_evals_done < count_logging_points(total)) return BSIG_OK;
     return enqueue_persistent(p, 0, as_stream(stream), total);
   }
   BSIG_REQUIRE(p->buf.n_test < 1 || p->buf.x_test,
@@ -1141,10 +1124,10 @@ extern "C" int bsig_fit_run(bsig_fit_plan* p, int64_t n_updates, bsig_stream_t s
   if (engine(p) && !p->split_adam && n_updates >= 1 && p->buf.n_test >= 1 &&
       evals_in_launch(p, false, p->buf.x_test_factors != nullptr))
     return enqueue_persistent(p, (int)n_updates, st, (int)n_updates);
-  const int64_t every = std::max<int64_t>(n_updates / 5, 1);   // mdnn.py:235
+  const int64_t every = eval_every(n_updates);
   int64_t done = 0;
   for (int64_t it = 0; it < n_updates; ++it) {
-    if (it % every == 0 || it + 1 == n_updates) {
+    if (is_logging_point(it, n_updates, every)) {
       BSIG_TRY(enqueue_updates(p, it + 1 - done, st));   // the run of updates up to here
       done = it + 1;
       BSIG_TRY(bsig_fit_eval(p, stream));
@@ -1157,14 +1140,8 @@ namespace bsig {
 // [train_loss at the logging points | test_loss | flag word] of one call, for its single read-back
 __global__ void pack_logs_kernel(const float* train_loss, const float* test_loss,
                                  const int32_t* state, int n_updates, int n_evals, float* out) {
-  const int every = n_updates / 5 > 1 ? n_updates / 5 : 1;        // mdnn.py:235
-  if (threadIdx.x == 0) {
-    int e = 0;
-    for (int it = 0; it < n_updates; ++it)
-      if (it % every == 0 || it + 1 == n_updates) { out[e] = train_loss[it]; ++e; }
-    out[2 * n_evals] = (float)state[ST_NONFINITE];
-  }
-  for (int i = threadIdx.x; i < n_evals; i += blockDim.x) out[n_evals + i] = test_loss[i];
+  pack_call_logs(train_loss, test_loss, state, n_updates, eval_every(n_updates), n_evals, out, (int)threadIdx.x,
+                 (int)blockDim.x);
 }
 }  // namespace bsig
 
@@ -1173,7 +1150,7 @@ extern "C" int bsig_fit_pack_logs(bsig_fit_plan* p, int64_t n_updates, float* ou
   BSIG_REQUIRE(p && p->bound && out, "fit_pack_logs: plan not bound / null");
   BSIG_REQUIRE(n_updates >= 0 && n_updates <= p->n_updates, "fit_pack_logs: bad n_updates");
   hipLaunchKernelGGL(pack_logs_kernel, dim3(1), dim3(64), 0, as_stream(stream), p->buf.train_loss,
-                     p->buf.test_loss, p->buf.state, (int)n_updates, (int)count_evals(n_updates), out);
+                     p->buf.test_loss, p->buf.state, (int)n_updates, (int)count_logging_points(n_updates), out);
   BSIG_CHECK_LAUNCH("pack_logs");
   return BSIG_OK;
 }
@@ -1183,19 +1160,26 @@ namespace bsig {
 __global__ void pack_block_logs_kernel(const float* train_loss, const float* test_loss, const int32_t* state,
                                        const bsig_fit_chunk* chunks, int n_evals, float* out) {
   const bsig_fit_chunk ch = chunks[blockIdx.x];
-  float* o = out + (int64_t)blockIdx.x * (2 * n_evals + 1);
-  if (threadIdx.x == 0) {
-    int e = 0;
-    for (int it = 0; it < ch.n_updates; ++it)
-      if (it % ch.eval_every == 0 || it + 1 == ch.n_updates) { o[e] = train_loss[ch.train_slot + it]; ++e; }
-    o[2 * n_evals] = (float)state[ST_NONFINITE];
-  }
-  for (int i = threadIdx.x; i < n_evals; i += blockDim.x) o[n_evals + i] = test_loss[ch.test_slot + i];
+  pack_call_logs(train_loss + ch.train_slot, test_loss + ch.test_slot, state, ch.n_updates, ch.eval_every, n_evals,
+                 out + (int64_t)blockIdx.x * (2 * n_evals + 1), (int)threadIdx.x, (int)blockDim.x);
 }
 }  // namespace bsig
 
 extern "C" int bsig_debug_block_launch(int engine_kind, int eval_in_launch, int forced_single) {
   return block_launch_resolved(engine_kind, eval_in_launch != 0, forced_single != 0) ? 1 : 0;
+}
+
+extern "C" int bsig_debug_fit_schedule(int n_updates, int step0, int n, int32_t* out, int cap) {
+  BSIG_REQUIRE(out && n_updates >= 0 && step0 >= 0 && n >= 0 && (int64_t)step0 + n <= n_updates &&
+               (int64_t)cap >= 3 + 2 * (int64_t)n_updates, "debug_fit_schedule: negative argument or short out");
+  const int every = eval_every(n_updates);
+  out[0] = every; out[1] = count_logging_points(n_updates);
+  out[2] = evals_in_run(step0, n, n_updates, every, true);
+  for (int it = 0; it < n_updates; ++it) {
+    out[3 + 2 * it] = is_logging_point(it, n_updates, every) ? 1 : 0;
+    out[4 + 2 * it] = evals_before(it, every);
+  }
+  return BSIG_OK;
 }
 
 extern "C" int bsig_fit_block_chunks(const bsig_fit_plan* p, int64_t n_train) {
@@ -1217,7 +1201,7 @@ extern "C" int bsig_fit_run_block(bsig_fit_plan* p, const float* feats, int64_t 
                "fit_run_block: this plan runs one chunk per launch (bsig_fit_block_chunks)");
   BSIG_REQUIRE(rows >= 1 && ld_feats >= p->cfg.rff_feats && ld_feats % 4 == 0 && aligned(feats, 16) &&
                ldy >= p->cfg.head.out_dim && n_ids >= 0, "fit_run_block: bad block");
-  const int n_upd = (int)p->n_updates, every = std::max(n_upd / 5, 1), n_ev = (int)p->n_evals;
+  const int n_upd = (int)p->n_updates, every = eval_every(n_upd), n_ev = (int)p->n_evals;
   int max_test = 0;
   for (int c = 0; c < n_chunks; ++c) {
     const bsig_fit_chunk& k = chunks_host[c];
@@ -1253,7 +1237,7 @@ __global__ void pack_dp_logs_kernel(const float* train_loss, const float* test_l
     if (i < n_updates) v = train_loss[i];
     else if (i < n_updates + n_evals) v = n_test > 0.f ? test_loss[i - n_updates] * n_test : 0.f;
     else if (i == n_updates + n_evals) v = n_test;
-    else v = (state[ST_NONFINITE] >> (i - n_updates - n_evals - 1)) & 1 ? 1.f : 0.f;
+    else v = (state[ST_FLAGS] >> (i - n_updates - n_evals - 1)) & 1 ? 1.f : 0.f;
     out[i] = v;
   }
 }
@@ -1402,7 +1386,7 @@ static int run_dp_resident(bsig_fit_plan* p, bsig_comm* comm, int64_t n_updates,
       BSIG_HIP(hipHostMalloc(reinterpret_cast<void**>(&hist), kHist * 4, 0));
       for (int i = 0; i < kHist; ++i) hist[i] = -1;
     }
-    if (n_hist < kHist) BSIG_HIP(hipMemcpyAsync(&hist[n_hist++], p->buf.state + 2, 4, hipMemcpyDeviceToHost, st));
+    if (n_hist < kHist) BSIG_HIP(hipMemcpyAsync(&hist[n_hist++], p->buf.state + ST_FLAGS, 4, hipMemcpyDeviceToHost, st));
     const auto t1 = std::chrono::steady_clock::now();
     fprintf(stderr, "run_dp_resident: %lld updates enqueued in %.1f us of host time; time-out bits so far:", (long long)n_updates,
             std::chrono::duration<double, std::micro>(t1 - t0_host).count());
@@ -1424,7 +1408,7 @@ extern "C" int bsig_fit_run_dp(bsig_fit_plan* p, bsig_comm* comm, int64_t n_upda
                "fit_run_dp: bsig_fit_begin's norm_batch %lld != batch %lld x world %d",
                (long long)p->norm_batch, (long long)p->batch, bsig_comm_world(comm));
   if (p->use_graph) BSIG_TRY(ensure_graphs(p));
-  const int64_t every = std::max<int64_t>(n_updates / 5, 1);   // mdnn.py:235
+  const int64_t every = eval_every(n_updates);
   int64_t n_evals = 0;
   // (the word the workgroups of a resident launch count themselves in is zeroed by bsig_fit_begin: one
   // resident call per begin, a further call continues with a launch per update)
@@ -1446,7 +1430,7 @@ extern "C" int bsig_fit_run_dp(bsig_fit_plan* p, bsig_comm* comm, int64_t n_upda
   if (resident) {
     BSIG_TRY(run_dp_resident(p, comm, n_updates, as_stream(stream)));
     p->resident_ran = true;
-    n_evals = count_evals(n_updates);
+    n_evals = count_logging_points(n_updates);
   }
   const bool was_pending = p->adam_pending;
   if (!resident) BSIG_TRY(bsig::comm_xr_drain(comm));     // (stale all-reduces of a resident call that gave up)
@@ -1462,7 +1446,7 @@ extern "C" int bsig_fit_run_dp(bsig_fit_plan* p, bsig_comm* comm, int64_t n_upda
       BSIG_TRY(allreduce_grads(p, comm, stream));
       BSIG_TRY(bsig_fit_apply(p, stream));
     }
-    if (it % every == 0 || it + 1 == n_updates) { BSIG_TRY(bsig_fit_eval(p, stream)); ++n_evals; }
+    if (is_logging_point(it, n_updates, every)) { BSIG_TRY(bsig_fit_eval(p, stream)); ++n_evals; }
   }
   BSIG_TRY(bsig_fit_flush(p, stream));
   if (reduced_logs) {

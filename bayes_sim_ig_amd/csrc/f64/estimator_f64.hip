@@ -176,41 +176,20 @@ static int head_nll(const bsig_mdn_cfg* c, const bsig_f64_hyper& hy, const Layou
 // Start of a run_training call: the state block of a fresh optimizer (mdnn.py:203) and its zeroed moments
 __global__ __launch_bounds__(256) void fit64_begin_kernel(int32_t* state, double* m, double* v, int64_t n) {
   if (blockIdx.x == 0) {
-    if (threadIdx.x < ST_WORDS) state[threadIdx.x] = 0;
+    if (threadIdx.x < ST64_WORDS) state[threadIdx.x] = 0;
     __syncthreads();
-    if (threadIdx.x == 0) {
-      double* dv = reinterpret_cast<double*>(state + ST_DBL);
-      dv[0] = 1.0; dv[1] = 1.0;   // beta1^0, beta2^0
-    }
+    if (threadIdx.x == 0) st64_begin(state);
   }
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     m[i] = 0.0; v[i] = 0.0;
   }
 }
 
-// The logging points of mdnn.py:235 -- the one statement of the rule on this side; the caller's
-// count of them (protocol.eval_updates in the Python mirror) is checked against it at pack time.
-__host__ __device__ inline bool is_logging_point(int64_t it, int64_t n_updates) {
-  const int64_t every = n_updates / 5 > 1 ? n_updates / 5 : 1;
-  return it % every == 0 || it + 1 == n_updates;
-}
-
 // [train_loss at the logging points | test_loss | flag word] of one call, for its single read-back
 __global__ void pack_logs_f64_kernel(const double* train_loss, const double* test_loss, const int32_t* state,
                                      int n_updates, int n_evals, double* out) {
-  if (threadIdx.x == 0) {
-    int e = 0;
-    for (int it = 0; it < n_updates; ++it)
-      if (is_logging_point(it, n_updates)) { out[e] = train_loss[it]; ++e; }
-    out[2 * n_evals] = (double)state[ST_NONFINITE];
-  }
-  for (int i = threadIdx.x; i < n_evals; i += blockDim.x) out[n_evals + i] = test_loss[i];
-}
-
-static int64_t count_evals(int64_t n_updates) {
-  int64_t n = 0;
-  for (int64_t it = 0; it < n_updates; ++it) n += is_logging_point(it, n_updates);
-  return n;
+  pack_call_logs(train_loss, test_loss, state, n_updates, eval_every(n_updates), n_evals, out, (int)threadIdx.x,
+                 (int)blockDim.x);
 }
 
 }  // namespace f64
@@ -387,10 +366,10 @@ static int fit64_update(bsig_fit64_plan* p, int64_t it, const Scratch& s, hipStr
   BSIG_TRY(forward_pass(&p->cfg, p->hy, p->L, b.params, in, p->batch, s, s.o, p->L.nh, st));
   BSIG_TRY(head_nll(&p->cfg, p->hy, p->L, s, b.y_train, b.ldy_train, ids, p->batch, p->norm_batch, nullptr,
                     p->seed, p->rng_ctr++, b.train_loss + it, true, b.grads + p->L.head_b_off,
-                    b.state + ST_NONFINITE, hook, st));
+                    b.state + ST_FLAGS, hook, st));
   BSIG_TRY(backward_pass(&p->cfg, p->L, b.params, in, p->batch, s, b.grads, st));
   return adam_launch(b.params, b.grads, b.exp_avg, b.exp_avg_sq, p->L.total, p->hy.beta1, p->hy.beta2,
-                     p->hy.adam_eps, 0.0, 1.0, reinterpret_cast<const double*>(b.state + ST_DBL), st);
+                     p->hy.adam_eps, 0.0, 1.0, st64_dbl(b.state), st);
 }
 
 static int fit64_eval(bsig_fit64_plan* p, int64_t e, const Scratch& s, hipStream_t st) {
@@ -404,7 +383,7 @@ static int fit64_eval(bsig_fit64_plan* p, int64_t e, const Scratch& s, hipStream
   hook.state = b.state; hook.kind = 2;
   BSIG_TRY(forward_pass(&p->cfg, p->hy, p->L, b.params, in, b.n_test, s, s.o, p->L.nh, st));
   return head_nll(&p->cfg, p->hy, p->L, s, b.y_test, b.ldy_test, nullptr, b.n_test, b.n_test, nullptr, p->seed,
-                  p->rng_ctr++, b.test_loss + e, false, nullptr, b.state + ST_NONFINITE, hook, st);
+                  p->rng_ctr++, b.test_loss + e, false, nullptr, b.state + ST_FLAGS, hook, st);
 }
 
 extern "C" int bsig_fit64_run(bsig_fit64_plan* p, int64_t n_updates, bsig_stream_t stream) {
@@ -415,10 +394,11 @@ extern "C" int bsig_fit64_run(bsig_fit64_plan* p, int64_t n_updates, bsig_stream
   hipStream_t st = as_stream(stream);
   Scratch s;
   carve(&p->cfg, p->L, std::max<int64_t>(p->batch, std::max<int64_t>(p->max_test, 1)), p->buf.workspace, &s);
+  const int64_t every = eval_every(n_updates);
   int64_t e = 0;
   for (int64_t it = 0; it < n_updates; ++it) {
     BSIG_TRY(fit64_update(p, it, s, st));
-    if (is_logging_point(it, n_updates)) BSIG_TRY(fit64_eval(p, e++, s, st));
+    if (is_logging_point(it, n_updates, every)) BSIG_TRY(fit64_eval(p, e++, s, st));
   }
   return BSIG_OK;
 }
@@ -427,9 +407,9 @@ extern "C" int bsig_fit64_pack_logs(bsig_fit64_plan* p, int64_t n_updates, int64
                                     bsig_stream_t stream) {
   BSIG_REQUIRE(p && p->bound && out, "fit64_pack_logs: plan not bound / null");
   BSIG_REQUIRE(n_updates >= 0 && n_updates <= p->n_updates, "fit64_pack_logs: bad n_updates");
-  BSIG_REQUIRE(n_evals == count_evals(n_updates),
+  BSIG_REQUIRE(n_evals == count_logging_points(n_updates),
                "fit64_pack_logs: the caller counts %lld logging points in %lld updates, the fit loop ran %lld",
-               (long long)n_evals, (long long)n_updates, (long long)count_evals(n_updates));
+               (long long)n_evals, (long long)n_updates, (long long)count_logging_points(n_updates));
   hipLaunchKernelGGL(pack_logs_f64_kernel, dim3(1), dim3(64), 0, as_stream(stream), p->buf.train_loss,
                      p->buf.test_loss, p->buf.state, (int)n_updates, (int)n_evals, out);
   BSIG_CHECK_LAUNCH("pack_logs_f64");

@@ -1,6 +1,7 @@
 // Internal interfaces of the fp64 mode (include/bsig_f64.h): launchers shared between its files.
 #pragma once
 #include "../common.h"
+#include "../fit_protocol.h"
 #include "../../../include/bsig_f64.h"
 
 namespace bsig {
@@ -26,9 +27,7 @@ inline bsig_f64_hyper resolve_hyper(const bsig_f64_hyper* h, const bsig_head_dim
   return r;
 }
 
-// Engine state block (int32 words): step, evaluations, flag word; doubles from word 8:
-// beta1^t, beta2^t, lr / (1 - beta1^t), sqrt(1 - beta2^t)
-enum { ST_STEP = 0, ST_EVAL = 1, ST_NONFINITE = 2, ST_DBL = 8, ST_WORDS = 32 };
+// (the engine's 32-word state block: fit_protocol.h)
 struct FinishHook {
   int32_t* state = nullptr; int kind = 0;   // 1: end of an update's forward half, 2: end of an evaluation
   double lr = 0, beta1 = 0, beta2 = 0;

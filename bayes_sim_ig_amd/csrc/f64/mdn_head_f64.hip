@@ -207,22 +207,12 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void mdn_nll_f64_kernel(HeadArg
     a.row_lse[row] = lse;
     if (a.row_uds) a.row_uds[row] = uds;
   }
-  if (__any(bad) && lane == 0 && a.nonfinite) atomicOr(a.nonfinite, 1);
+  if (__any(bad) && lane == 0 && a.nonfinite) atomicOr(a.nonfinite, kFlagNonfinite);
 }
 
 // Fit-engine state advance (single writer; every reader of these words runs in a later kernel).
 __device__ inline void run_finish_hook(const FinishHook& hook) {
-  int32_t* st = hook.state;
-  if (hook.kind == 1) {   // end of the forward half of an update: beta^t as running products
-    double* dv = reinterpret_cast<double*>(st + ST_DBL);
-    const double b1t = dv[0] * hook.beta1, b2t = dv[1] * hook.beta2;
-    dv[0] = b1t; dv[1] = b2t;
-    dv[2] = hook.lr / (1.0 - b1t);
-    dv[3] = sqrt(1.0 - b2t);
-    st[ST_STEP] += 1;
-  } else {
-    st[ST_EVAL] += 1;
-  }
+  st64_finish_hook(hook.state, hook.kind == 1, hook.beta1, hook.beta2, hook.lr);
 }
 
 // loss = -(sum of the rows' logsumexp) / batch; d pre += (EPS / (B D K)) sum(u dL/dsigma) exp(pre)
@@ -242,7 +232,7 @@ __global__ __launch_bounds__(256) void mdn_finish_f64_kernel(
     if (threadIdx.x == 0) {
       const double l = -s / (double)batch;
       loss[0] = l;
-      if (!isfinite(l) && nonfinite) atomicOr(nonfinite, 1);
+      if (!isfinite(l) && nonfinite) atomicOr(nonfinite, kFlagNonfinite);
     }
   }
   if (hook.state && blockIdx.x == 0 && threadIdx.x == 0) run_finish_hook(hook);
@@ -316,7 +306,7 @@ __global__ __launch_bounds__(256) void mdn_outputs_f64_kernel(
       bad |= !isfinite(v);
     }
   }
-  if (bad && nonfinite) atomicOr(nonfinite, 1);
+  if (bad && nonfinite) atomicOr(nonfinite, kFlagNonfinite);
 }
 
 // ---------------------------------------------------------------- host side

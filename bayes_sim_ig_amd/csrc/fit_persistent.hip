@@ -119,10 +119,10 @@ __device__ __forceinline__ int64_t u_uniform(int64_t v) {
 }
 __device__ __forceinline__ void u_chunk_load(const UArgs& p, int c, UCk& k) {
   if (p.chunks == nullptr) {
-    k.step0 = p.state[0]; k.n_updates = p.n_updates; k.n_total = p.n_total; k.eval_every = p.eval_every;
+    k.step0 = p.state[ST_STEP]; k.n_updates = p.n_updates; k.n_total = p.n_total; k.eval_every = p.eval_every;
     k.do_eval = p.do_eval; k.ubase = 0u; k.evbase = 0u;
-    k.seed = reinterpret_cast<const uint64_t*>(p.state + 8)[0];
-    k.rng_ctr0 = reinterpret_cast<const uint64_t*>(p.state + 8)[1];
+    k.seed = st_rng(p.state)[0];
+    k.rng_ctr0 = st_rng(p.state)[1];
     return;
   }
   const bsig_fit_chunk& e = p.chunks[c];
@@ -136,7 +136,7 @@ __device__ __forceinline__ void u_chunk_load(const UArgs& p, int c, UCk& k) {
 struct UEval {
   int n_test, passes; int64_t row0;  // held-out feature rows feats[row0 .. row0 + n_test)
   const float* y_test; int64_t ldy_test;
-  float* out;                        // its slot of the test-loss log (null: test_loss[state[1]], one chunk)
+  float* out;                        // its slot of the test-loss log (null: test_loss[state[ST_EVAL]], one chunk)
   unsigned gidx;                     // evaluation number of the launch: slab buffer gidx % 3, tag gidx + 1
   uint64_t seed, stream;             // jitter stream (one per update and per evaluation, in program order:
                                      // the per-phase path's numbering)
@@ -147,9 +147,9 @@ __device__ __forceinline__ UEval u_eval_of(const UArgs& p, int c, int e) {
   uint64_t ctr0;
   if (p.chunks == nullptr) {
     v.n_test = p.n_test; v.row0 = p.eval_row0; v.y_test = p.y_test; v.ldy_test = p.ldy_test; v.out = nullptr;
-    v.gidx = (unsigned)e; every = p.eval_every; n_total = p.n_total; step0 = p.state[0];
-    v.seed = reinterpret_cast<const uint64_t*>(p.state + 8)[0];
-    ctr0 = reinterpret_cast<const uint64_t*>(p.state + 8)[1];
+    v.gidx = (unsigned)e; every = p.eval_every; n_total = p.n_total; step0 = p.state[ST_STEP];
+    v.seed = st_rng(p.state)[0];
+    ctr0 = st_rng(p.state)[1];
   } else {
     const bsig_fit_chunk& k = p.chunks[c];
     v.n_test = u_uniform(k.n_test); v.row0 = u_uniform(k.row0) + u_uniform(k.n_train);
@@ -159,14 +159,11 @@ __device__ __forceinline__ UEval u_eval_of(const UArgs& p, int c, int e) {
     v.seed = (uint64_t)u_uniform((int64_t)k.seed); ctr0 = (uint64_t)u_uniform((int64_t)k.rng_ctr0);
   }
   v.passes = (v.n_test + p.B - 1) / p.B;
-  // the update it precedes: e * every + 1, the call's update count for the evaluation after the last update
-  const int at = min(e * every + 1, n_total);
-  const int ev0 = p.do_eval || p.chunks ? (step0 == 0 ? 0 : (step0 - 1) / every + 1) : 0;
-  v.stream = ctr0 + (uint64_t)(at - step0) + (uint64_t)(e - ev0);
+  const int at = eval_at_step(e, every, n_total);
+  const int ev0 = p.do_eval || p.chunks ? evals_before(step0, every) : 0;
+  v.stream = launch_stream(ctr0, at - step0, e, ev0);
   return v;
 }
-// index of the evaluation after the last update of a call of n_total updates
-__device__ __forceinline__ int u_last_eval(int n_total, int every) { return n_total <= 1 ? 0 : (n_total - 2) / every + 1; }
 
 __device__ __forceinline__ f32x4 umfma(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
@@ -205,8 +202,6 @@ __device__ __forceinline__ URole wg_role(int wg, int T, int G) {
 // step S then contracts the four ADJACENT rows 16S + 4c .. + 3: the padding behind the last
 // minibatch row (100 rows: 12 of the last 16) costs no MFMAs.
 __device__ __forceinline__ int u_rowpos(int b) { return (b & ~15) + ((b & 3) << 2) + ((b >> 2) & 3); }
-
-__device__ __forceinline__ int u_evals_before(int s, int every) { return s == 0 ? 0 : (s - 1) / every + 1; }
 
 #define BSIG_USTAMP(k)                                                           \
   do {                                                                           \
@@ -379,7 +374,7 @@ __device__ __forceinline__ void u_owner_eval(const UArgs& p, float* XS, float* r
   const int lane = tid & 63, w = tid >> 6;
   const int B = p.B, Nh = p.Nh, NhP = p.NhP, D = p.D, K = p.K, DK = D * K;
   const int per_wave = Nh + D + 3 * K;
-  int32_t* flagp = p.state + 2;
+  int32_t* flagp = p.state + ST_FLAGS;
   const unsigned etag = ev.gidx + 1u;
   if (w == 0) flags_wait(p.flag_eval, p.G, etag, lane, flagp);
   __syncthreads();
@@ -441,12 +436,12 @@ __device__ __forceinline__ void u_owner_eval(const UArgs& p, float* XS, float* r
     if (lane == 0) {
       const float l = -sum / (float)ev.n_test;
       if (ev.out) *ev.out = l;
-      else p.test_loss[p.state[1]] = l;
-      p.state[1] = p.state[1] + 1;
-      if (!isfinite(l)) atomicOr(flagp, 1);
+      else p.test_loss[p.state[ST_EVAL]] = l;
+      p.state[ST_EVAL] = p.state[ST_EVAL] + 1;
+      if (!isfinite(l)) atomicOr(flagp, kFlagNonfinite);
     }
   }
-  if (ro.bad) atomicOr(flagp, 1);
+  if (ro.bad) atomicOr(flagp, kFlagNonfinite);
   __syncthreads();
 }
 
@@ -473,14 +468,14 @@ __device__ __forceinline__ void u_own_init(const UArgs& p, UOwn& o, int own, boo
   o.a.eps_noise = p.eps_noise; o.a.d_out = p.d_out;
   o.rg = row_geom(p.D, p.K, lane0);       // (integer divisions by run-time values: once per launch)
   o.norm = (float)p.B * (float)(p.D * p.K);
-  o.flagp = p.state + 2;
+  o.flagp = p.state + ST_FLAGS;
 }
 // ... what the owner derives from the chunk: again at every chunk boundary
 __device__ __forceinline__ void u_own_chunk(UOwn& o, const UCk& k) {
   o.a.seed = k.seed;
   o.rng_ctr0 = k.rng_ctr0;
   o.step0 = k.step0;
-  o.ev0 = k.do_eval ? u_evals_before(k.step0, k.eval_every) : 0;
+  o.ev0 = k.do_eval ? evals_before(k.step0, k.eval_every) : 0;
   o.ubase = k.ubase;
 }
 
@@ -519,7 +514,9 @@ __device__ __forceinline__ void u_own_update(const UArgs& p, UOwn& o, int t, int
     }
     // the row's jitter draws do not depend on the forward product: drawn in the wait
     float eu_pre[kElemsPerLane];
-    a.stream_id = rng_ctr0 + (uint64_t)t + (uint64_t)(p.do_eval ? u_evals_before(step, p.eval_every) - ev0 : 0);
+    // launch_stream(rng_ctr0, t, evals_before(step), ev0) of fit_protocol.h, written out (as in the fast rows below): the
+    // call compiles to another register allocation of the owners' loop
+    a.stream_id = rng_ctr0 + (uint64_t)t + (uint64_t)(p.do_eval ? evals_before(step, p.eval_every) - ev0 : 0);
     if (owner_wave) diag_row_noise(a, rg.groups, rg.k, rg.d0, row, active, lane, eu_pre);
     if (w == 0) {
       flag_wait_one(p.flag_fwd, (int)(((int64_t)own * p.G) / p.n_owner), epoch, flagp);
@@ -590,10 +587,10 @@ __device__ __forceinline__ void u_own_update(const UArgs& p, UOwn& o, int t, int
       if (lane == 0) {
         const float l = -s / (float)B;
         p.train_loss[epoch - 1u] = l;
-        if (!isfinite(l)) atomicOr(flagp, 1);
+        if (!isfinite(l)) atomicOr(flagp, kFlagNonfinite);
       }
     }
-    if (ro.bad) atomicOr(flagp, 1);
+    if (ro.bad) atomicOr(flagp, kFlagNonfinite);
 }
 
 
@@ -674,7 +671,7 @@ __device__ __forceinline__ void u_own_update_fast(const UArgs& p, UOwn& o, int t
       // the draw of element (d, k) is diag_row_noise's: the generic row's lane of the element is
       // (d % G) * K + k with G = 64 / K dimension slots, its sweep q = d / G; counter (row * 64 + lane) * 2
       // + (q >> 2), output q & 3.  (exact, NQH <= 2: the lanes and sweeps coincide -- one call)
-      const uint64_t sid = o.rng_ctr0 + (uint64_t)t + (uint64_t)(p.do_eval ? u_evals_before(step, p.eval_every) - o.ev0 : 0);
+      const uint64_t sid = o.rng_ctr0 + (uint64_t)t + (uint64_t)(p.do_eval ? evals_before(step, p.eval_every) - o.ev0 : 0);
       if (exact && NQH <= 2) {
         const Philox4 ph = philox4x32_10(o.a.seed, sid, ((uint64_t)row * 64 + lane) * 2);
 #pragma unroll
@@ -852,10 +849,10 @@ __device__ __forceinline__ void u_own_update_fast(const UArgs& p, UOwn& o, int t
     if (lane == 0) {
       const float l = -s / (float)B;
       p.train_loss[epoch - 1u] = l;
-      if (!isfinite(l)) atomicOr(flagp, 1);
+      if (!isfinite(l)) atomicOr(flagp, kFlagNonfinite);
     }
   }
-  if (bad) atomicOr(flagp, 1);
+  if (bad) atomicOr(flagp, kFlagNonfinite);
 }
 
 // The minibatch tile of update `step`, straight into the forward product's B-operand registers:
@@ -915,23 +912,23 @@ __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, c
   const int B = p.B, Nh = p.Nh, NhP = p.NhP, D = p.D, K = p.K, DK = D * K;
   constexpr int FP = kUFP;
   const int WP = p.WP;
-  int32_t* flagp = p.state + 2;
+  int32_t* flagp = p.state + ST_FLAGS;
   // the chunks of the launch (a data-parallel rank's launches hold one, described by the arguments)
   const int n_chunks = (DP || XR || p.chunks == nullptr) ? 1 : p.n_chunks;
   UCk ck;
   u_chunk_load(p, 0, ck);
   const int step0 = ck.step0;
   if (p.prof && p.n_updates > 0 && tid == 0) p.prof[((int64_t)wg * kUProf) * 16 + 14] = wall_clock64();
-  double b1t = reinterpret_cast<const double*>(p.state + 12)[0];
-  double b2t = reinterpret_cast<const double*>(p.state + 12)[1];
+  double b1t = st_beta_pow(p.state)[0];
+  double b2t = st_beta_pow(p.state)[1];
   float a0 = 0.f, a1 = 0.f;
   const AdamK ak{1.0f - (float)p.beta1, (float)p.beta2, 1.0f - (float)p.beta2, p.adam_eps};
   const bool pend = DP && p.adam_pending != 0;
   // first launch of a run_training call: a fresh optimizer (mdnn.py:203) -- the moments start at
   // zero in the registers, nobody has to clear (or read) them in memory
   const bool fresh = !DP && step0 == 0;
-  const float pa0 = pend ? reinterpret_cast<const float*>(p.state)[4] : 0.f;
-  const float pa1 = pend ? reinterpret_cast<const float*>(p.state)[5] : 0.f;
+  const float pa0 = pend ? st_adam(p.state)[0] : 0.f;
+  const float pa1 = pend ? st_adam(p.state)[1] : 0.f;
 
   // ---- the tile: W -> LDS, Adam moments -> registers in the dW accumulator layout: element v of
   //      block (jj, nt) of lane (c16, g4) of wave w  <->  W[n0 + 16nt + 4g4 + v][k0 + 16(w + 8jj) + c16]
@@ -1062,7 +1059,7 @@ __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, c
   // update): sampled at entry, so that such a launch leaves at once instead of running its forward
   // product into the bounded polls of owners that have already left
   if (tid == 0)
-    red[63] = (__hip_atomic_load(flagp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 2) ? 1.f : 0.f;
+    red[63] = (__hip_atomic_load(flagp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kFlagTimeout) ? 1.f : 0.f;
   if (has_tile && p.MT < kUMT)      // F^T columns of the m-tiles no wavefront writes (minibatches of <= 96 rows)
     for (int idx = tid; idx < p.KS * (kUFP / 4); idx += kUT) {
       const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -1183,10 +1180,9 @@ __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, c
     }
     // the time-out bit (set by any bounded poll on the chip), sampled off the critical path
     if (tid_l == 0)
-      red[63] = (__hip_atomic_load(flagp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 2) ? 1.f : 0.f;
-    b1t *= p.beta1; b2t *= p.beta2;        // beta^t as running products (double)
-    a0 = (float)(p.lr / (1.0 - b1t));
-    a1 = (float)(1.0 / sqrt(1.0 - b2t));
+      red[63] = (__hip_atomic_load(flagp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kFlagTimeout) ? 1.f : 0.f;
+    const AdamAdvance adv = adam_advance(b1t, b2t, p.beta1, p.beta2, p.lr);
+    b1t = adv.b1t; b2t = adv.b2t; a0 = adv.a0; a1 = adv.a1;
 
     // ---- 2. rows of this workgroup, if it owns any ------------------------------------------------
     if (has_row) u_own_update(p, o, t, w, lane0, wg);
@@ -1198,9 +1194,9 @@ __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, c
       pending_eval = -1;
     }
     // (update 0 of a later chunk of the launch: the evaluation after the last update of the chunk before)
-    if (__builtin_expect(p.do_eval && (step > 0 ? (step - 1) % p.eval_every == 0 : c > 0), 0)) {
+    if (__builtin_expect(p.do_eval && (step > 0 ? eval_follows_update(step, p.eval_every) : c > 0), 0)) {
       pending_chunk = step > 0 ? c : c - 1;
-      pending_eval = step > 0 ? u_evals_before(step, p.eval_every) - 1 : u_last_eval(p.n_updates, p.eval_every);
+      pending_eval = step > 0 ? evals_before(step, p.eval_every) - 1 : last_eval_index(p.n_updates, p.eval_every);
       u_tile_eval<NT>(p, Wl, biasl, slot, ks, n0, k0, u_eval_of(p, pending_chunk, pending_eval));
     }
 
@@ -1468,7 +1464,7 @@ __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, c
     // a launch that gave up (a bounded poll timed out, here or in any workgroup) must not leave the
     // exchange stream waiting for gradients that will never come: every wait of the call passes
     if (slot == 0 && tid == 0 &&
-        (__hip_atomic_load(flagp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 2))
+        (__hip_atomic_load(flagp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kFlagTimeout))
       __hip_atomic_store(p.xr_ready, p.xr_base + (unsigned)p.n_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 
@@ -1482,7 +1478,7 @@ __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, c
     // only takes the pending Adam step of that update; a block of chunks: of its last chunk -- the
     // others' ran in the waits of the chunk behind them)
     if (ck.step0 + p.n_updates == p.n_total && (!DP || p.n_updates == 0)) {
-      const UEval ev = u_eval_of(p, n_chunks - 1, u_evals_before(p.n_total - 1, p.eval_every));
+      const UEval ev = u_eval_of(p, n_chunks - 1, evals_before(p.n_total - 1, p.eval_every));
       __syncthreads();
       u_tile_eval<NT>(p, Wl, biasl, slot, ks, n0, k0, ev);
       if (has_erow) u_owner_eval(p, XS, red, eo, ev, o.a);
@@ -1521,20 +1517,19 @@ __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, c
     // (an aborted run leaves the counters of the planned run: the call fails anyway; a block of chunks
     // leaves what the call of its last chunk would have left)
     const int step0 = ck.step0;
+    // (the end of a launch as fit_protocol.h states it, the stores written out: a call compiles to another
+    // register allocation of this kernel)
     int32_t* st = p.state;
-    reinterpret_cast<double*>(st + 12)[0] = b1t;
-    reinterpret_cast<double*>(st + 12)[1] = b2t;
-    reinterpret_cast<float*>(st)[4] = a0;
-    reinterpret_cast<float*>(st)[5] = a1;
+    reinterpret_cast<double*>(st + ST_BETA_POW)[0] = b1t;
+    reinterpret_cast<double*>(st + ST_BETA_POW)[1] = b2t;
+    reinterpret_cast<float*>(st)[ST_ADAM0] = a0;
+    reinterpret_cast<float*>(st)[ST_ADAM1] = a1;
     // (one jitter stream per update and per evaluation, in program order)
     int n_ev = 0;
-    if (ck.do_eval) {
-      n_ev = u_evals_before(step0 + ck.n_updates, ck.eval_every) - u_evals_before(step0, ck.eval_every);
-      if (!DP && step0 + ck.n_updates == ck.n_total && (ck.n_total - 1) % ck.eval_every != 0) ++n_ev;
-    }
-    reinterpret_cast<uint64_t*>(st + 8)[0] = ck.seed;
-    reinterpret_cast<uint64_t*>(st + 8)[1] = ck.rng_ctr0 + (uint64_t)(ck.n_updates + n_ev);
-    st[0] = step0 + ck.n_updates;
+    if (ck.do_eval) n_ev = evals_in_run(step0, ck.n_updates, ck.n_total, ck.eval_every, !DP);
+    reinterpret_cast<uint64_t*>(st + ST_RNG)[0] = ck.seed;
+    reinterpret_cast<uint64_t*>(st + ST_RNG)[1] = ck.rng_ctr0 + (uint64_t)(ck.n_updates + n_ev);
+    st[ST_STEP] = step0 + ck.n_updates;
   }
 }
 
@@ -1545,7 +1540,7 @@ __device__ __forceinline__ void owner_only_workgroup(const UArgs& p, float* smem
   const int tid = threadIdx.x, lane0 = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wg = blockIdx.x;
-  int32_t* flagp = p.state + 2;
+  int32_t* flagp = p.state + ST_FLAGS;
   const int n_chunks = (dp || p.chunks == nullptr) ? 1 : p.n_chunks;
   UCk ck;
   u_chunk_load(p, 0, ck);
@@ -1588,9 +1583,9 @@ __device__ __forceinline__ void owner_only_workgroup(const UArgs& p, float* smem
       if (has_erow) u_owner_eval(p, XS, red, eo, u_eval_of(p, pending_chunk, pending_eval), o.a);
       pending_eval = -1;
     }
-    if (__builtin_expect(p.do_eval && (step > 0 ? (step - 1) % p.eval_every == 0 : c > 0), 0)) {
+    if (__builtin_expect(p.do_eval && (step > 0 ? eval_follows_update(step, p.eval_every) : c > 0), 0)) {
       pending_chunk = step > 0 ? c : c - 1;
-      pending_eval = step > 0 ? u_evals_before(step, p.eval_every) - 1 : u_last_eval(p.n_updates, p.eval_every);
+      pending_eval = step > 0 ? evals_before(step, p.eval_every) - 1 : last_eval_index(p.n_updates, p.eval_every);
     }
     __syncthreads();
   }
@@ -1599,7 +1594,7 @@ __device__ __forceinline__ void owner_only_workgroup(const UArgs& p, float* smem
     if (pending_eval >= 0 && has_erow)
       u_owner_eval(p, XS, red, eo, u_eval_of(p, pending_chunk, pending_eval), o.a);
     if (ck.step0 + p.n_updates == p.n_total && (!dp || p.n_updates == 0)) {
-      const UEval ev = u_eval_of(p, n_chunks - 1, u_evals_before(p.n_total - 1, p.eval_every));
+      const UEval ev = u_eval_of(p, n_chunks - 1, evals_before(p.n_total - 1, p.eval_every));
       __syncthreads();
       if (has_erow) u_owner_eval(p, XS, red, eo, ev, o.a);
     }

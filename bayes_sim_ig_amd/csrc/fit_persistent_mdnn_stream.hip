@@ -87,10 +87,10 @@ __device__ __forceinline__ void mdnn_stream_tile_workgroup(const MdnnArgs& p, fl
   const int S = p.xS, A = p.xA, SA = S * A, I = p.I;
   const float rA = __builtin_amdgcn_rcpf((float)A);
   const int i_lo = (c_lo * kSC) / A;
-  int32_t* flagp = p.state + 2;
-  const int step0 = p.state[0];
-  double b1t = reinterpret_cast<const double*>(p.state + 12)[0];
-  double b2t = reinterpret_cast<const double*>(p.state + 12)[1];
+  int32_t* flagp = p.state + ST_FLAGS;
+  const int step0 = p.state[ST_STEP];
+  double b1t = st_beta_pow(p.state)[0];
+  double b2t = st_beta_pow(p.state)[1];
   float a0 = 0.f, a1 = 0.f;
   const AdamK ak{1.0f - (float)p.beta1, (float)p.beta2, 1.0f - (float)p.beta2, p.adam_eps};
   const bool fresh = !DP && step0 == 0;      // fresh optimizer (mdnn.py:203): moments start at zero
@@ -460,8 +460,8 @@ __device__ __forceinline__ void mdnn_stream_tile_workgroup(const MdnnArgs& p, fl
     relaunder();
     if (run_aborted(flagp, red, tid)) break;
     // the evaluation due after the previous update, then this minibatch's factor rows again
-    if (!DP && __builtin_expect(p.do_eval && step > 0 && ((step - 1) % p.eval_every == 0 || tail), 0)) {
-      eval_all(tail ? mdnn_evals_before(p.n_total - 1, p.eval_every) : mdnn_evals_before(step, p.eval_every) - 1,
+    if (!DP && __builtin_expect(p.do_eval && step > 0 && (eval_follows_update(step, p.eval_every) || tail), 0)) {
+      eval_all(tail ? evals_before(p.n_total - 1, p.eval_every) : evals_before(step, p.eval_every) - 1,
                tail ? 0u : epoch);
       if (tail) break;
       relaunder();
@@ -477,9 +477,8 @@ __device__ __forceinline__ void mdnn_stream_tile_workgroup(const MdnnArgs& p, fl
     BSIG_MSTAMP(1);
     if (has_next) load_factor_rows((int64_t)(step + 1) * B);
     BSIG_MSTAMP(6);
-    b1t *= p.beta1; b2t *= p.beta2;
-    a0 = (float)(p.lr / (1.0 - b1t));
-    a1 = (float)(1.0 / sqrt(1.0 - b2t));
+    const AdamAdvance adv = adam_advance(b1t, b2t, p.beta1, p.beta2, p.lr);
+    b1t = adv.b1t; b2t = adv.b2t; a0 = adv.a0; a1 = adv.a1;
     if (w == 0) flags_wait(p.flag_own, p.n_owner, epoch, lane, flagp);
     __syncthreads();
     BSIG_MSTAMP(2);
@@ -720,19 +719,21 @@ __device__ __forceinline__ void mdnn_stream_tile_workgroup(const MdnnArgs& p, fl
     p.params[off] = bw; p.m1[off] = bm; p.m2[off] = bv;
   }
   if (g == 0 && tid == 0 && p.n_updates > 0) {
+    // (the end of a launch as fit_protocol.h states it, written out: a call compiles to another register
+    // allocation of the update loop)
     int32_t* st = p.state;
-    reinterpret_cast<double*>(st + 12)[0] = b1t;
-    reinterpret_cast<double*>(st + 12)[1] = b2t;
-    reinterpret_cast<float*>(st)[4] = a0;
-    reinterpret_cast<float*>(st)[5] = a1;
+    reinterpret_cast<double*>(st + ST_BETA_POW)[0] = b1t;
+    reinterpret_cast<double*>(st + ST_BETA_POW)[1] = b2t;
+    reinterpret_cast<float*>(st)[ST_ADAM0] = a0;
+    reinterpret_cast<float*>(st)[ST_ADAM1] = a1;
     // (one jitter stream per update and per evaluation, in program order)
     int n_ev = 0;
     if (!DP && p.do_eval) {
-      n_ev = mdnn_evals_before(step0 + p.n_updates, p.eval_every) - mdnn_evals_before(step0, p.eval_every);
+      n_ev = evals_before(step0 + p.n_updates, p.eval_every) - evals_before(step0, p.eval_every);
       if (step0 + p.n_updates == p.n_total && (p.n_total - 1) % p.eval_every != 0) ++n_ev;
     }
-    reinterpret_cast<uint64_t*>(st + 8)[1] += (uint64_t)(p.n_updates + n_ev);
-    st[0] = step0 + p.n_updates;
+    reinterpret_cast<uint64_t*>(st + ST_RNG)[1] += (uint64_t)(p.n_updates + n_ev);
+    st[ST_STEP] = step0 + p.n_updates;
   }
 }
 

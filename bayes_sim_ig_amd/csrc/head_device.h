@@ -2,6 +2,7 @@
 // persistent update kernel (fit_persistent.hip).
 #pragma once
 #include "head.h"
+#include "fit_protocol.h"
 
 namespace bsig {
 
@@ -820,7 +821,7 @@ __device__ inline float granule_gather(unsigned long long* g, int G, uint32_t ta
     else granule_poll<4>(g, G, tag, lane, ok, v);
     if (__all(ok[0] && ok[1] && ok[2] && ok[3])) break;
     if (spin > (1u << 18)) {
-      if (flag && lane == 0) atomicOr(flag, 2);
+      if (flag && lane == 0) atomicOr(flag, kFlagTimeout);
       break;
     }
     __builtin_amdgcn_s_sleep(1);
@@ -851,7 +852,7 @@ __device__ inline void flags_wait(unsigned* flags, int G, unsigned epoch, int la
                     : nu == 3 ? flags_poll<3>(flags, G, epoch, lane) : flags_poll<4>(flags, G, epoch, lane);
     if (done) break;
     if (spin > (1u << 18)) {
-      if (flag && lane == 0) atomicOr(flag, 2);
+      if (flag && lane == 0) atomicOr(flag, kFlagTimeout);
       break;
     }
     __builtin_amdgcn_s_sleep(1);
@@ -869,7 +870,7 @@ __device__ inline void flag_wait_one(const unsigned* flags, int slot, unsigned e
     const unsigned x = __hip_atomic_load(flags + slot * kFlagStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (x >= epoch) break;
     if (spin > (1u << 17)) {
-      if (flag) atomicOr(flag, 2);
+      if (flag) atomicOr(flag, kFlagTimeout);
       break;
     }
     __builtin_amdgcn_s_sleep(3);
@@ -880,7 +881,7 @@ __device__ inline void granule_wait_one(const unsigned long long* g, int slot, u
     const unsigned long long x = __hip_atomic_load(g + slot * kGranStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if ((uint32_t)(x >> 32) == tag) break;
     if (spin > (1u << 17)) {
-      if (flag) atomicOr(flag, 2);
+      if (flag) atomicOr(flag, kFlagTimeout);
       break;
     }
     __builtin_amdgcn_s_sleep(3);

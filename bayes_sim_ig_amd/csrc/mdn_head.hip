@@ -254,7 +254,7 @@ __global__ void mdn_nll_kernel(HeadArgs a) {
       for (int j = tid; j < Nh; j += nt) o[j] = t[j];
     }
   }
-  if (bad && a.nonfinite) atomicOr(a.nonfinite, 1);
+  if (bad && a.nonfinite) atomicOr(a.nonfinite, kFlagNonfinite);
 }
 
 template <int WPB, int NQCAP = kElemsPerLane>
@@ -346,25 +346,13 @@ __global__ __launch_bounds__(WPB * 64) void mdn_nll_diag_wave_kernel(HeadArgs a)
     a.block_lse[blockIdx.x] = sl;
     if (a.block_uds) a.block_uds[blockIdx.x] = su;
   }
-  if (ro.bad && a.nonfinite) atomicOr(a.nonfinite, 1);
+  if (ro.bad && a.nonfinite) atomicOr(a.nonfinite, kFlagNonfinite);
 }
 
 // Fit-engine state advance (single writer; every reader of these words runs
 // in an earlier or a later kernel, or has published its last dependent value).
 __device__ inline void run_finish_hook(const FinishHook& hook) {
-  int32_t* st = hook.state;
-  if (hook.kind == 1) {           // end of the forward half of update `step`
-    // beta^t as running products (double): no pow() on the device
-    double* bp = reinterpret_cast<double*>(st + 12);
-    const double b1t = bp[0] * hook.beta1, b2t = bp[1] * hook.beta2;
-    bp[0] = b1t; bp[1] = b2t;
-    reinterpret_cast<float*>(st)[4] = (float)(hook.lr / (1.0 - b1t));
-    reinterpret_cast<float*>(st)[5] = (float)(1.0 / sqrt(1.0 - b2t));
-    st[0] = st[0] + 1;
-  } else {                        // end of a held-out evaluation
-    st[1] = st[1] + 1;
-  }
-  reinterpret_cast<uint64_t*>(st + 8)[1] += 1;   // jitter RNG stream
+  st_finish_hook(hook.state, hook.kind == 1, hook.beta1, hook.beta2, hook.lr);
 }
 
 // Finishing kernel: loss = -(sum of block partials) / batch; jitter-scale
@@ -388,7 +376,7 @@ __global__ __launch_bounds__(64 * kFinishLanes) void mdn_finish_kernel(
     if (threadIdx.x == 0) {
       const float l = -s / (float)batch;
       loss[loss_slot ? *loss_slot : 0] = l;
-      if (!isfinite(l) && nonfinite) atomicOr(nonfinite, 1);
+      if (!isfinite(l) && nonfinite) atomicOr(nonfinite, kFlagNonfinite);
     }
   }
   if (hook.state && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) run_finish_hook(hook);
@@ -489,7 +477,7 @@ __global__ __launch_bounds__(256) void mdn_outputs_kernel(
       bad |= !isfinite(v);
     }
   }
-  if (bad && nonfinite) atomicOr(nonfinite, 1);
+  if (bad && nonfinite) atomicOr(nonfinite, kFlagNonfinite);
 }
 
 // ---------------------------------------------------------------- host side

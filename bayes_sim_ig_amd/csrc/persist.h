@@ -47,7 +47,7 @@ struct PersistCommon {
   const float* y; int64_t ldy;            // targets, gathered through ids
   const int32_t* ids;                     // [n_updates*batch] minibatch row ids
   float* params; float* exp_avg; float* exp_avg_sq;   // flat buffers
-  int32_t* state;                         // the fit engine's 16-word state block
+  int32_t* state;                         // the fit engine's 16-word state block (fit_protocol.h)
   float* train_loss;                      // [n_updates]
   void* workspace; size_t workspace_bytes;
   // data-parallel ranks (null / 0 otherwise): the gradients of the update go to
@@ -65,7 +65,7 @@ struct PersistCommon {
   unsigned* xr_ready = nullptr; const unsigned* xr_done = nullptr; unsigned xr_base = 0;
   // held-out evaluations inside the launch (PersistEngine::eval_*): after update `it` of the call
   // with it % eval_every == 0 and after the last of its n_total updates (mdnn.py:235-242);
-  // evaluation k writes test_loss[state[1]] and advances state[1]
+  // evaluation k writes test_loss[state[ST_EVAL]] and advances that word (fit_protocol.h)
   int do_eval = 0; int eval_every = 1; int n_total = 0; int n_test = 0;
   const float* y_test = nullptr; int64_t ldy_test = 0;
   float* test_loss = nullptr;

@@ -57,7 +57,7 @@ __device__ __forceinline__ float adam_bias(float g, float& m, float& v, float w,
 // workgroup-uniform test of the time-out bit (set by any bounded poll on the chip)
 __device__ __forceinline__ bool run_aborted(int32_t* flagp, float* red, int tid) {
   if (tid == 0)
-    red[63] = (__hip_atomic_load(flagp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 2) ? 1.f : 0.f;
+    red[63] = (__hip_atomic_load(flagp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kFlagTimeout) ? 1.f : 0.f;
   __syncthreads();
   return red[63] != 0.f;
 }
@@ -127,9 +127,9 @@ __device__ __forceinline__ void xr_hand_off(unsigned* count, unsigned* ready, co
     __hip_atomic_store(ready, target, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   int spins = 0;
   while ((int)(__hip_atomic_load(done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) - target) < 0) {
-    if (++spins > (1 << 23)) { atomicOr(flagp, 2); break; }
+    if (++spins > (1 << 23)) { atomicOr(flagp, kFlagTimeout); break; }
     // (a run that gave up elsewhere: the workgroup that would release the exchange stream may be this one)
-    if ((spins & 1023) == 0 && (__hip_atomic_load(flagp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 2)) break;
+    if ((spins & 1023) == 0 && (__hip_atomic_load(flagp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kFlagTimeout)) break;
     __builtin_amdgcn_s_sleep(8);
   }
 }

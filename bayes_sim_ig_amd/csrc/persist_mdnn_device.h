@@ -199,10 +199,6 @@ __device__ __forceinline__ float4 fac_load4(const float* __restrict__ rowp, cons
     }                                                                                       \
   }
 
-// number of evaluation points it % every == 0 strictly before update s (the evaluation after
-// the last update of a call is not one of them)
-__device__ __forceinline__ int mdnn_evals_before(int s, int every) { return s == 0 ? 0 : (s - 1) / every + 1; }
-
 // ---- tile workgroups, evaluation number eidx: held-out summaries x this tile's weights (the
 //      A operand straight from memory: the minibatch tile in LDS is still needed for dW1)
 //      -> evaluation slabs, flag
@@ -288,10 +284,10 @@ __device__ __forceinline__ void mdnn_tile_workgroup(const MdnnArgs& p, float* sm
   const int wg = blockIdx.x, ks = wg % p.k_slices, nb = wg / p.k_slices;
   const int n0 = nb * kMNB, k0 = ks * kMC;
   const int B = p.B;
-  int32_t* flagp = p.state + 2;
-  const int step0 = p.state[0];
-  double b1t = reinterpret_cast<const double*>(p.state + 12)[0];
-  double b2t = reinterpret_cast<const double*>(p.state + 12)[1];
+  int32_t* flagp = p.state + ST_FLAGS;
+  const int step0 = p.state[ST_STEP];
+  double b1t = st_beta_pow(p.state)[0];
+  double b2t = st_beta_pow(p.state)[1];
   float a0 = 0.f, a1 = 0.f;
   const AdamK ak{1.0f - (float)p.beta1, (float)p.beta2, 1.0f - (float)p.beta2, p.adam_eps};
 
@@ -303,8 +299,8 @@ __device__ __forceinline__ void mdnn_tile_workgroup(const MdnnArgs& p, float* sm
   // first launch of a run_training call: a fresh optimizer (mdnn.py:203) -- the moments start
   // at zero in the registers, nobody has to clear (or read) them in memory
   const bool fresh = !DP && step0 == 0;
-  const float pa0 = pend ? reinterpret_cast<const float*>(p.state)[4] : 0.f;
-  const float pa1 = pend ? reinterpret_cast<const float*>(p.state)[5] : 0.f;
+  const float pa0 = pend ? st_adam(p.state)[0] : 0.f;
+  const float pa1 = pend ? st_adam(p.state)[1] : 0.f;
   // (three passes: every load is issued before the first store of a data-parallel launch's
   // pending Adam step -- interleaved, the possibly aliasing stores serialise the loads)
   if (DP && p.pair_ok) {
@@ -402,7 +398,7 @@ __device__ __forceinline__ void mdnn_tile_workgroup(const MdnnArgs& p, float* sm
   // update): sampled at entry, so that such a launch leaves at once instead of running its forward
   // product into the bounded polls of owners that have already left
   if (tid == 0)
-    red[63] = (__hip_atomic_load(flagp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 2) ? 1.f : 0.f;
+    red[63] = (__hip_atomic_load(flagp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kFlagTimeout) ? 1.f : 0.f;
   BSIG_MPF_LIST(BSIG_MPF_DECL)
   if (p.n_updates > 0) {
     const int64_t pf_row0 = (int64_t)step0 * B;
@@ -479,21 +475,22 @@ __device__ __forceinline__ void mdnn_tile_workgroup(const MdnnArgs& p, float* sm
 
     // ---- while the owners work: the evaluation due after the previous update (this tile
     //      still holds those weights), next summary tile, Adam scalars -------------------
+    // (eval_follows_update of fit_protocol.h, written out here and in the loops below: the call compiles to another
+    // register allocation of the update loop)
     if (__builtin_expect(p.do_eval && step > 0 && (step - 1) % p.eval_every == 0, 0))
-      mdnn_tile_eval(p, Wl, X, biasl, mdnn_evals_before(step, p.eval_every) - 1);
+      mdnn_tile_eval(p, Wl, X, biasl, evals_before(step, p.eval_every) - 1);
     // the time-out bit (set by any bounded poll on the chip), sampled off the critical path:
     // tested at the top of the next update
     if (tid_l == 0)
-      red[63] = (__hip_atomic_load(flagp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 2) ? 1.f : 0.f;
+      red[63] = (__hip_atomic_load(flagp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kFlagTimeout) ? 1.f : 0.f;
     if (t + 1 < p.n_updates) {
       const int64_t pf_row0 = (int64_t)(step + 1) * B;
       FacCols fcols{};
       if constexpr (FAC) fcols = fac_cols(k0 + BSIG_MPF_COL(), p.xS, p.xA);
       BSIG_MPF_LIST(BSIG_MPF_LOAD)
     }
-    b1t *= p.beta1; b2t *= p.beta2;
-    a0 = (float)(p.lr / (1.0 - b1t));
-    a1 = (float)(1.0 / sqrt(1.0 - b2t));
+    const AdamAdvance adv = adam_advance(b1t, b2t, p.beta1, p.beta2, p.lr);
+    b1t = adv.b1t; b2t = adv.b2t; a0 = adv.a0; a1 = adv.a1;
 
     if constexpr (FAC) {   // (diagnostics) the factor products of the next tile are in registers
       if (p.prof) { asm volatile("" :: "v"(pf0.x), "v"(pf12.w)); BSIG_MSTAMP(8); }
@@ -627,7 +624,7 @@ __device__ __forceinline__ void mdnn_tile_workgroup(const MdnnArgs& p, float* sm
     if (bias_pending && tid < kMNB) bias_step(tid);
     bias_pending = false;
     __syncthreads();
-    mdnn_tile_eval(p, Wl, X, biasl, mdnn_evals_before(p.n_total - 1, p.eval_every));
+    mdnn_tile_eval(p, Wl, X, biasl, evals_before(p.n_total - 1, p.eval_every));
   }
   // ---- write the tile back, advance the engine state ---------------------------
   if (col_ok && !DP) {
@@ -646,22 +643,24 @@ __device__ __forceinline__ void mdnn_tile_workgroup(const MdnnArgs& p, float* sm
   }
   // a resident launch that gave up must not leave the exchange stream waiting for gradients that will
   // never come: every wait of the call passes
-  if (xr && wg == 0 && tid == 0 && (__hip_atomic_load(flagp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 2))
+  if (xr && wg == 0 && tid == 0 && (__hip_atomic_load(flagp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kFlagTimeout))
     __hip_atomic_store(p.xr_ready, p.xr_base + (unsigned)p.n_updates, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   if (wg == 0 && tid == 0 && p.n_updates > 0) {
+    // (the end of a launch as fit_protocol.h states it, written out: a call compiles to another register
+    // allocation of the update loop)
     int32_t* st = p.state;
-    reinterpret_cast<double*>(st + 12)[0] = b1t;
-    reinterpret_cast<double*>(st + 12)[1] = b2t;
-    reinterpret_cast<float*>(st)[4] = a0;
-    reinterpret_cast<float*>(st)[5] = a1;
+    reinterpret_cast<double*>(st + ST_BETA_POW)[0] = b1t;
+    reinterpret_cast<double*>(st + ST_BETA_POW)[1] = b2t;
+    reinterpret_cast<float*>(st)[ST_ADAM0] = a0;
+    reinterpret_cast<float*>(st)[ST_ADAM1] = a1;
     // (one jitter stream per update and per evaluation, in program order)
     int n_ev = 0;
     if (p.do_eval) {
-      n_ev = mdnn_evals_before(step0 + p.n_updates, p.eval_every) - mdnn_evals_before(step0, p.eval_every);
+      n_ev = evals_before(step0 + p.n_updates, p.eval_every) - evals_before(step0, p.eval_every);
       if (!DP && step0 + p.n_updates == p.n_total && (p.n_total - 1) % p.eval_every != 0) ++n_ev;
     }
-    reinterpret_cast<uint64_t*>(st + 8)[1] += (uint64_t)(p.n_updates + n_ev);
-    st[0] = step0 + p.n_updates;
+    reinterpret_cast<uint64_t*>(st + ST_RNG)[1] += (uint64_t)(p.n_updates + n_ev);
+    st[ST_STEP] = step0 + p.n_updates;
   }
 }
 
@@ -764,17 +763,17 @@ __device__ __forceinline__ void mdnn_small_workgroup(const MdnnArgs& p, float* s
   const int B = p.B, DOP = p.FR + 4;
   const bool whead = WIDE && !is_w2;         // forms head outputs / d_out Wh for all rows (MdnnArgs)
   const int hb = sb - kMH / kMNB;
-  int32_t* flagp = p.state + 2;
-  const int step0 = p.state[0];
-  double b1t = reinterpret_cast<const double*>(p.state + 12)[0];
-  double b2t = reinterpret_cast<const double*>(p.state + 12)[1];
+  int32_t* flagp = p.state + ST_FLAGS;
+  const int step0 = p.state[ST_STEP];
+  double b1t = st_beta_pow(p.state)[0];
+  double b2t = st_beta_pow(p.state)[1];
   const AdamK ak{1.0f - (float)p.beta1, (float)p.beta2, 1.0f - (float)p.beta2, p.adam_eps};
 
   const bool pend = DP && p.adam_pending != 0;
   const bool xr = !DP && p.xr_ready != nullptr;      // resident across the gradient exchange (MdnnArgs)
   const bool fresh = !DP && step0 == 0;      // fresh optimizer: the moments start at zero
-  const float pa0 = pend ? reinterpret_cast<const float*>(p.state)[4] : 0.f;
-  const float pa1 = pend ? reinterpret_cast<const float*>(p.state)[5] : 0.f;
+  const float pa0 = pend ? st_adam(p.state)[0] : 0.f;
+  const float pa1 = pend ? st_adam(p.state)[1] : 0.f;
   // waves 0-3: element i of lane (h, l31) of wave w <-> W[n0 + acc_row(i, h)][32w + l31]
   float Wr[16], Mr[16], Vr[16];
   const int kcol = 32 * (w & 3) + l31;
@@ -857,9 +856,9 @@ __device__ __forceinline__ void mdnn_small_workgroup(const MdnnArgs& p, float* s
     const int step = step0 + t;
     const unsigned epoch = (unsigned)step + 1u;
     if (run_aborted(flagp, red, tid)) break;
-    b1t *= p.beta1; b2t *= p.beta2;
-    const float a0 = (float)(p.lr / (1.0 - b1t));
-    const float a1 = (float)(1.0 / sqrt(1.0 - b2t));
+    const AdamAdvance adv = adam_advance(b1t, b2t, p.beta1, p.beta2, p.lr);
+    b1t = adv.b1t; b2t = adv.b2t;
+    const float a0 = adv.a0, a1 = adv.a1;
     BSIG_MSTAMP(0);
 #define BSIG_LOAD_ACTIVATIONS() /* [B, 128], 16-byte loads */                                  \
     {                                                                                           \
@@ -1079,7 +1078,7 @@ __device__ __forceinline__ void mdnn_small_workgroup(const MdnnArgs& p, float* s
     if constexpr (WIDE && !DP) {
       if (__builtin_expect(p.do_eval && step > 0 && (step - 1) % p.eval_every == 0, 0)) {
         __syncthreads();
-        serve_eval(mdnn_evals_before(step, p.eval_every) - 1);
+        serve_eval(evals_before(step, p.eval_every) - 1);
       }
     }
     if (!DP) {
@@ -1094,7 +1093,7 @@ __device__ __forceinline__ void mdnn_small_workgroup(const MdnnArgs& p, float* s
   // the evaluation after the last update of the call (the operand copy holds that update's weights)
   if constexpr (WIDE && !DP) {
     if (p.do_eval && step0 + p.n_updates == p.n_total && !run_aborted(flagp, red, tid))
-      serve_eval(mdnn_evals_before(p.n_total - 1, p.eval_every));
+      serve_eval(evals_before(p.n_total - 1, p.eval_every));
   }
   if (!DP) {
 #pragma unroll
@@ -1314,10 +1313,10 @@ __device__ __forceinline__ void mdnn_owner_workgroup(const MdnnArgs& p, float* s
   const int c16_0 = tid_0 & 15, g_0 = (tid_0 & 63) >> 4;
   const int o = blockIdx.x - p.G1;
   const int r0 = o * MR;
-  int32_t* flagp = p.state + 2;
-  const int step0 = p.state[0];
-  const uint64_t rng_seed = reinterpret_cast<const uint64_t*>(p.state + 8)[0];
-  const uint64_t rng_ctr0 = reinterpret_cast<const uint64_t*>(p.state + 8)[1];
+  int32_t* flagp = p.state + ST_FLAGS;
+  const int step0 = p.state[ST_STEP];
+  const uint64_t rng_seed = st_rng(p.state)[0];
+  const uint64_t rng_ctr0 = st_rng(p.state)[1];
   HeadArgs a{};
   a.D = D; a.K = K; a.Nh = Nh; a.batch = B; a.from_tuple = 0;
   a.Ls = FULL ? D * (D - 1) / 2 : 0;
@@ -1529,15 +1528,15 @@ __device__ __forceinline__ void mdnn_owner_workgroup(const MdnnArgs& p, float* s
       const float sum = granule_gather(p.gran_eval + kGranArr, p.n_owner, etag, lane, flagp);
       if (lane == 0) {
         const float l = -sum / (float)p.n_test;
-        p.test_loss[p.state[1]] = l;
-        p.state[1] = p.state[1] + 1;
-        if (!isfinite(l)) atomicOr(flagp, 1);
+        p.test_loss[p.state[ST_EVAL]] = l;
+        p.state[ST_EVAL] = p.state[ST_EVAL] + 1;
+        if (!isfinite(l)) atomicOr(flagp, kFlagNonfinite);
       }
     }
-    if (bad) atomicOr(flagp, 1);
+    if (bad) atomicOr(flagp, kFlagNonfinite);
     __syncthreads();
   };
-  const int ev0 = p.do_eval ? mdnn_evals_before(step0, p.eval_every) : 0;
+  const int ev0 = p.do_eval ? evals_before(step0, p.eval_every) : 0;
   const RowGeom rg0 = row_geom(D, K, tid_0 & 63);   // (integer divisions by run-time values: once per launch)
 
   if (w_0 == 0) flags_wait(p.flag_pack, p.n_small, p.launch_tag, tid_0 & 63, flagp);
@@ -1576,8 +1575,10 @@ __device__ __forceinline__ void mdnn_owner_workgroup(const MdnnArgs& p, float* s
     }
     // one jitter stream per update and per evaluation, in program order; the row's draws do not depend
     // on the forward product: taken here, in the wait
+    // launch_stream(rng_ctr0, t, evaluations of the launch so far) of fit_protocol.h, written out (as the evaluation's
+    // below): the call compiles to another register allocation of the owners' loop
     a.stream_id = rng_ctr0 + (uint64_t)t +
-                  (uint64_t)(p.do_eval ? mdnn_evals_before(step, p.eval_every) - ev0 : 0);
+                  (uint64_t)(p.do_eval ? evals_before(step, p.eval_every) - ev0 : 0);
     float eu_pre[kElemsPerLane];
     if constexpr (!FULL) {
       if (fast) {
@@ -1887,7 +1888,7 @@ __device__ __forceinline__ void mdnn_owner_workgroup(const MdnnArgs& p, float* s
         }
       }
     }
-    if (ro.bad) atomicOr(flagp, 1);
+    if (ro.bad) atomicOr(flagp, kFlagNonfinite);
     if constexpr (WIDE) __builtin_amdgcn_s_waitcnt(0);   // d_out rows are out before the flag
     lds_barrier();
     BSIG_MSTAMP(14);
@@ -1979,22 +1980,21 @@ __device__ __forceinline__ void mdnn_owner_workgroup(const MdnnArgs& p, float* s
       if (lane == 0) {
         const float l = -s / (float)B;
         p.train_loss[step] = l;
-        if (!isfinite(l)) atomicOr(flagp, 1);
+        if (!isfinite(l)) atomicOr(flagp, kFlagNonfinite);
       }
     }
     // the evaluation due after the previous update: the tile workgroups formed its
     // first-layer products while this update's rows were being finished
     if (__builtin_expect(p.do_eval && step > 0 && (step - 1) % p.eval_every == 0, 0)) {
       __syncthreads();
-      owner_eval(mdnn_evals_before(step, p.eval_every) - 1,
-                 rng_ctr0 + (uint64_t)t + (uint64_t)(mdnn_evals_before(step, p.eval_every) - ev0) - 1u, step, false);
+      owner_eval(evals_before(step, p.eval_every) - 1,
+                 rng_ctr0 + (uint64_t)t + (uint64_t)(evals_before(step, p.eval_every) - ev0) - 1u, step, false);
     }
   }
   if (p.do_eval && step0 + p.n_updates == p.n_total && (!DP || p.n_updates == 0) &&
       !run_aborted(flagp, red, tid_0))
-    owner_eval(mdnn_evals_before(p.n_total - 1, p.eval_every),
-               rng_ctr0 + (uint64_t)p.n_updates +
-                   (uint64_t)(mdnn_evals_before(p.n_total - 1, p.eval_every) - ev0), p.n_total, true);
+    owner_eval(evals_before(p.n_total - 1, p.eval_every),
+               launch_stream(rng_ctr0, p.n_updates, evals_before(p.n_total - 1, p.eval_every), ev0), p.n_total, true);
 }
 
 // fit_persistent_mdnn_stream.hip

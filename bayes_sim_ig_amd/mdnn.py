@@ -78,11 +78,12 @@ class PendingLogs:
             train_list = [host[it] / world for it in eval_its]
             n_test_all = host[n_updates + n_e]
             test_list = [v / max(n_test_all, 1.0) for v in host[n_updates:n_updates + n_e]]
-            bad = (1 if host[n_updates + n_e + 1] > 0 else 0) | (2 if host[n_updates + n_e + 2] > 0 else 0)
+            bad = ((_lib.FLAG_NONFINITE if host[n_updates + n_e + 1] > 0 else 0) |
+                   (_lib.FLAG_TIMEOUT if host[n_updates + n_e + 2] > 0 else 0))
             self.n_test = int(n_test_all)
         else:
             train_list, test_list, bad = host[:n_e], host[n_e:2 * n_e], host[2 * n_e]
-        if int(bad) & 2:      # a bounded cross-workgroup poll of the persistent kernel gave up
+        if int(bad) & _lib.FLAG_TIMEOUT:      # a bounded cross-workgroup poll of the persistent kernel gave up
             raise PersistentTimeout('persistent update kernel timed out waiting for another workgroup: its '
                                     'workgroups (one per CU) were not all resident -- is the GPU shared with '
                                     'another process or partitioned?  The parameters and Adam moments of this '

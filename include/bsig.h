@@ -282,7 +282,7 @@ typedef struct bsig_fit_buffers {
   const int32_t* ids_table;      /* [n_updates, batch] minibatch row ids   */
   float* train_loss;             /* [n_updates]  loss of every update      */
   float* test_loss;              /* [n_evals]                              */
-  int32_t* state;                /* [16] int32 engine state (reset by begin); word 2 = non-finite flag */
+  int32_t* state;                /* [16] int32 engine state (reset by begin; csrc/fit_protocol.h); word 2 = flag word */
   void* workspace; size_t workspace_bytes;
   /* what the x_train rows hold: the summary itself (BSIG_X_ROWS), or the factor rows of a
    * cross-correlation summary (bsig_crosscorr_factors; cfg.input_dim = x_s*x_a + 2,
@@ -356,7 +356,7 @@ int bsig_fit_run(bsig_fit_plan* plan, int64_t n_updates, bsig_stream_t stream);
 int bsig_fit_updates(bsig_fit_plan* plan, int64_t n_updates, bsig_stream_t stream);
 /* The call's logs for ONE read-back: out[2*E + 1] (device) = train_loss at the E
  * logging points of mdnn.py:235-242 | test_loss[E] | the state block's flag word
- * (bit 0 non-finite, bit 1 poll time-out) as a float. */
+ * (bit 0 non-finite, bit 1 poll time-out: csrc/fit_protocol.h, which lays out the block) as a float. */
 int bsig_fit_pack_logs(bsig_fit_plan* plan, int64_t n_updates, float* out,
                        bsig_stream_t stream);
 /* A BLOCK of consecutive chunks in ONE launch of the persistent update kernel: what a caller that fits
@@ -405,6 +405,12 @@ int bsig_fit_run_block(bsig_fit_plan* plan, const float* feats, int64_t ld_feats
  * bsig_fit_is_persistent reports it, whether a single rank evaluates inside the launch, whether the
  * per-plan switch forces one chunk per launch. */
 int bsig_debug_block_launch(int engine_kind, int eval_in_launch, int forced_single);
+/* (tests) the logging schedule of a call of n_updates updates as every update engine takes it from
+ * csrc/fit_protocol.h (host arithmetic only): out[0] = every, out[1] = the number of logging points,
+ * out[2] = the evaluations of the n updates from step0 (the one after the last update included), then per
+ * update it < n_updates: out[3 + 2 it] = 1 where `it` is a logging point, out[4 + 2 it] = the evaluations
+ * before update `it`.  BSIG_EINVAL: a negative argument, step0 + n > n_updates, cap < 3 + 2 n_updates. */
+int bsig_debug_fit_schedule(int n_updates, int step0, int n, int32_t* out, int cap);
 /* Data-parallel pieces (BSIG_FIT_SPLIT_ADAM; mdnn.py:229-233 with the exchange
  * the reference does not have between loss.backward() and optimizer.step()):
  * bsig_fit_grad = forward + NLL + backward of one minibatch into `grads`
@@ -511,7 +517,7 @@ int bsig_fit_dp_graph_status(const bsig_fit_plan* plan, char* msg, size_t msg_by
 void bsig_debug_persist_profile(void* device_buffer);
 /* Tests: occupy `blocks` CUs for `ms` milliseconds with workgroups that hold `lds_bytes` of LDS
  * each, so that a persistent update launch behind it cannot get all its workgroups resident
- * (its bounded polls then time out: bit 1 of the state block's flag word; the Python mirror
+ * (its bounded polls then time out: bit 1 of the state block's flag word, csrc/fit_protocol.h; the Python mirror
  * restores the call's start state and repeats it on the per-phase kernels). */
 int bsig_debug_spin(int blocks, size_t lds_bytes, int ms, bsig_stream_t stream);
 /* Diagnostics / tests: how the persistent update kernel of the linear heads (MDRFF) would tile a

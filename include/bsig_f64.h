@@ -181,7 +181,7 @@ typedef struct bsig_fit64_buffers {
   const int32_t* ids_table;      /* [n_updates, batch] */
   double* train_loss;            /* [n_updates] */
   double* test_loss;             /* [n_evals]   */
-  int32_t* state;                /* [32] int32 engine state (reset by begin); word 2 = non-finite flag */
+  int32_t* state;                /* [32] int32 engine state (reset by begin; csrc/fit_protocol.h); word 2 = flag word */
   void* workspace; size_t workspace_bytes;
   int32_t x_kind;                /* BSIG_X_ROWS; factor rows: BSIG_EUNSUPPORTED */
 } bsig_fit64_buffers;

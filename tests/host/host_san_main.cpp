@@ -1,7 +1,7 @@
 // Host-side logic of libbsig_hip under AddressSanitizer + UndefinedBehaviorSanitizer (CPU build:
 // every source compiled --cuda-host-only, tools/build_host_san.sh): argument checks, parameter
-// layouts, GEMM planners, persistent-kernel geometry, plan binding, the external-exchange
-// communicator.  No kernel is launched (there may be no GPU); every call must return its
+// layouts, GEMM planners, persistent-kernel geometry, plan binding, the chunk protocol's logging
+// schedule, the external-exchange communicator.  No kernel is launched (there may be no GPU); every call must return its
 // documented code and leave a message in bsig_last_error() on failure.
 #include <cstdio>
 #include <cstdlib>
@@ -126,6 +126,41 @@ int main() {
   EXPECT(bsig_fit_create(&mdnn, 0, 0, 1, &none) == BSIG_EINVAL);
   bsig_fit_destroy(nullptr);
   EXPECT(bsig_fit_workspace_bytes(nullptr) == 0 && bsig_fit_is_persistent(nullptr) == 0);
+
+  // ---- the logging schedule of a call (csrc/fit_protocol.h through bsig_debug_fit_schedule) against a
+  //      restatement of mdnn.py:235 written here
+  {
+    std::vector<int> sizes;
+    for (int n = 0; n <= 64; ++n) sizes.push_back(n);
+    for (int n : {100, 101, 104, 1000}) sizes.push_back(n);
+    for (int n : sizes) {
+      const int every = n / 5 > 1 ? n / 5 : 1;
+      std::vector<int> logs(n, 0), before(n, 0);
+      int n_evals = 0;
+      for (int it = 0; it < n; ++it) {
+        before[it] = 0;
+        for (int j = 0; j < it; ++j) before[it] += j % every == 0 ? 1 : 0;
+        logs[it] = (it % every == 0 || it == n - 1) ? 1 : 0;
+        n_evals += logs[it];
+      }
+      std::vector<int32_t> out(3 + 2 * n, -7);          // exactly the documented size: ASan sees any overrun
+      EXPECT(bsig_debug_fit_schedule(n, 0, n, out.data(), (int)out.size()) == BSIG_OK);
+      EXPECT(out[0] == every && out[1] == n_evals && out[2] == n_evals);
+      for (int it = 0; it < n; ++it) EXPECT(out[3 + 2 * it] == logs[it] && out[4 + 2 * it] == before[it]);
+      int total = 0;
+      for (int step0 = 0; step0 < n; ++step0) {
+        EXPECT(bsig_debug_fit_schedule(n, step0, 1, out.data(), (int)out.size()) == BSIG_OK);
+        EXPECT(out[2] == logs[step0]);
+        total += out[2];
+      }
+      EXPECT(total == n_evals);
+      if (n > 0) EXPECT(bsig_debug_fit_schedule(n, 0, n, out.data(), (int)out.size() - 1) == BSIG_EINVAL);
+    }
+    int32_t o3[3];
+    EXPECT(bsig_debug_fit_schedule(-1, 0, 0, o3, 3) == BSIG_EINVAL && bsig_debug_fit_schedule(4, -1, 1, o3, 64) == BSIG_EINVAL);
+    EXPECT(bsig_debug_fit_schedule(4, 0, -1, o3, 64) == BSIG_EINVAL && bsig_debug_fit_schedule(4, 3, 2, o3, 64) == BSIG_EINVAL);
+    EXPECT(bsig_debug_fit_schedule(4, 0, 4, nullptr, 64) == BSIG_EINVAL && std::strlen(bsig_last_error()) > 0);
+  }
 
   // ---- communicator behind a caller-supplied exchange (bsig_comm_init_external)
   bsig_comm* comm = nullptr;

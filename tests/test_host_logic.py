@@ -654,3 +654,52 @@ def test_summary_path_argument_errors():
     rc, _ = summary_path(*S.query_args(c._replace(t=1, ta=1)))
     assert rc == _lib.BSIG_EINVAL and 'traj_len' in lib.bsig_last_error().decode()
     assert lib.bsig_debug_summary_path(0, 3, 5, 5, 3, 1, 0, 10, 64, 1, 0, None) == _lib.BSIG_EINVAL
+
+
+FIT_SCHEDULE_SIZES = list(range(1, 65)) + [100, 101, 104, 1000]
+
+
+def _fit_schedule(lib, n_updates, step0, n, cap=None):
+    cap = 3 + 2 * n_updates if cap is None else cap
+    out = (ctypes.c_int32 * max(cap, 1))()
+    rc = lib.bsig_debug_fit_schedule(n_updates, step0, n, out, cap)
+    return rc, list(out)
+
+
+def test_fit_schedule_matches_protocol_and_brute_force():
+    """The native statement of the chunk protocol's schedule (csrc/fit_protocol.h, through
+    bsig_debug_fit_schedule) against protocol.eval_updates and a restatement written here: `every`, the
+    logging points, the evaluations before each update, and the evaluations of a launch -- of every
+    single-update launch of a call (they add up to the call's) and of the one launch that is the call."""
+    from bayes_sim_ig_amd import protocol
+    lib = _lib.load()
+    for n_updates in FIT_SCHEDULE_SIZES:
+        every, its = protocol.eval_updates(n_updates)
+        brute_every = n_updates // 5 if n_updates // 5 > 1 else 1
+        brute = [it for it in range(n_updates) if it % brute_every == 0 or it == n_updates - 1]
+        assert every == brute_every and its == brute
+        rc, out = _fit_schedule(lib, n_updates, 0, n_updates)
+        assert rc == _lib.BSIG_OK
+        assert out[0] == every and out[1] == len(its) and out[2] == len(its)
+        assert [it for it in range(n_updates) if out[3 + 2 * it]] == its
+        # evaluations before update `it`: those after the updates j < it that the schedule names (the one after
+        # the last update follows it, so it precedes no update)
+        assert out[4:4 + 2 * n_updates:2] == [sum(1 for j in range(it) if j % every == 0) for it in range(n_updates)]
+        total = 0
+        for step0 in range(n_updates):
+            rc, one = _fit_schedule(lib, n_updates, step0, 1)
+            assert rc == _lib.BSIG_OK and one[:2] == out[:2]
+            assert one[2] == (1 if step0 in its else 0), (n_updates, step0)
+            total += one[2]
+        assert total == len(its)
+
+
+def test_fit_schedule_argument_errors():
+    lib = _lib.load()
+    assert _fit_schedule(lib, 10, 0, 10)[0] == _lib.BSIG_OK
+    assert _fit_schedule(lib, 0, 0, 0, cap=3) == (_lib.BSIG_OK, [1, 0, 0])
+    for args in ((-1, 0, 0), (10, -1, 1), (10, 0, -1), (10, 5, 6)):
+        assert _fit_schedule(lib, *args, cap=64)[0] == _lib.BSIG_EINVAL, args
+    assert _fit_schedule(lib, 10, 0, 10, cap=22)[0] == _lib.BSIG_EINVAL          # 3 + 2 * 10 = 23 needed
+    assert 'debug_fit_schedule' in lib.bsig_last_error().decode()
+    assert lib.bsig_debug_fit_schedule(10, 0, 10, None, 64) == _lib.BSIG_EINVAL
