@@ -193,6 +193,7 @@ _PROTOS = {
     'bsig_fit_block_chunks': (C.c_int, [vp, i64]),
     'bsig_fit_run_block': (C.c_int, [vp, vp, i64, i64, vp, i64, vp, i64, vp, vp, C.c_int, vp, vp, vp, i64, vp]),
     'bsig_debug_block_launch': (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    'bsig_debug_fit_deferred': (C.c_int, [vp, vp]),
     'bsig_debug_fit_schedule': (C.c_int, [C.c_int, C.c_int, C.c_int, vp, C.c_int]),
     'bsig_fit_run_dp': (C.c_int, [vp, vp, i64, vp, vp]),
 }

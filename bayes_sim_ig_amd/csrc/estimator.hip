@@ -382,6 +382,11 @@ struct bsig_fit_plan {
   bool resident_ran;           // a resident data-parallel call ran since bsig_fit_begin (its workgroup count word is used up)
   bool adam_pending;           // ... data-parallel: the Adam step on the reduced gradients is
                                // taken by the next launch (or flushed before an evaluation)
+  // single rank, linear heads: the held-out evaluations run in kernels behind the update launch, from weight
+  // snapshots (persist.h: DeferredEval) -- unless BSIG_EVAL_IN_LAUNCH=1 or the snapshots would exceed their cap
+  bool eval_deferred;
+  bsig::DeferredEval deferred;
+  int64_t n_deferred, n_in_launch;   // (bsig_debug_fit_deferred) launches of a single rank's whole call, either way
   hipStream_t cap_stream;
   hipGraphExec_t g_step, g_grad, g_apply, g_eval;
   bool graphs_ready;           // ensure_graphs has run for this binding (g_eval may legitimately be absent)
@@ -466,7 +471,7 @@ struct BlockRun {
   const bsig_fit_chunk* chunks; int n_chunks, max_test, total_updates; float* train_loss; float* test_loss;
 };
 static int enqueue_persistent(bsig_fit_plan* p, int n, hipStream_t st, int eval_total = 0,
-                              const CommXr* xr = nullptr, const BlockRun* blk = nullptr) {
+                              const CommXr* xr = nullptr, const BlockRun* blk = nullptr, bool deferred = false) {
   PlanMem m; plan_mem(p, &m);
   const bsig_fit_buffers& b = p->buf;
   PersistCommon c;
@@ -502,6 +507,16 @@ static int enqueue_persistent(bsig_fit_plan* p, int n, hipStream_t st, int eval_
       pb.y_test = blk->y; pb.ldy_test = blk->ldy; pb.n_test = blk->max_test;
       pb.chunks = blk->chunks; pb.n_chunks = blk->n_chunks;
     }
+    // a single rank's whole call (or block of calls): the evaluations behind the launch, where the plan's
+    // snapshot memory holds them (else, as ever, inside it)
+    if (deferred && p->eval_deferred && eval_total == n && !p->split_adam && !xr &&
+        deferred_eval_reserve(p->ug, (int)count_logging_points(n) * (blk ? blk->n_chunks : 1), &p->deferred)) {
+      pb.deferred = p->deferred.mem;
+      ++p->n_deferred;
+      BSIG_TRY(persist_run(persist_shape(p), p->ug, pb, n, st));
+      return deferred_eval_run(persist_shape(p), p->ug, pb, n, st);
+    }
+    if (deferred) ++p->n_in_launch;
     return persist_run(persist_shape(p), p->ug, pb, n, st);
   }
   PersistMdnnBuffers pb;
@@ -810,6 +825,7 @@ extern "C" int bsig_fit_create_ex(const bsig_mdn_cfg* cfg, int64_t batch,
   if (set("BSIG_NO_INKERNEL_EVAL")) p->eng.eval_single = p->eng.eval_dp = false;
   p->eng.block_launch = block_launch_resolved(p->eng.kind, p->eng.eval_single, set("BSIG_FIT_CHUNK_PER_LAUNCH"));
   p->eng.workspace_bytes = round_up<size_t>(p->eng.workspace_bytes, 256);
+  p->eval_deferred = p->eng.kind == 1 && p->eng.eval_single && !set("BSIG_EVAL_IN_LAUNCH");
   if (p->hoist) {
     p->feats_bytes = round_up<size_t>(feats, 256);
     const int64_t mf = cfg->rff_cos_only ? cfg->rff_feats : cfg->rff_feats / 2;
@@ -826,6 +842,7 @@ extern "C" void bsig_fit_destroy(bsig_fit_plan* p) {
   if (!p) return;
   drop_graphs(p);
   if (p->cap_stream) (void)hipStreamDestroy(p->cap_stream);
+  deferred_eval_free(&p->deferred);
   delete p;
 }
 
@@ -1123,7 +1140,7 @@ extern "C" int bsig_fit_run(bsig_fit_plan* p, int64_t n_updates, bsig_stream_t s
   // plans covered by a persistent kernel: the whole call, evaluations included, is ONE launch
   if (engine(p) && !p->split_adam && n_updates >= 1 && p->buf.n_test >= 1 &&
       evals_in_launch(p, false, p->buf.x_test_factors != nullptr))
-    return enqueue_persistent(p, (int)n_updates, st, (int)n_updates);
+    return enqueue_persistent(p, (int)n_updates, st, (int)n_updates, nullptr, nullptr, true);
   const int64_t every = eval_every(n_updates);
   int64_t done = 0;
   for (int64_t it = 0; it < n_updates; ++it) {
@@ -1164,6 +1181,12 @@ __global__ void pack_block_logs_kernel(const float* train_loss, const float* tes
                  out + (int64_t)blockIdx.x * (2 * n_evals + 1), (int)threadIdx.x, (int)blockDim.x);
 }
 }  // namespace bsig
+
+extern "C" int bsig_debug_fit_deferred(const bsig_fit_plan* p, int64_t* out) {
+  BSIG_REQUIRE(p && out, "debug_fit_deferred: null");
+  out[0] = p->n_deferred; out[1] = p->n_in_launch; out[2] = (int64_t)p->deferred.bytes;
+  return BSIG_OK;
+}
 
 extern "C" int bsig_debug_block_launch(int engine_kind, int eval_in_launch, int forced_single) {
   return block_launch_resolved(engine_kind, eval_in_launch != 0, forced_single != 0) ? 1 : 0;
@@ -1219,7 +1242,7 @@ extern "C" int bsig_fit_run_block(bsig_fit_plan* p, const float* feats, int64_t 
   BSIG_TRY(fit_begin(p, chunks_host[0].seed, norm_batch, stream, false));
   hipStream_t st = as_stream(stream);
   const BlockRun blk{feats, ld_feats, y, ldy, ids, chunks_dev, n_chunks, max_test, n_chunks * n_upd, train_loss, test_loss};
-  BSIG_TRY(enqueue_persistent(p, n_upd, st, n_upd, nullptr, &blk));
+  BSIG_TRY(enqueue_persistent(p, n_upd, st, n_upd, nullptr, &blk, true));
   hipLaunchKernelGGL(pack_block_logs_kernel, dim3(n_chunks), dim3(64), 0, st, train_loss, test_loss, p->buf.state,
                      chunks_dev, n_ev, packed_logs);
   BSIG_CHECK_LAUNCH("pack_block_logs");

@@ -5,8 +5,8 @@
 // A launch runs the updates of one run_training call -- or of a BLOCK of consecutive calls
 // (bsig_fit_run_block: up to BayesSim.FIT_BLOCK_CHUNKS chunks of a fit): the weight tiles stay in LDS across
 // the chunk boundaries, where only the Adam moments, the step count and the chunk's rows, ids, seed and log
-// slots change (UCk, read from a chunk table), and the evaluation after a chunk's last update runs in the
-// waits of the next chunk's first updates instead of serially behind the launch.
+// slots change (UCk, read from a chunk table), and the weights the evaluation after a chunk's last update
+// needs are snapshotted in the wait of the next chunk's first update (in front of its Adam phase).
 //
 // Round 4: UNIFIED workgroups.  The head matrix W [Nh, F] is tiled over the WHOLE chip:
 // workgroup (nb, ks) owns the 16 x KS tile W[16nb.., KS*ks..] (NT = 1; 32 rows with NT = 2
@@ -33,10 +33,16 @@
 //      d_out transposed into LDS (jitter-scale gradient term applied on the way), forms
 //      dW = d_out^T F (MFMA 16x16x4, both operands 16-byte LDS reads along the minibatch
 //      axis) and applies Adam to its tile; the k-slice-0 workgroups also own the biases.
-// Held-out evaluations (mdnn.py:235-242) run inside the launch: the tile part (held-out
+// Held-out evaluations (mdnn.py:235-242).  A single rank's launch (SNAP instantiation) does not run them: in
+// the wait of the update after an evaluation point every tile workgroup copies its weight tile from LDS to
+// a snapshot buffer, and the kernels of fit_deferred_eval.hip, enqueued behind the launch, evaluate from
+// the snapshots -- an evaluation feeds nothing back into the weights, and inside the launch it made every
+// update next to it several us longer.  The data-parallel instantiations (and BSIG_EVAL_IN_LAUNCH=1, or a
+// launch whose snapshots would exceed their cap) run them inside the launch: the tile part (held-out
 // rows x the evaluated weights, still in LDS) in the wait of the update after the
 // evaluation point, the row part one update later by workgroups that own no minibatch
-// row (they idle in that wait) -- three evaluation slab buffers make that safe.
+// row (they idle in that wait) -- three evaluation slab buffers make that safe.  Both run the
+// evaluation code of persist_linear_device.h: same bits.
 // Cross-workgroup data: write-through stores / cache-bypassing loads + flags, as in v1
 // (persist_device.h); all polls are bounded (bit 1 of the state block's flag word).
 #include "persist.h"
@@ -44,130 +50,9 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "head_device.h"
-#include "persist_device.h"
+#include "persist_linear_device.h"
 
 namespace bsig {
-
-constexpr int kUT = 512;             // threads per workgroup (8 wavefronts)
-constexpr int kUSteps = 18;          // 16-column steps of a k-slice a lane can hold (18 x 16 B registers)
-constexpr int kUGroup = 6;           // k-slices are 1, 2 or 3 groups of 6 steps (96 / 192 / 288 columns): the
-                                     // unrolled step loops branch once per group, not once per step
-constexpr int kUMT = 7;              // 16-row m-tiles of the minibatch (<= 112 rows): fixed, so that the
-                                     // dW product's loop over the minibatch has no run-time bound
-constexpr int kULds = 160 * 1024;
-constexpr int kUProf = 8;            // profiled updates per launch
-// Pitch of the F^T / d_out^T rows in LDS (floats): minibatches of up to 112 rows.  = 4 (mod 8):
-// conflict-free 16-byte reads down 8 rows and 4-byte writes across rows.  A compile-time constant:
-// the 72 transposed writes of a lane per update are then immediate offsets off one address --
-// with a run-time pitch the compiler keeps 72 loop-invariant addresses in registers (or scratch).
-constexpr int kUFP = 116;
-
-struct UArgs {
-  int B, Bp, MT;                     // minibatch rows, padded to 16, 16-row m-tiles
-  int Fdim, KS, ksteps, KB, WP;      // features, k-slice width, its 16-column steps / blocks, pitch of W rows
-  int Nh, NhP, D, K;
-  int n_blocks, k_slices, G, T, n_owner, R;
-  int n_updates, xs_floats;
-  int fast_rows;                     // (A/B runs: BSIG_PERSIST_FAST_ROWS=0 keeps the shape-generic row)
-  const float* feats; int64_t ld_feats; const int32_t* feat_ids;
-  const float* y; int64_t ldy; const int32_t* ids;
-  float* params; float* m1; float* m2; int64_t w_off, b_off;
-  int32_t* state; float* train_loss;
-  double lr, beta1, beta2;
-  float adam_eps, eps_noise, min_w, ll_limit, inv_norm;
-  float* slabs; float* d_out; float* e_out; unsigned* flag_fwd; unsigned long long* gran;
-  unsigned long long* gran_rep;      // [2][8][kGranArr] replicated granules (gran_rep())
-  // data-parallel ranks (one update per launch; see PersistBuffers)
-  float* grads; int adam_pending; int quad_ok;
-  // data-parallel rank RESIDENT across the exchange (XR instantiation; see PersistBuffers)
-  unsigned* xr_ready; const unsigned* xr_done; unsigned* xr_count; unsigned xr_base;   // (xr_count: a word of the sync region)
-  // held-out evaluations inside the launch
-  int do_eval, eval_every, n_total, n_test, eval_passes, NE, RE;
-  int64_t eval_row0;
-  const float* y_test; int64_t ldy_test;
-  float* test_loss;
-  float* eval_slabs;                 // [3][eval_passes][k_slices][B][NhP] (eval_passes: the most of any chunk)
-  unsigned* flag_eval;               // [G]   evaluation number + 1
-  unsigned long long* gran_eval;     // [2][kGranArr]
-  long long* prof;                   // diagnostics: [T][kUProf][16] wall-clock stamps, or null
-  int prof_t0;                       // ... of updates prof_t0 .. prof_t0 + kUProf of the launch (BSIG_PROF_T0)
-  // a block of chunks in one launch (persist.h: PersistBuffers::chunks): entry c replaces, at the boundary in
-  // front of chunk c, what the fields above say about ONE chunk (n_updates, n_total, eval_every, n_test,
-  // eval_row0, y_test, the state block's step / seed / stream counter); feats, y, ids, train_loss and
-  // test_loss are then the block's.  null: one chunk, described by the fields above (n_chunks = 1).
-  const bsig_fit_chunk* chunks; int n_chunks;
-};
-
-// What a workgroup keeps of the chunk it is in (workgroup-uniform; read at the chunk boundary)
-struct UCk {
-  int step0, n_updates, n_total, eval_every, do_eval;
-  // Flag and granule tags count the updates / evaluations of the LAUNCH (they must stay monotonic across
-  // chunks): update t of the chunk has epoch ubase + step + 1, evaluation e the tag evbase + e + 1.  The
-  // widest tag is epoch * 4 + 3 in 32 bits: a launch holds fewer than 2^30 updates (persist_run checks;
-  // 32 chunks of 100 updates and 6 evaluations reach epoch 3200 and evaluation tag 192).  Adam, the jitter
-  // streams and the evaluation schedule count chunk-local steps.
-  unsigned ubase, evbase;
-  // (The update loops index the ids and the train-loss log by the update of the LAUNCH, epoch - 1: the chunks'
-  // ids and log slots follow each other, the ids are rows of the block; n_updates, eval_every and do_eval are the
-  // same for every chunk of a launch -- the loops read the launch's arguments, which cost no live register.)
-  uint64_t seed, rng_ctr0;
-};
-__device__ __forceinline__ int u_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ int64_t u_uniform(int64_t v) {
-  return (int64_t)(((uint64_t)(uint32_t)u_uniform((int)((uint64_t)v >> 32)) << 32) | (uint32_t)u_uniform((int)(uint64_t)v));
-}
-__device__ __forceinline__ void u_chunk_load(const UArgs& p, int c, UCk& k) {
-  if (p.chunks == nullptr) {
-    k.step0 = p.state[ST_STEP]; k.n_updates = p.n_updates; k.n_total = p.n_total; k.eval_every = p.eval_every;
-    k.do_eval = p.do_eval; k.ubase = 0u; k.evbase = 0u;
-    k.seed = st_rng(p.state)[0];
-    k.rng_ctr0 = st_rng(p.state)[1];
-    return;
-  }
-  const bsig_fit_chunk& e = p.chunks[c];
-  k.step0 = 0; k.n_updates = u_uniform(e.n_updates); k.n_total = k.n_updates; k.eval_every = u_uniform(e.eval_every);
-  k.do_eval = 1; k.ubase = (unsigned)u_uniform(e.upd_base); k.evbase = (unsigned)u_uniform(e.eval_base);
-  k.seed = (uint64_t)u_uniform((int64_t)e.seed); k.rng_ctr0 = (uint64_t)u_uniform((int64_t)e.rng_ctr0);
-}
-
-// One held-out evaluation: evaluation e (chunk-local) of chunk c.  Built where it is used (the evaluation
-// whose parts run in the waits of the NEXT chunk's first updates still belongs to its own chunk).
-struct UEval {
-  int n_test, passes; int64_t row0;  // held-out feature rows feats[row0 .. row0 + n_test)
-  const float* y_test; int64_t ldy_test;
-  float* out;                        // its slot of the test-loss log (null: test_loss[state[ST_EVAL]], one chunk)
-  unsigned gidx;                     // evaluation number of the launch: slab buffer gidx % 3, tag gidx + 1
-  uint64_t seed, stream;             // jitter stream (one per update and per evaluation, in program order:
-                                     // the per-phase path's numbering)
-};
-__device__ __forceinline__ UEval u_eval_of(const UArgs& p, int c, int e) {
-  UEval v;
-  int every, n_total, step0;
-  uint64_t ctr0;
-  if (p.chunks == nullptr) {
-    v.n_test = p.n_test; v.row0 = p.eval_row0; v.y_test = p.y_test; v.ldy_test = p.ldy_test; v.out = nullptr;
-    v.gidx = (unsigned)e; every = p.eval_every; n_total = p.n_total; step0 = p.state[ST_STEP];
-    v.seed = st_rng(p.state)[0];
-    ctr0 = st_rng(p.state)[1];
-  } else {
-    const bsig_fit_chunk& k = p.chunks[c];
-    v.n_test = u_uniform(k.n_test); v.row0 = u_uniform(k.row0) + u_uniform(k.n_train);
-    v.y_test = p.y + v.row0 * p.ldy; v.ldy_test = p.ldy; v.out = p.test_loss + u_uniform(k.test_slot) + e;
-    v.gidx = (unsigned)u_uniform(k.eval_base) + (unsigned)e; every = u_uniform(k.eval_every);
-    n_total = u_uniform(k.n_updates); step0 = 0;
-    v.seed = (uint64_t)u_uniform((int64_t)k.seed); ctr0 = (uint64_t)u_uniform((int64_t)k.rng_ctr0);
-  }
-  v.passes = (v.n_test + p.B - 1) / p.B;
-  const int at = eval_at_step(e, every, n_total);
-  const int ev0 = p.do_eval || p.chunks ? evals_before(step0, every) : 0;
-  v.stream = launch_stream(ctr0, at - step0, e, ev0);
-  return v;
-}
-
-__device__ __forceinline__ f32x4 umfma(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 // Workgroup id -> roles.  Workgroup ids go round the 8 XCDs (id mod 8 is the XCD, measured).  The
 // G tiles are dealt to the XCDs in contiguous runs -- tile (nb, ks) is number ks * n_blocks + nb,
@@ -241,31 +126,6 @@ __device__ __forceinline__ void granule_publish8(const UArgs& p, int arr, int sl
   if (lane < 8) granule_publish(gran_rep(p, arr, lane), slot, tag, v);
 }
 
-// A row owner's sum over the k-slices: out[r * out_pitch + col] = sum_z slabs[z * zs + rowoff(r) + col]
-// for r < nrows, col < n_cols (float offsets; `slabs` workgroup-uniform), slices added in order, up
-// to 16 loads in flight per lane -- buffer loads: one address register per lane, the slice offset
-// is scalar.  `fn(col, v)` sees every sum.
-template <typename RowOff, typename F>
-__device__ __forceinline__ void u_rows_sum(const float* slabs, RowOff&& rowoff, int k_slices, int zs, int nrows,
-                                           int n_cols, float* out, int out_pitch, int tid, F&& fn) {
-  const __amdgpu_buffer_rsrc_t sr = xwg_buffer(slabs);
-  for (int idx = tid; idx < nrows * n_cols; idx += kUT) {
-    const int r = idx / n_cols, col = idx - r * n_cols;
-    const int voff = (rowoff(r) + col) * 4;
-    float v = 0.f;
-    for (int z = 0; z < k_slices; z += 16) {
-      float q[16];
-#pragma unroll
-      for (int u = 0; u < 16; ++u)
-        q[u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(sr, voff, min(z + u, k_slices - 1) * zs * 4, kXwgPolicy));
-#pragma unroll
-      for (int u = 0; u < 16; ++u)
-        if (z + u < k_slices) v += q[u];
-    }
-    out[r * out_pitch + col] = v;
-    fn(col, v);
-  }
-}
 
 // The same sum in ONE round trip for an owner without a tile (its LDS is free): thread (quad column,
 // slice group sg) adds the slices sg, sg + SG, ... of 4 adjacent columns (16-byte loads, <= 8 in
@@ -307,143 +167,6 @@ __device__ __forceinline__ void u_rows_sum4(const float* slabs, RowOff&& rowoff,
   }
 }
 
-// ---- tile part of held-out evaluation ev: held-out rows x this tile's weights (the B operand
-//      straight from memory, six 16-column steps at a time) -> evaluation slab buffer gidx % 3, flag
-template <int NT>
-__device__ __forceinline__ void u_tile_eval(const UArgs& p, const float* Wl, const float* biasl, int slot,
-                                            int ks, int n0, int k0, const UEval& ev) {
-  int tid = threadIdx.x;
-  asm volatile("" : "+v"(tid));    // (nothing below may be computed ahead of the update loop and kept live in it)
-  const int lane = tid & 63, w = tid >> 6, c16 = lane & 15, g4 = lane >> 4;
-  const int B = p.B, NhP = p.NhP;
-  for (int pass = 0; pass < ev.passes; ++pass) {
-    const int rows = min(B, ev.n_test - pass * B);
-    if (rows <= 0) break;
-    if (w < p.MT) {
-      f32x4 acc[NT];
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-        acc[nt] = ks == 0 ? *reinterpret_cast<const f32x4*>(biasl + 16 * nt + 4 * g4) : zero;
-      }
-      const int64_t r = ev.row0 + pass * B + min(16 * w + c16, rows - 1);
-      const float* src = p.feats + r * p.ld_feats;
-      const float* ap = Wl + c16 * p.WP + 4 * g4;
-#pragma unroll 1
-      for (int s0 = 0; s0 < p.ksteps; s0 += kUGroup) {
-        f32x4 breg[kUGroup];
-#pragma unroll
-        for (int q = 0; q < kUGroup; ++q) {
-          const int col = k0 + 16 * (s0 + q) + 4 * g4;
-          const f32x4 v = *reinterpret_cast<const f32x4*>(src + min((int64_t)col, p.ld_feats - 4));
-          const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-          breg[q] = col < p.Fdim ? v : zero;
-        }
-#pragma unroll
-        for (int q = 0; q < kUGroup; ++q) {
-#pragma unroll
-          for (int nt = 0; nt < NT; ++nt) {
-            const f32x4 a4 = *reinterpret_cast<const f32x4*>(ap + nt * 16 * p.WP + 16 * (s0 + q));
-            acc[nt] = umfma(a4[0], breg[q][0], acc[nt]);
-            acc[nt] = umfma(a4[1], breg[q][1], acc[nt]);
-            acc[nt] = umfma(a4[2], breg[q][2], acc[nt]);
-            acc[nt] = umfma(a4[3], breg[q][3], acc[nt]);
-          }
-        }
-      }
-      if (16 * w + c16 < rows) {
-        const __amdgpu_buffer_rsrc_t sr = xwg_buffer(
-            p.eval_slabs + ((((int64_t)(ev.gidx % 3u) * p.eval_passes + pass) * p.k_slices + ks) * B) * NhP + n0);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-          xwg_store4(sr, (16 * w + c16) * NhP + 16 * nt + 4 * g4, acc[nt][0], acc[nt][1], acc[nt][2], acc[nt][3]);
-      }
-    }
-  }
-  __builtin_amdgcn_s_waitcnt(0);
-  __syncthreads();
-  if (tid == 0) flag_raise(p.flag_eval, slot, ev.gidx + 1u);
-}
-
-// ---- row part of held-out evaluation ev by evaluation owner `eo`:
-//      held-out rows eo, eo + NE, ... (RE of them, one wavefront each), forward only
-__device__ __forceinline__ void u_owner_eval(const UArgs& p, float* XS, float* red, int eo, const UEval& ev,
-                                             const HeadArgs& a) {
-  int tid = threadIdx.x;
-  asm volatile("" : "+v"(tid));
-  const int lane = tid & 63, w = tid >> 6;
-  const int B = p.B, Nh = p.Nh, NhP = p.NhP, D = p.D, K = p.K, DK = D * K;
-  const int per_wave = Nh + D + 3 * K;
-  int32_t* flagp = p.state + ST_FLAGS;
-  const unsigned etag = ev.gidx + 1u;
-  if (w == 0) flags_wait(p.flag_eval, p.G, etag, lane, flagp);
-  __syncthreads();
-  const int nr = eo < ev.n_test ? min(p.RE, (ev.n_test - eo + p.NE - 1) / p.NE) : 0;   // this owner's rows
-  const float* ebase = p.eval_slabs + (int64_t)(ev.gidx % 3u) * p.eval_passes * p.k_slices * B * NhP;
-  float eacc = 0.f;
-  u_rows_sum(ebase,
-             [&](int r) {
-               const int erow = eo + p.NE * r, pass = erow / B, rb = erow - pass * B;
-               return (pass * p.k_slices * B + rb) * NhP;
-             },
-             p.k_slices, B * NhP, nr, Nh, XS, per_wave, tid,
-             [&](int col, float v) { if (col >= K + DK && col < K + 2 * DK) eacc += expf(v); });
-  eacc = wave_sum_dpp(eacc);
-  if (lane == 0) red[w] = eacc;
-  __syncthreads();
-  if (tid == 0) {
-    float sx = 0.f;
-    for (int q = 0; q < kUT / 64; ++q) sx += red[q];
-    granule_publish(p.gran_eval, eo, etag, sx);
-  }
-  const int erow = eo + p.NE * w;
-  const bool act = w < nr;
-  float* tile = XS + w * per_wave;
-  float* yv = tile + Nh;
-  float* rk = yv + D;
-  float* lpk = rk + K;
-  float* dlg = lpk + K;
-  if (act)
-    for (int j = lane; j < D; j += 64) yv[j] = ev.y_test[(int64_t)erow * ev.ldy_test + j];
-  RowOut ro;
-  ro.lse = 0.f; ro.uds = 0.f; ro.bad = false;
-#pragma unroll
-  for (int q = 0; q < kElemsPerLane; ++q) ro.esg0[q] = 0.f;
-  if (w < p.RE) {
-    HeadArgs ae = a;
-    ae.d_out = nullptr;                    // forward only
-    ae.batch = ev.n_test;
-    ae.seed = ev.seed;
-    ae.stream_id = ev.stream;
-    diag_row(ae, erow, act, lane, tile, yv, rk, lpk, dlg,
-             [&] {
-               return p.eps_noise != 0.f
-                          ? p.eps_noise * (granule_gather(p.gran_eval, p.NE, etag, lane, flagp) /
-                                           ((float)ev.n_test * (float)DK))
-                          : 0.f;
-             },
-             ro);
-  }
-  if (lane == 0) red[16 + w] = act ? ro.lse : 0.f;
-  __syncthreads();
-  if (tid == 0) {
-    float sl = 0.f;
-    for (int q = 0; q < kUT / 64; ++q) sl += red[16 + q];
-    granule_publish(p.gran_eval + kGranArr, eo, etag, sl);
-  }
-  if (eo == 0 && w == 0) {
-    const float sum = granule_gather(p.gran_eval + kGranArr, p.NE, etag, lane, flagp);
-    if (lane == 0) {
-      const float l = -sum / (float)ev.n_test;
-      if (ev.out) *ev.out = l;
-      else p.test_loss[p.state[ST_EVAL]] = l;
-      p.state[ST_EVAL] = p.state[ST_EVAL] + 1;
-      if (!isfinite(l)) atomicOr(flagp, kFlagNonfinite);
-    }
-  }
-  if (ro.bad) atomicOr(flagp, kFlagNonfinite);
-  __syncthreads();
-}
 
 // ---- the row-owner role ---------------------------------------------------------------------
 // (functions of their own with a context struct, not code inside the tile workgroups' loop: a
@@ -462,10 +185,7 @@ __device__ __forceinline__ void u_own_init(const UArgs& p, UOwn& o, int own, boo
                                            float* red, float* part, int lane0) {
   o.own = own; o.r0 = own * p.R; o.per_wave = p.Nh + p.D + 3 * p.K; o.has_tile = has_tile;
   o.XS = XS; o.red = red; o.part = part;
-  o.a = HeadArgs{};
-  o.a.D = p.D; o.a.K = p.K; o.a.Nh = p.Nh; o.a.batch = p.B; o.a.from_tuple = 0;
-  o.a.min_w = p.min_w; o.a.ll_limit = p.ll_limit; o.a.inv_norm = p.inv_norm;
-  o.a.eps_noise = p.eps_noise; o.a.d_out = p.d_out;
+  o.a = u_head_args(p);
   o.rg = row_geom(p.D, p.K, lane0);       // (integer divisions by run-time values: once per launch)
   o.norm = (float)p.B * (float)(p.D * p.K);
   o.flagp = p.state + ST_FLAGS;
@@ -890,9 +610,32 @@ __device__ __forceinline__ void u_own_update_fast(const UArgs& p, UOwn& o, int t
 // workgroup polls the word that stream writes, takes its tile of the REDUCED gradients back around
 // the caches and takes the Adam step.  Same arithmetic per element as the other two instantiations:
 // a 1-rank group reproduces the single-rank run bit for bit.
-template <bool DP, int NT, bool XR = false>
+// SNAP (single rank only): the held-out evaluations run in kernels BEHIND the launch (fit_deferred_eval.hip).  At
+// an evaluation point a tile workgroup only copies its weight tile (and its biases) from LDS to the snapshot
+// buffer -- where the in-launch variant runs the tile part, in the wait for the owners -- and the evaluation
+// code, its slab buffers, flags and granules are not in the loops at all.  Nothing in the launch reads a
+// snapshot: no flag, no drain; the end of the kernel makes it visible.
+template <int NT>
+__device__ __forceinline__ void u_tile_snapshot(const UArgs& p, const float* Wl, const float* biasl, int slot, int ks,
+                                                unsigned gidx) {
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));    // (nothing below may be computed ahead of the update loop and kept live in it)
+  const int wq = 16 * NT * p.WP / 4;           // 16-byte quads of the tile (WP is a multiple of 4)
+  float* dst = p.snap + ((int64_t)gidx * p.G + slot) * u_snap_slot_floats(NT, p.WP);
+  for (int i = tid; i < wq; i += kUT)
+    *reinterpret_cast<f32x4*>(dst + 4 * i) = *reinterpret_cast<const f32x4*>(Wl + 4 * i);
+  if (ks == 0 && tid < 4 * NT)
+    *reinterpret_cast<f32x4*>(dst + 4 * wq + 4 * tid) = *reinterpret_cast<const f32x4*>(biasl + 4 * tid);
+}
+// evaluation number of the launch (the snapshot slot; UEval::gidx) of evaluation e of chunk c
+__device__ __forceinline__ unsigned u_eval_gidx(const UArgs& p, int c, int e) {
+  return p.chunks ? (unsigned)u_uniform(p.chunks[c].eval_base) + (unsigned)e : (unsigned)e;
+}
+
+template <bool DP, int NT, bool XR = false, bool SNAP = false>
 __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, const URole& role) {
   static_assert(!(DP && XR), "XR is the resident kernel with the exchange inside, not the per-update launch");
+  static_assert(!(SNAP && (DP || XR)), "deferred evaluations: single-rank launches");
   constexpr int NBW = 16 * NT;                 // head rows of the tile
   constexpr int MAXBLK = NT == 1 ? 3 : 2;      // 16-column blocks per wavefront in the dW / Adam phase
   float* Ft = smem;                            // [KS][FP]   minibatch features of this k-slice, transposed
@@ -1071,9 +814,14 @@ __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, c
   u_own_init(p, o, own, true, XS, red, Ft, lane0);
   u_own_chunk(o, ck);
   // evaluation owner: the workgroups without a minibatch row come first
-  const int eo = (own - p.n_owner + p.T) % p.T;
-  const bool has_erow = p.do_eval && eo < p.NE;
-  int pending_eval = -1, pending_chunk = 0;    // evaluation whose tile part is out and whose row part is due
+  [[maybe_unused]] const int eo = (own - p.n_owner + p.T) % p.T;
+  [[maybe_unused]] const bool has_erow = p.do_eval && eo < p.NE;
+  [[maybe_unused]] int pending_eval = -1, pending_chunk = 0;    // evaluation whose tile part is out and whose row part is due
+  if constexpr (SNAP) {
+    // what a one-chunk call started with, for the evaluation kernels behind the launch (u_eval_of: state_in);
+    // workgroup 0 is also the one that advances the block at the end
+    if (wg == 0 && tid < ST_WORDS) const_cast<int32_t*>(p.state_in)[tid] = p.state[tid];
+  }
 
   // feature tile of the first update (later ones are fetched during the waits)
   f32x4 Freg[kUSteps];
@@ -1188,16 +936,25 @@ __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, c
     if (has_row) u_own_update(p, o, t, w, lane0, wg);
     // ---- held-out evaluations in the wait: the row part of the evaluation whose products went out
     //      during the previous update, the tile part of the one due after the previous update
-    if (__builtin_expect(pending_eval >= 0, 0)) {
-      __syncthreads();
-      if (has_erow) u_owner_eval(p, XS, red, eo, u_eval_of(p, pending_chunk, pending_eval), o.a);
-      pending_eval = -1;
+    if constexpr (!SNAP) {
+      if (__builtin_expect(pending_eval >= 0, 0)) {
+        __syncthreads();
+        if (has_erow) u_owner_eval(p, XS, red, eo, u_eval_of(p, pending_chunk, pending_eval), o.a);
+        pending_eval = -1;
+      }
     }
     // (update 0 of a later chunk of the launch: the evaluation after the last update of the chunk before)
     if (__builtin_expect(p.do_eval && (step > 0 ? eval_follows_update(step, p.eval_every) : c > 0), 0)) {
-      pending_chunk = step > 0 ? c : c - 1;
-      pending_eval = step > 0 ? evals_before(step, p.eval_every) - 1 : last_eval_index(p.n_updates, p.eval_every);
-      u_tile_eval<NT>(p, Wl, biasl, slot, ks, n0, k0, u_eval_of(p, pending_chunk, pending_eval));
+      const int ec = step > 0 ? c : c - 1;
+      const int ee = step > 0 ? evals_before(step, p.eval_every) - 1 : last_eval_index(p.n_updates, p.eval_every);
+      if constexpr (SNAP) {
+        // (the weights after the Adam phase of the update before: this wait lies in front of this update's)
+        u_tile_snapshot<NT>(p, Wl, biasl, slot, ks, u_eval_gidx(p, ec, ee));
+      } else {
+        pending_chunk = ec;
+        pending_eval = ee;
+        u_tile_eval<NT>(p, Wl, biasl, slot, ks, n0, k0, u_eval_of(p, pending_chunk, pending_eval));
+      }
     }
 
     // ---- 3. dW = d_out^T F on this tile, Adam --------------------------------------------------
@@ -1469,6 +1226,14 @@ __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, c
   }
 
   // ---- evaluations still owed at the end of the launch ------------------------------------------
+  if constexpr (SNAP) {
+    // the evaluation after the last update of the launch: its snapshot (the barrier: every wavefront's Adam
+    // phase is behind it).  A launch that gave up leaves snapshots nobody reads (the evaluation kernels return
+    // at the time-out bit).
+    __syncthreads();
+    if (p.do_eval && ck.step0 + p.n_updates == p.n_total)
+      u_tile_snapshot<NT>(p, Wl, biasl, slot, ks, u_eval_gidx(p, n_chunks - 1, evals_before(p.n_total - 1, p.eval_every)));
+  } else
   if (p.do_eval && !run_aborted(flagp, red, tid)) {
     if (pending_eval >= 0) {
       if (has_erow) u_owner_eval(p, XS, red, eo, u_eval_of(p, pending_chunk, pending_eval), o.a);
@@ -1534,6 +1299,7 @@ __device__ __forceinline__ void unified_workgroup(const UArgs& p, float* smem, c
 }
 
 // ---- a workgroup without a tile: row owner (and evaluation owner) only -------------------------
+template <bool SNAP>
 __device__ __forceinline__ void owner_only_workgroup(const UArgs& p, float* smem, const URole& role, int NBW, bool dp) {
   float* XS = smem + p.KS * kUFP + NBW * p.WP;      // (the layout of the tile workgroups)
   float* red = XS + p.xs_floats;
@@ -1548,10 +1314,10 @@ __device__ __forceinline__ void owner_only_workgroup(const UArgs& p, float* smem
   u_own_init(p, o, role.owner, false, XS, red, smem, lane0);
   u_own_chunk(o, ck);
   const bool has_row = role.owner < p.n_owner;
-  const int eo = (role.owner - p.n_owner + p.T) % p.T;
-  const bool has_erow = p.do_eval && eo < p.NE;
+  [[maybe_unused]] const int eo = (role.owner - p.n_owner + p.T) % p.T;
+  [[maybe_unused]] const bool has_erow = p.do_eval && eo < p.NE;
   const int fk = u_fast_kind(p);                    // (one loop, the row picked per update: the evaluation code once)
-  int pending_eval = -1, pending_chunk = 0;
+  [[maybe_unused]] int pending_eval = -1, pending_chunk = 0;
   for (int c = 0; c < n_chunks; ++c) {
   if (c > 0) {      // chunk boundary: see unified_workgroup (a launch that gave up leaves every chunk at its first update)
     u_chunk_load(p, c, ck);
@@ -1578,18 +1344,21 @@ __device__ __forceinline__ void owner_only_workgroup(const UArgs& p, float* smem
         default: u_own_update(p, o, t, w, lane0, wg); break;
       }
     }
-    if (__builtin_expect(pending_eval >= 0, 0)) {
-      __syncthreads();
-      if (has_erow) u_owner_eval(p, XS, red, eo, u_eval_of(p, pending_chunk, pending_eval), o.a);
-      pending_eval = -1;
-    }
-    if (__builtin_expect(p.do_eval && (step > 0 ? eval_follows_update(step, p.eval_every) : c > 0), 0)) {
-      pending_chunk = step > 0 ? c : c - 1;
-      pending_eval = step > 0 ? evals_before(step, p.eval_every) - 1 : last_eval_index(p.n_updates, p.eval_every);
+    if constexpr (!SNAP) {
+      if (__builtin_expect(pending_eval >= 0, 0)) {
+        __syncthreads();
+        if (has_erow) u_owner_eval(p, XS, red, eo, u_eval_of(p, pending_chunk, pending_eval), o.a);
+        pending_eval = -1;
+      }
+      if (__builtin_expect(p.do_eval && (step > 0 ? eval_follows_update(step, p.eval_every) : c > 0), 0)) {
+        pending_chunk = step > 0 ? c : c - 1;
+        pending_eval = step > 0 ? evals_before(step, p.eval_every) - 1 : last_eval_index(p.n_updates, p.eval_every);
+      }
     }
     __syncthreads();
   }
   }
+  if constexpr (SNAP) return;      // (the evaluations: kernels behind the launch)
   if (p.do_eval && !run_aborted(flagp, red, tid)) {
     if (pending_eval >= 0 && has_erow)
       u_owner_eval(p, XS, red, eo, u_eval_of(p, pending_chunk, pending_eval), o.a);
@@ -1601,13 +1370,13 @@ __device__ __forceinline__ void owner_only_workgroup(const UArgs& p, float* smem
   }
 }
 
-template <bool DP, int NT, bool XR = false>
+template <bool DP, int NT, bool XR = false, bool SNAP = false>
 __global__ __launch_bounds__(kUT) void linear_head_updates_kernel(UArgs p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
 #ifndef BSIG_HOST_SAN_BUILD   // (see fit_persistent_mdnn.hip)
   const URole role = wg_role(blockIdx.x, p.T, p.G);
-  if (role.tile < 0) owner_only_workgroup(p, smem, role, 16 * NT, DP);
-  else unified_workgroup<DP, NT, XR>(p, smem, role);
+  if (role.tile < 0) owner_only_workgroup<SNAP>(p, smem, role, 16 * NT, DP);
+  else unified_workgroup<DP, NT, XR, SNAP>(p, smem, role);
 #endif
 }
 
@@ -1741,13 +1510,15 @@ int persist_geometry(const PersistShape& s, int32_t* out) {
 // the > 64 KB dynamic-LDS limit of every instantiation this file launches
 static int u_allow_dynamic_lds() {
   static bool done[64] = {};
-  const void* kernels[6] = {reinterpret_cast<const void*>(linear_head_updates_kernel<false, 1>),
+  const void* kernels[8] = {reinterpret_cast<const void*>(linear_head_updates_kernel<false, 1>),
+                            reinterpret_cast<const void*>(linear_head_updates_kernel<false, 1, false, true>),
+                            reinterpret_cast<const void*>(linear_head_updates_kernel<false, 2, false, true>),
                             reinterpret_cast<const void*>(linear_head_updates_kernel<false, 2>),
                             reinterpret_cast<const void*>(linear_head_updates_kernel<true, 1>),
                             reinterpret_cast<const void*>(linear_head_updates_kernel<false, 1, true>),
                             reinterpret_cast<const void*>(linear_head_updates_kernel<true, 2>),
                             reinterpret_cast<const void*>(linear_head_updates_kernel<false, 2, true>)};
-  return allow_dynamic_lds(done, kernels, 6, kULds);
+  return allow_dynamic_lds(done, kernels, 8, kULds);
 }
 
 template <int NT>
@@ -1801,13 +1572,15 @@ static int u_launch(const UGeom& g, const UArgs& p, bool dp, int n, bool do_eval
     hipLaunchKernelGGL((linear_head_updates_kernel<false, NT, true>), dim3(g.T), dim3(kUT), g.lds, st, p);
   else if (dp)
     hipLaunchKernelGGL((linear_head_updates_kernel<true, NT>), dim3(g.T), dim3(kUT), g.lds, st, p);
+  else if (p.snap)
+    hipLaunchKernelGGL((linear_head_updates_kernel<false, NT, false, true>), dim3(g.T), dim3(kUT), g.lds, st, p);
   else
     hipLaunchKernelGGL((linear_head_updates_kernel<false, NT>), dim3(g.T), dim3(kUT), g.lds, st, p);
   BSIG_CHECK_LAUNCH("linear_head_updates");
   return BSIG_OK;
 }
 
-int persist_run(const PersistShape& s, const UGeom& g, const PersistBuffers& b, int n, hipStream_t st) {
+int persist_fill_args(const PersistShape& s, const UGeom& g, const PersistBuffers& b, int n, UArgs* out) {
   BSIG_REQUIRE(b.feats && b.y && b.ids && b.params && b.exp_avg && b.exp_avg_sq && b.state &&
                    b.train_loss && b.workspace, "persistent updates: null buffer");
   BSIG_REQUIRE(b.workspace_bytes >= u_data_bytes(g) + u_sync_bytes(), "persistent updates: workspace too small");
@@ -1820,7 +1593,8 @@ int persist_run(const PersistShape& s, const UGeom& g, const PersistBuffers& b, 
   BSIG_REQUIRE(!(b.xr_ready && !(b.w_off % 4 == 0 && s.feat_dim % 4 == 0 && aligned(b.grads, 16) &&
                                  (int64_t)g.Nh * s.feat_dim < ((int64_t)1 << 29))),
                "persistent updates: a resident data-parallel launch moves 16-byte gradient quads");
-  if (n <= 0 && !b.adam_pending && !b.do_eval) return BSIG_OK;
+  BSIG_REQUIRE(!(b.deferred && !(b.do_eval && !b.grads && !b.xr_ready && n >= 1 && b.n_total == n)),
+               "persistent updates: deferred evaluations belong to a single rank's whole call");
   // (a block: n_total updates in the launch; the widest tag is epoch * 4 + 3 in 32 bits)
   BSIG_REQUIRE(!(b.chunks && !(b.n_chunks >= 1 && !b.grads && !b.xr_ready && b.do_eval && b.feat_ids == b.ids &&
                                n >= 1 && b.n_total == n && (int64_t)b.n_chunks * n < (1 << 30))),
@@ -1876,6 +1650,19 @@ int persist_run(const PersistShape& s, const UGeom& g, const PersistBuffers& b, 
     p.prof_t0 = t0 ? atoi(t0) : 0;
   }
   if (b.xr_ready && !p.n_total) p.n_total = n;      // (the release of a launch that gave up: every wait passes)
+  p.state_in = p.state;
+  if (b.deferred) {      // (DeferredEval: the state block's copy in front, the snapshots 256 bytes in)
+    p.state_in = reinterpret_cast<const int32_t*>(b.deferred);
+    p.snap = reinterpret_cast<float*>(reinterpret_cast<char*>(b.deferred) + 256);
+  }
+  *out = p;
+  return BSIG_OK;
+}
+
+int persist_run(const PersistShape& s, const UGeom& g, const PersistBuffers& b, int n, hipStream_t st) {
+  if (n <= 0 && !b.adam_pending && !b.do_eval) return BSIG_OK;
+  UArgs p;
+  BSIG_TRY(persist_fill_args(s, g, b, n, &p));
   return g.NT == 1 ? u_launch<1>(g, p, b.grads != nullptr, n, b.do_eval != 0, st)
                    : u_launch<2>(g, p, b.grads != nullptr, n, b.do_eval != 0, st);
 }

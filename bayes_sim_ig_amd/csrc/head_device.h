@@ -793,6 +793,12 @@ __device__ inline void granule_publish(unsigned long long* g, int slot, uint32_t
   __hip_atomic_store(g + slot * kGranStride, ((unsigned long long)tag << 32) | (unsigned long long)__float_as_uint(v),
                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// The order of a cross-workgroup sum: lane l comes with the values of slots l, l + 64, l + 128, l + 192 (zero
+// beyond the last slot); every gather of granules sums them this way, and so does whoever forms the same sum
+// from values another kernel left in memory (fit_deferred_eval.hip).
+__device__ __forceinline__ float granule_slot_sum(const float (&v)[4]) {
+  return (wave_sum_dpp(v[0]) + wave_sum_dpp(v[1])) + (wave_sum_dpp(v[2]) + wave_sum_dpp(v[3]));
+}
 // (All the polls of a round are issued before the first is looked at: with a test between them the
 // compiler waits for each load in turn, and a 188-flag fan-in cost three memory round trips -- 1.6 us
 // on flags that were already up -- instead of one.)
@@ -826,7 +832,7 @@ __device__ inline float granule_gather(unsigned long long* g, int G, uint32_t ta
     }
     __builtin_amdgcn_s_sleep(1);
   }
-  return (wave_sum_dpp(v[0]) + wave_sum_dpp(v[1])) + (wave_sum_dpp(v[2]) + wave_sum_dpp(v[3]));
+  return granule_slot_sum(v);
 }
 
 __device__ inline void flag_raise(unsigned* flags, int slot, unsigned epoch) {
@@ -914,7 +920,7 @@ struct GranuleEps {
       all = all && (!mine || up);
     }
     float sum;
-    if (__all(all)) sum = (wave_sum_dpp(v[0]) + wave_sum_dpp(v[1])) + (wave_sum_dpp(v[2]) + wave_sum_dpp(v[3]));
+    if (__all(all)) sum = granule_slot_sum(v);
     else sum = granule_gather(const_cast<unsigned long long*>(g), G, tag, lane, flag);
     return eps_noise * (sum / norm);
   }

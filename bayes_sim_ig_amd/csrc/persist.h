@@ -82,7 +82,28 @@ struct PersistBuffers : PersistCommon {
   // (= feat_ids), train_loss and test_loss are the block's, n_test the most of any chunk, n_total the updates of
   // the whole launch; every chunk evaluates inside the launch.  null: one chunk, described by the fields above.
   const bsig_fit_chunk* chunks = nullptr; int n_chunks = 1;
+  // Deferred evaluations (single rank, do_eval): the plan's DeferredEval memory, reserved for at least the
+  // evaluations of this launch.  The update launch then only snapshots the weight tiles at the evaluation points
+  // and deferred_eval_run, enqueued behind it, evaluates from the snapshots.  null: evaluations inside the launch.
+  void* deferred = nullptr;
 };
+
+// ---- held-out evaluations behind the update launch (fit_deferred_eval.hip) ---------------------------------
+// Device memory of a plan's deferred evaluations: [copy of the state block | snapshots of the weight tiles at
+// the evaluation points of a launch | partial products, row sums and owner sums of a GROUP of evaluations].
+// Allocated at the first launch that needs it (and again when a launch holds more evaluations), freed with the plan.
+struct DeferredEval { void* mem = nullptr; size_t bytes = 0; int n_evals = 0; };
+// The most a plan's snapshots may take (BSIG_DEFERRED_EVAL_CAP_MB overrides: tests): a launch whose evaluations
+// need more keeps them inside the launch.
+constexpr size_t kDeferredSnapCapBytes = (size_t)2 << 30;
+// bytes the partial products of a group of evaluations may take (the evaluations of a launch run in groups)
+constexpr size_t kDeferredGroupBytes = (size_t)96 << 20;
+size_t deferred_eval_snapshot_bytes(const UGeom& g, int n_evals);
+// true: *d holds a launch of n_evals evaluations (false: over the cap, or no memory -- evaluate inside the launch)
+bool deferred_eval_reserve(const UGeom& g, int n_evals, DeferredEval* d);
+void deferred_eval_free(DeferredEval* d);
+// the evaluations of the launch persist_run(s, g, b, n, st) made with b.deferred set, on the same stream
+int deferred_eval_run(const PersistShape& s, const UGeom& g, const PersistBuffers& b, int n, hipStream_t st);
 
 // The tiling of a shape and whether the device can hold every workgroup of its launch at once (asks
 // the device and raises the kernels' dynamic-LDS limit: once per plan).  false: not covered, *g and

@@ -61,17 +61,30 @@ class PersistentTimeout(RuntimeError):
     state they saved at the start and repeat the work on the per-phase kernels."""
 
 
+class _BlockLogs:
+    """The packed logs of every chunk of a block launch: read back ONCE, by the first chunk that asks."""
+
+    def __init__(self, packed):
+        self.packed, self._host = packed, None
+
+    def row(self, c):
+        if self._host is None:
+            self._host = self.packed.cpu().tolist()
+        return self._host[c]
+
+
 class PendingLogs:
     """The 6+6 losses and the non-finite flag of one run_training call, still on
     the device; ``result()`` is the call's single host read-back.  BayesSim.fit
     defers it to the end of the chunk loop so the GPU never waits for the host."""
 
-    def __init__(self, packed, n_e, n_test, verbose, dp=None):
+    def __init__(self, packed, n_e, n_test, verbose, dp=None, block=None):
         self.packed, self.n_e, self.n_test, self.verbose = packed, n_e, n_test, verbose
         self.dp = dp      # (eval_its, n_updates, world): `packed` is bsig_fit_run_dp's reduced_logs
+        self.block = block   # (_BlockLogs, chunk): a chunk of a block launch, whose chunks share one read-back
 
     def result(self):
-        host = self.packed.cpu().tolist()
+        host = self.block[0].row(self.block[1]) if self.block is not None else self.packed.cpu().tolist()
         n_e = self.n_e
         if self.dp is not None:
             eval_its, n_updates, world = self.dp
@@ -773,7 +786,8 @@ class MDNN(nn.Module):
             _lib.ptr(stage), n_chunks, _lib.ptr(train_loss), _lib.ptr(test_loss), _lib.ptr(packed),
             batch_size, st))
         self._block_launches += 1
-        return [PendingLogs(packed[c], n_e, split[c][1], type(self).VERBOSE) for c in range(n_chunks)]
+        shared = _BlockLogs(packed)
+        return [PendingLogs(packed[c], n_e, split[c][1], type(self).VERBOSE, block=(shared, c)) for c in range(n_chunks)]
 
     @_on_model_device
     def _run_training_once(self, x_data, y_data, n_updates, batch_size, test_frac=0.2,

@@ -364,8 +364,9 @@ int bsig_fit_pack_logs(bsig_fit_plan* plan, int64_t n_updates, float* out,
  * chunk) would otherwise do as bind / set_features / begin / run / pack_logs per chunk.  Between two
  * chunks the reference keeps the weights, creates a fresh Adam (mdnn.py:203), takes the next chunk's rows
  * (mdnn.py:206-211) and draws new minibatch ids (mdnn.py:219-222): the kernel keeps its weight tiles on
- * the chip across the boundary, restarts the moments in registers and runs the evaluation after a chunk's
- * last update (mdnn.py:235-242) in the waits of the next chunk's first updates.  Every number is the one
+ * the chip across the boundary, restarts the moments in registers and snapshots the weights for the evaluation
+ * after a chunk's last update (mdnn.py:235-242) in the wait of the next chunk's first update (the evaluations
+ * themselves run in kernels behind the launch, bsig_debug_fit_deferred).  Every number is the one
  * the per-chunk calls produce, bit for bit.
  * One table entry per chunk.  The chunk's rows are rows row0 .. row0 + n_train + n_test of the block's
  * feature and target matrices, the n_test held-out rows last; its [n_updates, batch] minibatch ids (rows of
@@ -401,6 +402,14 @@ int bsig_fit_run_block(bsig_fit_plan* plan, const float* feats, int64_t ld_feats
                        const bsig_fit_chunk* chunks_host, const bsig_fit_chunk* chunks_dev, int n_chunks,
                        float* train_loss, float* test_loss, float* packed_logs, int64_t norm_batch,
                        bsig_stream_t stream);
+/* Where a single rank's held-out evaluations ran (linear heads in the persistent kernel): out[0] = launches of
+ * this plan whose evaluations ran in kernels BEHIND the update launch, from snapshots of the weight tiles the
+ * launch left at its evaluation points (the default; same numbers bit for bit), out[1] = launches that evaluated
+ * INSIDE the update launch (BSIG_EVAL_IN_LAUNCH=1, read when the plan is created; or a launch whose snapshots
+ * would exceed the cap of 2 GiB -- BSIG_DEFERRED_EVAL_CAP_MB overrides it --, or found no memory), out[2] = bytes
+ * of device memory the plan holds for snapshots and evaluation scratch (allocated at the first such launch,
+ * freed with the plan). */
+int bsig_debug_fit_deferred(const bsig_fit_plan* plan, int64_t* out);
 /* (tests) the "several chunks per launch" answer for an engine description: kind as
  * bsig_fit_is_persistent reports it, whether a single rank evaluates inside the launch, whether the
  * per-plan switch forces one chunk per launch. */
