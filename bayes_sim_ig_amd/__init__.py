@@ -13,4 +13,5 @@ from .mdrff import MDRFF                      # noqa: F401
 from .rff import RFF                          # noqa: F401
 from .summarizers import (pad_states_actions, summary_start, summary_waypts,  # noqa: F401
                           summary_corr, summary_corrdiff, summary_signatory,
-                          signature_depth, cross_correlation)
+                          signature_depth, cross_correlation, summary_logsignature,
+                          logsignature_dim, lyndon_words)

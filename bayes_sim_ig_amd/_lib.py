@@ -1,5 +1,5 @@
 """ctypes binding of libbsig_hip.so (include/bsig.h, include/bsig_f64.h, include/bsig_matmul.h,
-include/bsig_signature.h).
+include/bsig_signature.h, include/bsig_logsignature.h).
 
 Whether a call computes in fp32 or fp64 is decided in ONE place, the two ``Precision`` objects ``F32`` and
 ``F64`` below: they carry the dtype, the sizes and the entry points that exist in both modes under one
@@ -243,6 +243,13 @@ _PROTOS_SIGNATURE = {
     'bsig_signature_ex': (C.c_int, [vp, vp, vp, C.c_int, vp, i64] + [C.c_int] * 4 + [i64, vp]),
     'bsig_signature_ex_f64': (C.c_int, [vp, vp, vp, C.c_int, vp, i64] + [C.c_int] * 4 + [i64, vp]),
 }
+# include/bsig_logsignature.h: the log-signature at the Lyndon words, on the general signature kernel
+_PROTOS_LOGSIGNATURE = {
+    'bsig_logsignature_dim': (i64, [C.c_int, C.c_int]),
+    'bsig_logsignature_words': (C.c_int, [C.c_int, C.c_int, C.POINTER(i32), i64]),
+    'bsig_logsignature': (C.c_int, [vp, vp, vp, C.c_int, vp, vp, i64] + [C.c_int] * 4 + [i64, vp]),
+    'bsig_logsignature_f64': (C.c_int, [vp, vp, vp, C.c_int, vp, vp, i64] + [C.c_int] * 4 + [i64, vp]),
+}
 COMM_ID_BYTES = 128
 EXCHANGE_SUM, EXCHANGE_BROADCAST = 0, 1
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int, vp, i64, C.c_int, vp)
@@ -270,6 +277,11 @@ def exported_symbols_signature():
     return sorted(_PROTOS_SIGNATURE)
 
 
+def exported_symbols_logsignature():
+    """Names every declaration of include/bsig_logsignature.h must resolve to."""
+    return sorted(_PROTOS_LOGSIGNATURE)
+
+
 def matmul_precision(name):
     """'float32' | 'split_bf16' -> BSIG_MATMUL_* (include/bsig_matmul.h); ValueError on anything else."""
     if name not in MATMUL_PRECISIONS:
@@ -294,7 +306,7 @@ def load():
                 '__graft_entry__.build(); there is no CPU fallback' % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(_PROTOS.items()) + list(_PROTOS_F64.items()) + list(_PROTOS_MATMUL.items()) +
-                                  list(_PROTOS_SIGNATURE.items())):
+                                  list(_PROTOS_SIGNATURE.items()) + list(_PROTOS_LOGSIGNATURE.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _check_abi(lib)
@@ -381,6 +393,8 @@ class Precision:
     # include/bsig_signature.h (the general signature kernel): resolved like OPS, from _PROTOS_SIGNATURE
     SIGNATURE_OPS = {
         'signature_ex': ('bsig_signature_ex', 'bsig_signature_ex_f64'),
+        # include/bsig_logsignature.h, from _PROTOS_LOGSIGNATURE
+        'logsignature': ('bsig_logsignature', 'bsig_logsignature_f64'),
     }
     HYPER_OPS = ('head_forward', 'head_outputs', 'nll_from_tuple', 'loss_grad')    # take the hyper in fp64
     # the plan lifecycle
@@ -412,7 +426,8 @@ class Precision:
         # fp32 replays an update from a HIP graph, so a call's rows are staged at fixed addresses; fp64
         # has no graphs: it binds the rows where they lie and is never asked for one (FIT_GRAPH)
         self.replays_graphs = self.itemsize == 4
-        self._protos = dict(_PROTOS_F64 if self.itemsize == 8 else _PROTOS, **_PROTOS_SIGNATURE)
+        self._protos = dict(_PROTOS_F64 if self.itemsize == 8 else _PROTOS, **_PROTOS_SIGNATURE,
+                            **_PROTOS_LOGSIGNATURE)
         for op in (list(self.OPS) + list(self.SIGNATURE_OPS) + list(self.FIT_OPS) +
                    list(self.QUERIES)):                                          # (a typo fails the import)
             assert self.symbol(op) is None or self.symbol(op) in self._protos, op

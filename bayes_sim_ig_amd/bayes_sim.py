@@ -20,13 +20,14 @@ from .mdnn import MDNN
 from .mdrff import MDRFF
 from .summarizers import (pad_states_actions, summary_start, summary_waypts,  # noqa: F401
                           summary_corr, summary_corrdiff, summary_signatory,
-                          signature_depth, cross_correlation)
+                          signature_depth, cross_correlation, summary_logsignature)
 
 _SUMMARIZERS = {
     'summary_start': summary_start, 'summary_waypts': summary_waypts,
     'summary_corr': summary_corr, 'summary_corrdiff': summary_corrdiff,
-    'summary_signatory': summary_signatory,
+    'summary_signatory': summary_signatory, 'summary_logsignature': summary_logsignature,
 }
+_SIGNATURES = ('summary_signatory', 'summary_logsignature')      # take sigDepth and sigChannels
 _MODELS = {'MDNN': MDNN, 'MDRFF': MDRFF}
 
 
@@ -49,14 +50,19 @@ class BayesSim(object):
         """Arguments as in the reference (bayes_sim.py:27-52).  Optional
         ``model_cfg`` keys beyond the reference's: ``nFeat`` (RFF features,
         default 200 as hard-coded at bayes_sim.py:81), ``sigDepth`` (1..6: the
-        truncation depth of ``summary_signatory``; default: the reference's rule,
-        at most 3) and ``sigChannels`` (``summary_signatory`` only: the channels
+        truncation depth of ``summary_signatory`` and ``summary_logsignature``;
+        default: the reference's rule, at most 3) and ``sigChannels`` (those two
+        summarizers only: the channels
         of ``[states | actions]`` that make up the path after the time channel,
         in any order -- index ``c < obs_dim`` is a state channel, any other action
         channel ``c - obs_dim``; they are gathered by the kernel, the trajectories
         are not sliced; ``input_dim`` follows from both keys, and a shape whose
         levels do not fit a workgroup's LDS at ``trainTrajLen`` is a
-        NotImplementedError here, include/bsig_signature.h), ``dtype``
+        NotImplementedError here, include/bsig_signature.h;
+        ``'summarizerFxn': 'summary_logsignature'`` -- not in the reference -- is the
+        log-signature of the same path at the Lyndon words, ``logsignature_dim``
+        inputs instead of ``signature_dim``, under the same LDS condition,
+        include/bsig_logsignature.h), ``dtype``
         ('float32', the default, or 'float64': the estimator's fp64 mode, as
         ``bs.model.double()``), ``summaryDtype`` ('float32', the default in both
         modes: the summaries are made in fp32 and a double model gets them
@@ -77,18 +83,25 @@ class BayesSim(object):
             raise ValueError("model_cfg['sigDepth'] must be in 1..%d, got %r"
                              % (_lib.SIGNATURE_MAX_DEPTH, self._sig_depth))
         if self._sig_channels is not None:
-            if name != 'summary_signatory':
+            if name not in _SIGNATURES:
                 raise ValueError("model_cfg['sigChannels'] applies to 'summary_signatory', not to %r" % name)
             self._sig_channels = _summ.signature_channels(self._sig_channels, obs_dim, act_dim)
         # the reference pushes a zero trajectory through the summarizer to get
         # the width (bayes_sim.py:57-60); the width is a closed form
+        itemsize = 8 if model_cfg.get('summaryDtype', 'float32') == 'float64' else 4
         if name == 'summary_signatory' and (self._sig_channels is not None or (self._sig_depth or 0) > 3):
             # include/bsig_signature.h: the general kernel; whether it covers the shape is host arithmetic
             path_dim = 1 + (obs_dim + act_dim if self._sig_channels is None else len(self._sig_channels))
             depth = self._sig_depth or _summ.signature_depth(path_dim)
             traj_summaries_dim = _summ.signature_dim(path_dim, depth)
-            itemsize = 8 if model_cfg.get('summaryDtype', 'float32') == 'float64' else 4
             _lib.check(_lib.load().bsig_signature_ex_fits(path_dim, model_cfg['trainTrajLen'], depth, itemsize))
+        elif name == 'summary_logsignature':
+            # include/bsig_logsignature.h: the same kernel's LDS at every depth but 1 (level 1 needs none)
+            path_dim = 1 + (obs_dim + act_dim if self._sig_channels is None else len(self._sig_channels))
+            depth = self._sig_depth or _summ.signature_depth(path_dim)
+            traj_summaries_dim = _summ.logsignature_dim(path_dim, depth)
+            if depth > 1:
+                _lib.check(_lib.load().bsig_signature_ex_fits(path_dim, model_cfg['trainTrajLen'], depth, itemsize))
         else:
             traj_summaries_dim = _summ.summary_dim(
                 name, model_cfg['trainTrajLen'], obs_dim, act_dim,
@@ -145,7 +158,7 @@ class BayesSim(object):
     def _summarize(self, states, actions, finite_flag=None, lazy=False):
         # ('summaryDtype': 'float64' -- the summarizers' fp64 kernels; else no keyword: the fp32 path)
         kw = {} if self._summary_dtype is None else {'dtype': self._summary_dtype}
-        if self.summarizer_name == 'summary_signatory' and (self._sig_depth or self._sig_channels is not None):
+        if self.summarizer_name in _SIGNATURES and (self._sig_depth or self._sig_channels is not None):
             return self.summarizer_fxn(states, actions, depth=self._sig_depth or None,
                                        channels=self._sig_channels, **kw)
         if self.summarizer_name in ('summary_corr', 'summary_corrdiff'):

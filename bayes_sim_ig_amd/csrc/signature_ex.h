@@ -101,32 +101,29 @@ inline int plan(const char* what, int64_t d, int length, int depth, int itemsize
   return BSIG_OK;
 }
 
+// What a workgroup does with a trajectory's levels once its path has ended: the signature's own tail
+// stores them, levels 1..depth concatenated.  (csrc/logsignature.h has the other tail.)
 template <typename T>
-__global__ __launch_bounds__(kMaxThreads) void signature_ex_kernel(
-    const T* __restrict__ states, const T* __restrict__ actions, const int32_t* __restrict__ channels,
-    T* __restrict__ out, int64_t n, int length, int sd, int ad, int64_t ld_out, Layout g) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char sigex_smem[];
+struct StoreLevels {
+  __device__ __forceinline__ void operator()(T* __restrict__ o, const T* cur, const T* topv, const T*,
+                                             const Layout& g, int tid, int nt) const {
+    const int low = g.low, width = g.low + g.top;
+    for (int e = tid; e < width; e += nt) o[e] = e < low ? cur[e] : topv[e - low];
+  }
+};
+
+// The path loop at depth >= 2, shared by every kernel that needs the levels of a trajectory: the LDS
+// of the Layout, the set-up once per workgroup, the trajectories grid-strided, one barrier per segment.
+// When a path has ended, `tail(o, cur, topv, rcp, g, tid, nt)` finds levels 1..depth-1 in `cur`, level
+// depth in `topv`, the reciprocals in `rcp`, all of them stable until the whole workgroup has left it
+// (the barrier that opens the next trajectory), and writes the trajectory's output row `o`.
+template <typename T, typename Tail>
+__device__ __forceinline__ void path_levels(
+    unsigned char* sigex_smem, const T* __restrict__ states, const T* __restrict__ actions,
+    const int32_t* __restrict__ channels, T* __restrict__ out, int64_t n, int length, int sd, int ad,
+    int64_t ld_out, const Layout& g, Tail tail) {
   const int tid = threadIdx.x, nt = blockDim.x;
   const int d = g.d, depth = g.depth;
-  if (depth == 1) {                      // last - first point (time channel: L-1); no LDS
-    for (int64_t traj = blockIdx.x; traj < n; traj += gridDim.x) {
-      const T* s = states + traj * (int64_t)length * sd;
-      const T* a = actions + traj * (int64_t)length * ad;
-      T* o = out + traj * ld_out;
-      for (int c = tid; c < d; c += nt) {
-        T v;
-        if (c == 0) {
-          v = (T)(length - 1);
-        } else {
-          const int ch = channels ? channels[c - 1] : c - 1;
-          v = ch < sd ? s[(int64_t)(length - 1) * sd + ch] - s[ch]
-                      : a[(int64_t)(length - 1) * ad + ch - sd] - a[ch - sd];
-        }
-        o[c] = v;
-      }
-    }
-    return;
-  }
   T* buf_a = reinterpret_cast<T*>(sigex_smem);                  // levels 1..depth-1
   T* buf_b = reinterpret_cast<T*>(sigex_smem + g.off_b);        // levels 1..depth-1, the other copy
   T* topv = reinterpret_cast<T*>(sigex_smem + g.off_top);       // level depth
@@ -200,25 +197,58 @@ __global__ __launch_bounds__(kMaxThreads) void signature_ex_kernel(
       __syncthreads();
       T* sw = cur; cur = nxt; nxt = sw;
     }
-    const int width = low + top;
-    for (int e = tid; e < width; e += nt) o[e] = e < low ? cur[e] : topv[e - low];
+    tail(o, cur, topv, rcp, g, tid, nt);
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kMaxThreads) void signature_ex_kernel(
+    const T* __restrict__ states, const T* __restrict__ actions, const int32_t* __restrict__ channels,
+    T* __restrict__ out, int64_t n, int length, int sd, int ad, int64_t ld_out, Layout g) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char sigex_smem[];
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int d = g.d, depth = g.depth;
+  if (depth == 1) {                      // last - first point (time channel: L-1); no LDS
+    for (int64_t traj = blockIdx.x; traj < n; traj += gridDim.x) {
+      const T* s = states + traj * (int64_t)length * sd;
+      const T* a = actions + traj * (int64_t)length * ad;
+      T* o = out + traj * ld_out;
+      for (int c = tid; c < d; c += nt) {
+        T v;
+        if (c == 0) {
+          v = (T)(length - 1);
+        } else {
+          const int ch = channels ? channels[c - 1] : c - 1;
+          v = ch < sd ? s[(int64_t)(length - 1) * sd + ch] - s[ch]
+                      : a[(int64_t)(length - 1) * ad + ch - sd] - a[ch - sd];
+        }
+        o[c] = v;
+      }
+    }
+    return;
+  }
+  path_levels<T>(sigex_smem, states, actions, channels, out, n, length, sd, ad, ld_out, g,
+                 StoreLevels<T>());
 }
 
 // A launch with more than 64 KB of dynamic LDS needs the function's limit raised first (once per
 // device of this process and function).
-template <typename T>
-int allow_lds(size_t lds) {
-  static bool attr_set[64] = {};
+// (`kernel` and its `attr_set[64]`, one flag per device, belong together.)
+inline int allow_lds_of(const void* kernel, bool* attr_set, size_t lds) {
   if (lds <= 64 * 1024) return BSIG_OK;
   int dev = 0;
   BSIG_HIP(hipGetDevice(&dev));
   if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-    BSIG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(signature_ex_kernel<T>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+    BSIG_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
     if (dev >= 0 && dev < 64) attr_set[dev] = true;
   }
   return BSIG_OK;
+}
+
+template <typename T>
+int allow_lds(size_t lds) {
+  static bool attr_set[64] = {};
+  return allow_lds_of(reinterpret_cast<const void*>(signature_ex_kernel<T>), attr_set, lds);
 }
 
 // The entry point of either precision: the argument checks, the routing of include/bsig_signature.h,

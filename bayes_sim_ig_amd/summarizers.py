@@ -345,3 +345,90 @@ def summary_signatory(states, actions, depth=None, out=None, dtype=None, channel
         _lib.ptr(s), _lib.ptr(a), _lib.ptr(vec), len(picked or ()), _lib.ptr(buf), n, length, sd, ad,
         depth, ld, _lib.stream())
     return _finish(buf, n, width, home, out)
+
+
+def logsignature_dim(path_dim, depth):
+    """Width of a log-signature row: the number of Lyndon words of length 1..depth over ``path_dim`` letters
+    (Witt's formula), without touching the GPU (bsig_logsignature_dim, include/bsig_logsignature.h).
+    ValueError where ``signature_dim`` raises it."""
+    width = int(_lib.load().bsig_logsignature_dim(int(path_dim), int(depth)))
+    if width < 0:
+        raise ValueError('no log-signature row for path_dim=%r, depth=%r (path_dim >= 2, depth in 1..%d, '
+                         'signature width below 2^31)' % (path_dim, depth, _lib.SIGNATURE_MAX_DEPTH))
+    return width
+
+
+_word_offsets = {}         # (path_dim, depth) -> the library's offset table, a tuple of ints
+_word_vectors = {}         # (path_dim, depth, device) -> the table as an int32 vector on that device
+
+
+def _lyndon_offsets(path_dim, depth):
+    """bsig_logsignature_words: per output element, the flat offset of its word in the signature row."""
+    key = (int(path_dim), int(depth))
+    table = _word_offsets.get(key)
+    if table is None:
+        width = logsignature_dim(*key)
+        buf = (C.c_int32 * width)()
+        _lib.check(_lib.load().bsig_logsignature_words(key[0], key[1], buf, width))
+        table = _word_offsets[key] = tuple(buf)
+    return table
+
+
+def lyndon_words(path_dim, depth):
+    """The Lyndon words of length 1..depth over the letters ``0 < 1 < ... < path_dim - 1`` (0: the time
+    channel) as tuples of letters, in the order of a ``summary_logsignature`` row: by length, then
+    lexicographically.  Read off the offsets the library hands the kernel, not made a second time."""
+    words, base, k = [], 0, 1
+    for at in _lyndon_offsets(path_dim, depth):
+        while at >= base + path_dim ** k:
+            base += path_dim ** k
+            k += 1
+        rem, letters = at - base, []
+        for _ in range(k):
+            rem, letter = divmod(rem, path_dim)
+            letters.append(letter)
+        words.append(tuple(reversed(letters)))
+    return words
+
+
+def _word_vector(path_dim, depth, device):
+    """The offset table of (path_dim, depth) on ``device``: uploaded once."""
+    key = (int(path_dim), int(depth), str(device))
+    vec = _word_vectors.get(key)
+    if vec is None:
+        vec = _word_vectors[key] = torch.tensor(_lyndon_offsets(path_dim, depth), dtype=torch.int32).to(device)
+    return vec
+
+
+def summary_logsignature(states, actions, depth=None, out=None, dtype=None, channels=None):
+    """The log-signature of the path ``[t | picked channels]`` at the Lyndon words -- ``signatory``'s
+    ``logsignature(path, depth, mode="words")`` -- by an epilogue on the general signature kernel
+    (include/bsig_logsignature.h, csrc/logsignature.h): ``logsignature_dim(d, depth)`` coordinates that
+    determine the ``signature_dim(d, depth)`` terms of ``summary_signatory``, in the order of
+    ``lyndon_words(d, depth)``.  The signature itself is never written to memory.
+
+    Arguments, checks, default depth (``signature_depth(d)``), ``out=``, ``dtype=torch.float64`` and errors
+    are those of ``summary_signatory``.  Depth 1 is the signature's level 1; every other call, whatever
+    ``channels``, runs the log-signature kernel.  In fp32 the log cancels: see the README for the error
+    relative to the value at depth 6; ``dtype=torch.float64`` is the remedy."""
+    prec = _precision(dtype)
+    assert len(states.shape) == 3, 'states should be batch x time x state_dim'
+    assert len(actions.shape) == 3, 'Need actions: ntraj x n_steps x state_dim'
+    picked = None if channels is None else signature_channels(channels, states.shape[2], actions.shape[2])
+    if depth is not None and depth > _lib.SIGNATURE_MAX_DEPTH:
+        raise ValueError('depth %r is above %d' % (depth, _lib.SIGNATURE_MAX_DEPTH))
+    s, a, home = _prep(states, actions, prec)
+    n, length, sd = s.shape
+    ad = a.shape[2]
+    assert a.shape[1] == length
+    path_dim = 1 + (sd + ad if picked is None else len(picked))
+    if depth is None:
+        depth = signature_depth(path_dim)
+    width = logsignature_dim(path_dim, depth)
+    buf, ld = _alloc(n, width, s.device, out, prec)
+    vec = None if picked is None else _channel_vector(picked, s.device)
+    words = None if depth == 1 else _word_vector(path_dim, depth, s.device)
+    prec.logsignature(
+        _lib.ptr(s), _lib.ptr(a), _lib.ptr(vec), len(picked or ()), _lib.ptr(words), _lib.ptr(buf), n, length,
+        sd, ad, depth, ld, _lib.stream())
+    return _finish(buf, n, width, home, out)

@@ -2,7 +2,8 @@
 # Build libbsig_hip.so (gfx950) in-tree.  hipcc cross-compiles without a GPU.
 # An object is rebuilt when the CONTENT of its source, of any csrc header, of include/bsig.h, include/bsig_matmul.h or the
 # flags changed (a stamp next to the object; file times do not survive every transport).  The objects of the fp64 mode
-# and of the general signature kernel also cover include/bsig_f64.h and include/bsig_signature.h.
+# and of the general signature kernel also cover include/bsig_f64.h and include/bsig_signature.h, those of the
+# log-signature kernel include/bsig_logsignature.h as well.
 set -euo pipefail
 cd "$(dirname "$0")"
 SRC=bayes_sim_ig_amd/csrc
@@ -25,6 +26,8 @@ COMMON=$(cat "$SRC"/*.h include/bsig.h include/bsig_matmul.h | sha256sum | cut -
 COMMON64=$(cat "$SRC"/f64/*.h include/bsig_f64.h | sha256sum | cut -d' ' -f1)
 # the general signature kernel (csrc/signature_ex.h, include/bsig_signature.h), in both precisions
 SIGEX=$(sha256sum < include/bsig_signature.h | cut -d' ' -f1)
+# the log-signature kernel (csrc/logsignature.h, include/bsig_logsignature.h) sees both headers
+LOGSIG=$(cat include/bsig_signature.h include/bsig_logsignature.h | sha256sum | cut -d' ' -f1)
 pids=()
 build_one() {  # name, source, extra flags[, hash of further headers the source sees]
   local stamp="$OUT/obj/$1.stamp"
@@ -41,6 +44,8 @@ for f in summarizers gemm_f32 gemm_tile_64 gemm_tile_128 gemm_tile_128x32 gemm_t
 done
 build_one signature_ex "$SRC/signature_ex.hip" "" "$SIGEX"
 build_one signature_ex_f64 "$SRC/f64/signature_ex_f64.hip" "" "$COMMON64 $SIGEX"
+build_one logsignature "$SRC/logsignature.hip" "" "$LOGSIG"
+build_one logsignature_f64 "$SRC/f64/logsignature_f64.hip" "" "$COMMON64 $LOGSIG"
 for f in api comm; do
   build_one "$f" "$SRC/$f.cpp" "-x hip"
 done
