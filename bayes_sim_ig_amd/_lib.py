@@ -1,5 +1,5 @@
 """ctypes binding of libbsig_hip.so (include/bsig.h, include/bsig_f64.h, include/bsig_matmul.h,
-include/bsig_signature.h, include/bsig_logsignature.h).
+include/bsig_signature.h, include/bsig_logsignature.h, include/bsig_input_norm.h).
 
 Whether a call computes in fp32 or fp64 is decided in ONE place, the two ``Precision`` objects ``F32`` and
 ``F64`` below: they carry the dtype, the sizes and the entry points that exist in both modes under one
@@ -250,6 +250,15 @@ _PROTOS_LOGSIGNATURE = {
     'bsig_logsignature': (C.c_int, [vp, vp, vp, C.c_int, vp, vp, i64] + [C.c_int] * 4 + [i64, vp]),
     'bsig_logsignature_f64': (C.c_int, [vp, vp, vp, C.c_int, vp, vp, i64] + [C.c_int] * 4 + [i64, vp]),
 }
+# include/bsig_input_norm.h: column statistics of the estimator's input rows and their standardisation
+INPUT_NORM_SLAB_ROWS = 64
+_PROTOS_INPUT_NORM = {
+    'bsig_input_norm_workspace_bytes': (i64, [i64, i64]),
+    'bsig_input_norm_stats': (C.c_int, [vp, i64, i64, i64, vp, vp, vp, sz, vp]),
+    'bsig_input_norm_stats_f64': (C.c_int, [vp, i64, i64, i64, vp, vp, vp, sz, vp]),
+    'bsig_input_norm_apply': (C.c_int, [vp, i64, vp, vp, vp, i64, i64, i64, vp]),
+    'bsig_input_norm_apply_f64': (C.c_int, [vp, i64, vp, vp, vp, i64, i64, i64, vp]),
+}
 COMM_ID_BYTES = 128
 EXCHANGE_SUM, EXCHANGE_BROADCAST = 0, 1
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int, vp, i64, C.c_int, vp)
@@ -282,6 +291,11 @@ def exported_symbols_logsignature():
     return sorted(_PROTOS_LOGSIGNATURE)
 
 
+def exported_symbols_input_norm():
+    """Names every declaration of include/bsig_input_norm.h must resolve to."""
+    return sorted(_PROTOS_INPUT_NORM)
+
+
 def matmul_precision(name):
     """'float32' | 'split_bf16' -> BSIG_MATMUL_* (include/bsig_matmul.h); ValueError on anything else."""
     if name not in MATMUL_PRECISIONS:
@@ -306,7 +320,8 @@ def load():
                 '__graft_entry__.build(); there is no CPU fallback' % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(_PROTOS.items()) + list(_PROTOS_F64.items()) + list(_PROTOS_MATMUL.items()) +
-                                  list(_PROTOS_SIGNATURE.items()) + list(_PROTOS_LOGSIGNATURE.items())):
+                                  list(_PROTOS_SIGNATURE.items()) + list(_PROTOS_LOGSIGNATURE.items()) +
+                                  list(_PROTOS_INPUT_NORM.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _check_abi(lib)
@@ -395,6 +410,10 @@ class Precision:
         'signature_ex': ('bsig_signature_ex', 'bsig_signature_ex_f64'),
         # include/bsig_logsignature.h, from _PROTOS_LOGSIGNATURE
         'logsignature': ('bsig_logsignature', 'bsig_logsignature_f64'),
+        # include/bsig_input_norm.h, from _PROTOS_INPUT_NORM: the input-side companions of normalize_rows /
+        # copy_rows (the statistics of rows, and the copy that standardises)
+        'input_norm_stats': ('bsig_input_norm_stats', 'bsig_input_norm_stats_f64'),
+        'input_norm_apply': ('bsig_input_norm_apply', 'bsig_input_norm_apply_f64'),
     }
     HYPER_OPS = ('head_forward', 'head_outputs', 'nll_from_tuple', 'loss_grad')    # take the hyper in fp64
     # the plan lifecycle
@@ -427,7 +446,7 @@ class Precision:
         # has no graphs: it binds the rows where they lie and is never asked for one (FIT_GRAPH)
         self.replays_graphs = self.itemsize == 4
         self._protos = dict(_PROTOS_F64 if self.itemsize == 8 else _PROTOS, **_PROTOS_SIGNATURE,
-                            **_PROTOS_LOGSIGNATURE)
+                            **_PROTOS_LOGSIGNATURE, **_PROTOS_INPUT_NORM)
         for op in (list(self.OPS) + list(self.SIGNATURE_OPS) + list(self.FIT_OPS) +
                    list(self.QUERIES)):                                          # (a typo fails the import)
             assert self.symbol(op) is None or self.symbol(op) in self._protos, op

@@ -68,7 +68,13 @@ class BayesSim(object):
         modes: the summaries are made in fp32 and a double model gets them
         widened; 'float64', only with ``'dtype': 'float64'``: the summarizers
         compute in double too, so nothing between the trajectories and the
-        posterior is rounded to fp32)."""
+        posterior is rounded to fp32), ``inputNorm`` (a bool, default False: the
+        model is built with ``input_norm=True`` and standardises the summaries --
+        per-column mean and standard deviation of the first chunk's training rows,
+        made on the device, kept in ``state_dict`` and applied alike by ``fit``,
+        ``run_training`` and ``predict``; constant columns become zero;
+        include/bsig_input_norm.h.  Meant for ``sigDepth`` >= 3, whose raw terms
+        reach (trainTrajLen - 1)^k / k!)."""
         self.prior = prior
         self.proposal = proposal
         model_class = model_cfg['modelClass']
@@ -142,6 +148,11 @@ class BayesSim(object):
         if matmul == 'split_bf16' and dtype == 'float64':
             raise ValueError("model_cfg['matmulPrecision'] = 'split_bf16' applies to an fp32 estimator, "
                              "not to model_cfg['dtype'] = 'float64'")
+        input_norm = model_cfg.get('inputNorm', False)
+        if not isinstance(input_norm, bool):
+            raise ValueError("model_cfg['inputNorm'] must be a bool, got %r" % (input_norm,))
+        if input_norm:
+            kwargs['input_norm'] = True
         self.model = _MODELS[model_class](**kwargs)
         if matmul is not None:
             self.model.set_matmul_precision(matmul)
@@ -175,21 +186,46 @@ class BayesSim(object):
     def _lazy_summaries(self):
         # (a double model takes summary rows only: materialised by the summarizer kernels -- in fp32 and
         # widened, or in double with 'summaryDtype': 'float64')
+        # (nor does a model that standardises its inputs: the standardised outer product does not factor)
         return (self.model.rff is None and self.model._flat.is_cuda and not self.model._f64 and
-                os.environ.get('BSIG_NO_FUSED_SUMMARY') != '1')
+                self.model._inorm is None and os.environ.get('BSIG_NO_FUSED_SUMMARY') != '1')
 
     def run_training(self, params, traj_states, traj_actions, _defer=False, _finite_flag=None,
-                     _summaries=None, _feats=None):
+                     _summaries=None, _feats=None, _standardized=False):
         """One chunk: summarize, then NUM_GRAD_UPDATES Adam updates of
         MINIBATCH_SIZE (reference bayes_sim.py:91-114)."""
         traj_summaries = _summaries if _summaries is not None else \
             self._summarize(traj_states, traj_actions, _finite_flag, lazy=True)
         kw = {} if _feats is None else {'_feats': _feats}
+        if _standardized:       # fit() has standardised the block these rows come from
+            kw['_standardized'] = True
         return self.model.run_training(
             x_data=traj_summaries, y_data=params,
             n_updates=BayesSim.NUM_GRAD_UPDATES,
             batch_size=BayesSim.MINIBATCH_SIZE,
             test_frac=BayesSim.TEST_FRACTION, _defer=_defer, **kw)
+
+    def fit_input_norm(self, states, actions):
+        """The input statistics of a model built with ``'inputNorm': True`` from the summaries of ALL the
+        given trajectories (``fit`` by itself takes the first chunk's training rows), frozen from here on.
+        Synchronises, and asserts that the statistics are finite."""
+        norm = self.model._require_inorm()
+        self.model.fit_input_norm(self._summarize(states, actions))
+        if not bool((torch.isfinite(norm.mean).all() & torch.isfinite(norm.inv_std).all()).item()):
+            norm.count.zero_()
+            norm.ready = False
+            raise AssertionError('non-finite value in the trajectory summaries')
+        return self
+
+    def _standardize_block(self, summ, n_first):
+        """fit()'s block path for a model with input_norm: the statistics, where they do not exist yet, from
+        the rows the chunk loop would have used -- the training rows of the first chunk, ``n_first`` pairs --
+        then the block standardised in place, once, in the model's precision.  Nothing is read back."""
+        model = self.model
+        summ, ld, prec = model._input_rows(summ, model._prec.dtype)
+        if not model.input_norm_ready:
+            model._stats_of(summ, ld, _lib.split_rows(n_first, BayesSim.TEST_FRACTION)[0], prec)
+        return model.normalize_inputs(summ, out=summ)
 
     FIT_BLOCK_BYTES = 4 << 30        # (not in the reference) bound on a block's summaries in fit()
 
@@ -235,8 +271,10 @@ class BayesSim(object):
         """Block by block: the block's summaries and features when ``done`` leaves the block before; the
         block's chunks in ONE launch of the persistent update kernel where the model's plan can; else chunk
         by chunk.  The logs (and the isfinite asserts) are read back after the last chunk is enqueued: one
-        host synchronisation for the whole fit."""
+        host synchronisation for the whole fit.  A model with input_norm: each block is standardised once,
+        before an MDRFF's features are projected from it, and its chunks are handed over as standardised."""
         model, n, done, pending = self.model, params.shape[0], 0, []
+        model._check_input_norm_dp()
         self._check_equal_counts(n)
         on_gpu = torch.is_tensor(traj_states) and traj_states.is_cuda
         flag = torch.zeros(1, dtype=torch.int32, device=traj_states.device) if on_gpu else None
@@ -247,6 +285,8 @@ class BayesSim(object):
             if block and done >= hi:
                 lo, hi = done, min(n, done + block)
                 summ = self._summarize(traj_states[lo:hi], traj_actions[lo:hi], flag, lazy=True)
+                if model._inorm is not None:
+                    summ = self._standardize_block(summ, BayesSim.get_n_trajs_per_batch(n, lo))
                 # (a double MDRFF projects in double inside each call: chunk by chunk, no block launch)
                 feats = model.rff.to_features(summ) if model.rff is not None and not model._f64 else None
                 sizes = self._block_launch_sizes(n, lo, hi) if feats is not None and model._dp is None else []
@@ -262,7 +302,7 @@ class BayesSim(object):
             if block:
                 pending.append(self.run_training(
                     params[done:done + m], None, None, _defer=True,
-                    _summaries=summ[done - lo:done - lo + m],
+                    _summaries=summ[done - lo:done - lo + m], _standardized=model._inorm is not None,
                     _feats=None if feats is None else feats[done - lo:done - lo + m]))
             else:
                 pending.append(self.run_training(params[done:done + m],

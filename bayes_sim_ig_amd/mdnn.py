@@ -18,6 +18,10 @@ and sizes it uses comes from ``self._prec``, one of ``_lib.F32`` / ``_lib.F64``,
 environment variable BSIG_MATMUL_PRECISION, read when a model is constructed) lets the fit plan's products
 run on the bf16 matrix pipes with every fp32 operand split into three bf16 pieces: fp32-grade results that
 are not bitwise the reference's fp32 arithmetic.  The default, 'float32', is.
+
+``MDNN(..., input_norm=True)`` (not in the reference, which normalises the targets only) adds a standardisation
+of the summaries to the model: per-column mean and reciprocal standard deviation (include/bsig_input_norm.h),
+made once on the device, kept in ``state_dict`` and applied by every entry point that takes summaries.
 """
 import contextlib
 import ctypes as C
@@ -133,6 +137,41 @@ class _FusedNLL(torch.autograd.Function):
         return (None, None, None, None, None, None, *grads)
 
 
+def _flat_rule(mean, std, dtype):
+    """inv_std of include/bsig_input_norm.h from host-given statistics: 0 where std <= 8 u |mean| (u: the unit
+    roundoff of the rows' type ``dtype``), else 1 / std.  float64 numpy in and out."""
+    u = 2.0 ** -52 if dtype == torch.float64 else 2.0 ** -23
+    flat = std <= 8.0 * u * np.abs(mean)
+    with np.errstate(divide='ignore'):
+        return np.where(flat, 0.0, 1.0 / np.where(flat, 1.0, std))
+
+
+class InputNorm(nn.Module):
+    """The statistics of a model built with ``input_norm=True``: ``mean`` and ``inv_std`` (float64
+    [input_dim]: include/bsig_input_norm.h) and ``count`` (int64 scalar: the number of rows they were made
+    from, 0: not there yet).  The buffers follow the model to its device and keep their dtypes through
+    ``.float()`` / ``.double()``.  ``ready`` is the host's copy of ``count > 0``: asking costs no read-back."""
+
+    def __init__(self, width, device):
+        super().__init__()
+        self.width = int(width)
+        self.register_buffer('mean', torch.zeros(self.width, dtype=torch.float64, device=device))
+        self.register_buffer('inv_std', torch.ones(self.width, dtype=torch.float64, device=device))
+        self.register_buffer('count', torch.zeros((), dtype=torch.int64, device=device))
+        self.ready = False
+
+    def _apply(self, fn, *args, **kwargs):
+        # a change of device is followed, a change of dtype is not
+        for name, buf in list(self._buffers.items()):
+            self._buffers[name] = buf.to(fn(buf).device)
+        return self
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        if prefix + 'count' in state_dict:
+            self.ready = int(state_dict[prefix + 'count']) > 0
+
+
 class MDNN(nn.Module):
     LL_LIMIT = 1.0e5     # limit log likelihood to avoid large gradients
     MIN_WEIGHT = 1.0e-5  # minimum component weights to enable updates
@@ -151,7 +190,8 @@ class MDNN(nn.Module):
                  n_gaussians, full_covariance, hidden_layers, activation, lr,
                  device='cpu', **kwargs):
         """Same arguments as the reference (mdnn.py:26-52).  ``device`` must
-        name a GPU for anything beyond construction."""
+        name a GPU for anything beyond construction.  ``input_norm=True`` (a keyword of ``**kwargs``, default
+        False): the model standardises its summaries (``fit_input_norm``)."""
         super(MDNN, self).__init__()
         self.input_dim = input_dim
         self.output_dim = output_dim
@@ -207,6 +247,10 @@ class MDNN(nn.Module):
         self._block_launches = 0
         self._matmul = _lib.default_matmul_precision()      # (BSIG_MATMUL_PRECISION; ValueError on a bad value)
         self._flatten(device)
+        # after every submodule of the reference, and nothing drawn from an RNG: the initialisation and the
+        # state_dict keys of a default model are untouched
+        if kwargs.get('input_norm', False):
+            self.input_norm = InputNorm(kwargs.get('_input_norm_dim', input_dim), device)
 
     # ------------------------------------------------------------ plumbing
     def _cfg(self):
@@ -467,6 +511,107 @@ class MDNN(nn.Module):
             return 0
         return int(torch.randint(0, 2 ** 62, (1,)).item())
 
+    # ------------------------------------------------- input standardisation
+    @property
+    def _inorm(self):
+        """The InputNorm submodule of a model built with ``input_norm=True``, else None."""
+        return self._modules.get('input_norm')
+
+    @property
+    def input_norm_ready(self):
+        """True once a model built with ``input_norm=True`` has its statistics (``fit_input_norm``,
+        ``set_input_norm``, the first ``run_training``, ``load_state_dict``).  False for any other model."""
+        return self._inorm is not None and self._inorm.ready
+
+    def _require_inorm(self, ready=False):
+        norm = self._inorm
+        if norm is None:
+            raise RuntimeError('this model was built without input_norm=True')
+        if ready and not norm.ready:
+            raise RuntimeError('the input statistics of this model do not exist yet: run_training makes them '
+                               'from its first training rows; or call fit_input_norm / set_input_norm / '
+                               'load_state_dict first')
+        return norm
+
+    def _stats_of(self, xs, ld, n, prec):
+        """mean / inv_std <- the statistics of the first ``n`` rows of ``xs`` (a device tensor of
+        ``prec``'s dtype), frozen from here on.  Asynchronous: ``count`` is written on the stream."""
+        lib, norm = self._gpu(), self._inorm
+        need = int(lib.bsig_input_norm_workspace_bytes(n, norm.width))
+        assert need > 0, 'input statistics need at least one row'
+        ws = self._buf('inorm_ws', need // 8, torch.float64)
+        prec.input_norm_stats(_lib.ptr(xs), ld, n, norm.width, _lib.ptr(norm.mean), _lib.ptr(norm.inv_std),
+                              _lib.ptr(ws), ws.numel() * 8, _lib.stream())
+        norm.count.fill_(n)
+        norm.ready = True
+
+    def _input_rows(self, x, dtype=None):
+        """``x`` as device rows of ``dtype`` (default: its own where that is fp32 or fp64, else fp32)."""
+        if hasattr(x, 'materialize'):
+            x = x.materialize()
+        if dtype is None:
+            dtype = torch.float64 if x.dtype == torch.float64 else torch.float32
+        xs, ld = _lib.as_rows(x, self._flat.device, dtype)
+        assert xs.shape[1] == self._inorm.width, 'expected rows of %d columns' % self._inorm.width
+        return xs, ld, (_lib.F64 if dtype == torch.float64 else _lib.F32)
+
+    @_on_model_device
+    def fit_input_norm(self, x):
+        """Make the statistics from ALL rows of ``x`` on the device and freeze them: no later call refits.
+        The rows are taken in the model's precision, as ``run_training`` takes them when it makes the
+        statistics itself (an fp32 model narrows double rows first, a double model widens fp32 rows)."""
+        self._require_inorm()
+        self._gpu()
+        xs, ld, prec = self._input_rows(x, self._prec.dtype)
+        self._stats_of(xs, ld, xs.shape[0], prec)
+        return self
+
+    def set_input_norm(self, mean, std, count=1, dtype=None):
+        """The host-given form of ``fit_input_norm``: ``mean`` and ``std`` [input_dim]; ``inv_std`` follows
+        by the flat rule of include/bsig_input_norm.h with the unit roundoff of ``dtype`` (default: the
+        model's).  ``count``: the number of rows behind them where known (any positive number: ready)."""
+        norm = self._require_inorm()
+        mean = np.asarray(torch.as_tensor(mean).detach().cpu().numpy(), dtype=np.float64).reshape(-1)
+        std = np.asarray(torch.as_tensor(std).detach().cpu().numpy(), dtype=np.float64).reshape(-1)
+        if mean.shape != (norm.width,) or std.shape != (norm.width,):
+            raise ValueError('set_input_norm: mean and std must hold %d values' % norm.width)
+        if not (std >= 0).all() or int(count) < 1:
+            raise ValueError('set_input_norm: std must be >= 0 and count >= 1')
+        inv = _flat_rule(mean, std, dtype or self._dtype)
+        norm.mean.copy_(torch.from_numpy(mean))
+        norm.inv_std.copy_(torch.from_numpy(inv))
+        norm.count.fill_(int(count))
+        norm.ready = True
+        return self
+
+    @_on_model_device
+    def normalize_inputs(self, x, out=None):
+        """The counterpart of ``normalize_samples`` for the other side: (x - mean) * inv_std of summary rows
+        ``x``, in ``x``'s own type (the fp32 or the double kernel).  ``out``: rows of the same type and shape
+        on the device, last dimension contiguous; ``out is x`` standardises in place."""
+        norm = self._require_inorm(ready=True)
+        self._gpu()
+        xs, ld, prec = self._input_rows(x)
+        if out is None:
+            out = torch.empty(xs.shape, dtype=prec.dtype, device=xs.device)
+        if not (out.is_cuda and out.dtype == prec.dtype and out.shape == xs.shape and out.stride(1) == 1):
+            raise AssertionError('normalize_inputs: out must be device rows of the type and shape of x')
+        ld_out = out.stride(0) if out.shape[0] > 1 else max(out.shape[1], 1)
+        prec.input_norm_apply(_lib.ptr(xs), ld, _lib.ptr(norm.mean), _lib.ptr(norm.inv_std), _lib.ptr(out),
+                              ld_out, xs.shape[0], norm.width, _lib.stream())
+        return out
+
+    def _check_input_norm_dp(self):
+        if self._inorm is not None and not self._inorm.ready and self._dp is not None:
+            raise ValueError('a data-parallel model with input_norm needs its input statistics before '
+                             'run_training (every rank would fit them on its own first chunk): call '
+                             'fit_input_norm or set_input_norm with the same values on every rank first')
+
+    def _standardised(self, x):
+        """Fresh rows of the model's precision: ``x`` standardised (the model has ready statistics)."""
+        xs, _, _ = self._input_rows(x, self._prec.dtype)
+        return self.normalize_inputs(xs)
+
     # ----------------------------------------------------------- forward
     @_on_model_device
     def _head_forward(self, x, is_feat=False):
@@ -493,10 +638,14 @@ class MDNN(nn.Module):
     def forward(self, x, noise=None, _is_feat=False):
         """Reference mdnn.py:89-125 -> (weights[B,K], mu[B,D,K], L_d[B,D,K],
         L[B,L_size,K] | None).  ``noise`` injects the rand_like draw.  Takes no plan: its products
-        are fp32 whatever the model's matmul precision."""
+        are fp32 whatever the model's matmul precision.  A model with ``input_norm`` standardises ``x``
+        first (RuntimeError while it has no statistics)."""
+        norm = self._inorm if not _is_feat else None
+        if norm is not None:
+            self._require_inorm(ready=True)
         self._gpu()
         prec = self._prec
-        cfg, out = self._head_forward(x, _is_feat)
+        cfg, out = self._head_forward(x if norm is None else self._standardised(x), _is_feat)
         b, d, k = out.shape[0], self.output_dim, self.n_gaussians
         dev, dt = out.device, self._dtype
         weights = torch.empty((b, k), dtype=dt, device=dev)
@@ -555,12 +704,14 @@ class MDNN(nn.Module):
         """forward + mdn_loss_fn + backward for one minibatch
         (mdnn.py:229-233): returns the 0-dim loss; gradients land in every
         parameter's ``.grad`` (views of the flat gradient buffer).  ``y`` is
-        already normalised."""
+        already normalised; ``x`` is not standardised yet (a model with ``input_norm`` does that here)."""
+        if self._inorm is not None:
+            self._require_inorm(ready=True)
         self._gpu()
         prec = self._prec
         cfg = self._cfg()
         dev = self._flat.device
-        xs, ldx = _lib.as_rows(x, dev, prec.dtype)
+        xs, ldx = _lib.as_rows(x if self._inorm is None else self._standardised(x), dev, prec.dtype)
         ys, ldy = _lib.as_rows(y, dev, prec.dtype)
         ridx = None
         b = xs.shape[0]
@@ -614,16 +765,27 @@ class MDNN(nn.Module):
         """Replica state outside the flat parameter buffer (MDRFF: the RFF frequencies)."""
 
     def run_training(self, x_data, y_data, n_updates, batch_size, test_frac=0.2,
-                     ids_table=None, _defer=False, _feats=None):
+                     ids_table=None, _defer=False, _feats=None, _standardized=False):
         """Reference mdnn.py:180-243.  Returns {'train_loss': [...],
         'test_loss': [...]} with the same 6 logging points.  ``ids_table``
         [n_updates, batch] (optional) overrides the numpy-RNG minibatch draw
-        (teacher forcing for parity tests)."""
+        (teacher forcing for parity tests).
+
+        A model with ``input_norm`` standardises ``x_data`` on its way into the chunk staging (the fp32
+        staging copy is the standardising copy; a double model standardises into a buffer of its own).
+        While it has no statistics, the call makes them from its own training rows -- the first ``n_train``
+        of the split, never the held-out rows -- and freezes them: the reference's chunk protocol takes them
+        from the first chunk's 800 training rows.  Under ``enable_data_parallel`` that would give every
+        replica another scale: ValueError, before anything is enqueued.  A ``CrossCorrFactors`` input is
+        materialised first (the standardised outer product does not factor): the call then behaves as under
+        BSIG_NO_FUSED_SUMMARY=1, on whatever plan the engine has for summary rows."""
         self._check_f64_dp()
+        if not _standardized:
+            self._check_input_norm_dp()
 
         def once():
             return self._run_training_once(x_data, y_data, n_updates, batch_size, test_frac,
-                                           ids_table, _defer, _feats)
+                                           ids_table, _defer, _feats, _standardized)
         # (deferred logs: the caller -- BayesSim.fit -- holds the snapshot and repeats its loop)
         return once() if _defer else self._retrying(once)
 
@@ -791,7 +953,7 @@ class MDNN(nn.Module):
 
     @_on_model_device
     def _run_training_once(self, x_data, y_data, n_updates, batch_size, test_frac=0.2,
-                           ids_table=None, _defer=False, _feats=None):
+                           ids_table=None, _defer=False, _feats=None, _standardized=False):
         assert x_data.shape[0] == y_data.shape[0]
         lib, prec = self._gpu(), self._prec
         self.train()
@@ -808,6 +970,13 @@ class MDNN(nn.Module):
         if isinstance(x_data, CrossCorrFactors) and \
                 not prec.accepts_factor_rows(self._plan, x_data.s_dim, x_data.a_dim):
             x_data = x_data.materialize()
+        # input_norm: summary rows of the model's precision; the statistics, where they do not exist yet,
+        # from this call's training rows (``_standardized``: the caller -- BayesSim.fit -- has done both)
+        norm = None if _standardized else self._inorm
+        if norm is not None:
+            x_data, ld_raw, _ = self._input_rows(x_data, prec.dtype)
+            if not norm.ready:
+                self._stats_of(x_data, ld_raw, n_train, prec)
         ldy = _lib.round_up(d, 4)
         ys, ldy_src = _lib.as_rows(y_data, dev, prec.dtype)
         assert x_data.shape[1] == self.input_dim and ys.shape[1] == d
@@ -826,6 +995,9 @@ class MDNN(nn.Module):
         elif not prec.replays_graphs:
             # no graph to replay in this precision: the (widened) rows are bound where they lie
             x_stage, ldx = _lib.as_rows(x_data, dev, prec.dtype)
+            if norm is not None:      # ... and standardised into a buffer of the model's
+                ldx = self.input_dim
+                x_stage = self.normalize_inputs(x_stage, self._buf('x_norm', n_tot * ldx)[:n_tot * ldx].view(n_tot, ldx))
             self._bufs['x_keepalive'] = (x_stage, None)
         else:
             # chunk staging: fixed addresses (graph replay) and 16-B aligned rows
@@ -834,7 +1006,11 @@ class MDNN(nn.Module):
             x_stage = self._buf('x_stage', cap_rows * ldx)
             # (an MDRFF whose rows' features are handed over never reads the summaries themselves)
             if _feats is None or not prec.takes_features(self._plan, n_train):
-                prec.copy_rows(_lib.ptr(xs), ldx_src, None, _lib.ptr(x_stage), ldx, n_tot, self.input_dim, st)
+                if norm is not None:      # the staging copy IS the standardising copy: no further pass
+                    prec.input_norm_apply(_lib.ptr(xs), ldx_src, _lib.ptr(norm.mean), _lib.ptr(norm.inv_std),
+                                          _lib.ptr(x_stage), ldx, n_tot, self.input_dim, st)
+                else:
+                    prec.copy_rows(_lib.ptr(xs), ldx_src, None, _lib.ptr(x_stage), ldx, n_tot, self.input_dim, st)
         y_stage = self._buf('y_stage', cap_rows * ldy)
         self._stage_targets(ys, ldy_src, y_stage, ldy, n_tot, st)
         n_ids = n_updates * batch_size
@@ -912,11 +1088,15 @@ class MDNN(nn.Module):
         """Reference mdnn.py:250-289: one pdf.MoG per row of ``xs`` with
         de-normalised means and [diag | strict-lower] factors.  The
         full-covariance row indexing bug of mdnn.py:281 (``L[:, :, comp_id]``
-        instead of ``L[pt, :, comp_id]``) is not reproduced."""
+        instead of ``L[pt, :, comp_id]``) is not reproduced.  A model with ``input_norm`` standardises
+        ``xs`` first (before an MDRFF's projection)."""
         ntest, dim = xs.size()
+        if self._inorm is not None:
+            self._require_inorm(ready=True)
         if self.rff is not None and self._matmul != 'float32':
             # the projection follows the model's matmul precision; the head products stay fp32
-            w, mu, l_d, low = self.forward(self.rff.to_features(xs), noise=noise, _is_feat=True)
+            feats = self.rff.to_features(xs if self._inorm is None else self._standardised(xs))
+            w, mu, l_d, low = self.forward(feats, noise=noise, _is_feat=True)
         else:
             w, mu, l_d, low = self.forward(xs, noise=noise)
         w, mu, l_d = w.cpu().numpy(), mu.cpu().numpy(), l_d.cpu().numpy()

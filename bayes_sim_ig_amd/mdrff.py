@@ -17,14 +17,17 @@ class MDRFF(MDNN):
                  n_gaussians, lr, activation, full_covariance, device='cpu',
                  n_feat=500, kernel='RBF', sigma=1.0, freqs=None, **kwargs):
         """Same arguments as the reference (mdrff.py:15-17); ``freqs``
-        optionally injects the [n_feat/2, input_dim] frequency matrix."""
+        optionally injects the [n_feat/2, input_dim] frequency matrix; ``input_norm=True`` (a keyword of
+        ``**kwargs``): the summaries are standardised before the projection (MDNN.fit_input_norm)."""
         self._rff_input_dim = input_dim
         a = (2.0 / float(n_feat)) ** 0.5          # rff.py:107
         super().__init__(n_feat, output_dim, output_lows, output_highs,
                          n_gaussians, hidden_layers=[], lr=lr,
                          activation=activation,
                          full_covariance=full_covariance, device=device,
-                         _rff_feats=n_feat, _rff_scale=a)
+                         _rff_feats=n_feat, _rff_scale=a,
+                         # (the statistics are those of the summary rows, before the projection)
+                         input_norm=kwargs.get('input_norm', False), _input_norm_dim=input_dim)
         # heads see n_feat inputs; the estimator's rows are input_dim wide
         self.input_dim = input_dim
         self.rff = RFF(n_feat, input_dim, sigma, cos_only=False,

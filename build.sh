@@ -3,7 +3,7 @@
 # An object is rebuilt when the CONTENT of its source, of any csrc header, of include/bsig.h, include/bsig_matmul.h or the
 # flags changed (a stamp next to the object; file times do not survive every transport).  The objects of the fp64 mode
 # and of the general signature kernel also cover include/bsig_f64.h and include/bsig_signature.h, those of the
-# log-signature kernel include/bsig_logsignature.h as well.
+# log-signature kernel include/bsig_logsignature.h as well, those of the input standardisation include/bsig_input_norm.h.
 set -euo pipefail
 cd "$(dirname "$0")"
 SRC=bayes_sim_ig_amd/csrc
@@ -28,6 +28,8 @@ COMMON64=$(cat "$SRC"/f64/*.h include/bsig_f64.h | sha256sum | cut -d' ' -f1)
 SIGEX=$(sha256sum < include/bsig_signature.h | cut -d' ' -f1)
 # the log-signature kernel (csrc/logsignature.h, include/bsig_logsignature.h) sees both headers
 LOGSIG=$(cat include/bsig_signature.h include/bsig_logsignature.h | sha256sum | cut -d' ' -f1)
+# the input standardisation (csrc/input_norm.h, include/bsig_input_norm.h), in both precisions
+INORM=$(sha256sum < include/bsig_input_norm.h | cut -d' ' -f1)
 pids=()
 build_one() {  # name, source, extra flags[, hash of further headers the source sees]
   local stamp="$OUT/obj/$1.stamp"
@@ -46,6 +48,8 @@ build_one signature_ex "$SRC/signature_ex.hip" "" "$SIGEX"
 build_one signature_ex_f64 "$SRC/f64/signature_ex_f64.hip" "" "$COMMON64 $SIGEX"
 build_one logsignature "$SRC/logsignature.hip" "" "$LOGSIG"
 build_one logsignature_f64 "$SRC/f64/logsignature_f64.hip" "" "$COMMON64 $LOGSIG"
+build_one input_norm "$SRC/input_norm.hip" "" "$INORM"
+build_one input_norm_f64 "$SRC/f64/input_norm_f64.hip" "" "$COMMON64 $INORM"
 for f in api comm; do
   build_one "$f" "$SRC/$f.cpp" "-x hip"
 done
