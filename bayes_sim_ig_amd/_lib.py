@@ -1,5 +1,5 @@
-"""ctypes binding of libbsig_hip.so (include/bsig.h, include/bsig_f64.h, include/bsig_matmul.h,
-include/bsig_signature.h, include/bsig_logsignature.h, include/bsig_input_norm.h).
+"""ctypes binding of libbsig_hip.so: every public header include/bsig*.h, one table of prototypes per header
+(``HEADERS``), merged into the one table (``PROTOS``) the loader and the precision seam read.
 
 Whether a call computes in fp32 or fp64 is decided in ONE place, the two ``Precision`` objects ``F32`` and
 ``F64`` below: they carry the dtype, the sizes and the entry points that exist in both modes under one
@@ -109,7 +109,15 @@ def fit_chunk_table(sizes, seeds, n_updates, batch_size, test_frac):
     return table
 
 
-_PROTOS = {
+_HD, _HY, _CFG = C.POINTER(HeadDims), C.POINTER(F64Hyper), C.POINTER(MdnCfg)
+SIGNATURE_MAX_DEPTH = 6        # include/bsig_signature.h
+INPUT_NORM_SLAB_ROWS = 64      # include/bsig_input_norm.h
+# public header -> the prototypes of its declarations: name -> (restype, argtypes).  A new header adds its
+# table here and nothing else; tests/test_headers_host.py holds every table against its header.  (The tables of
+# the two base headers also go by a name: an entry point Precision routes fp32 to must not be one of the fp64
+# header and the other way round.)
+HEADERS = {}
+HEADERS['bsig.h'] = _PROTOS = {
     'bsig_last_error': (C.c_char_p, []),
     'bsig_version': (C.c_int, []),
     'bsig_abi_info': (u64, [C.c_int]),
@@ -197,9 +205,8 @@ _PROTOS = {
     'bsig_debug_fit_schedule': (C.c_int, [C.c_int, C.c_int, C.c_int, vp, C.c_int]),
     'bsig_fit_run_dp': (C.c_int, [vp, vp, i64, vp, vp]),
 }
-# include/bsig_f64.h: the fp64 mode
-_HD, _HY, _CFG = C.POINTER(HeadDims), C.POINTER(F64Hyper), C.POINTER(MdnCfg)
-_PROTOS_F64 = {
+# the fp64 mode
+HEADERS['bsig_f64.h'] = _PROTOS_F64 = {
     'bsig_summary_start_f64': (C.c_int, [vp, vp, vp, i64] + [C.c_int] * 5 + [i64, vp]),
     'bsig_crosscorr_f64': (C.c_int, [vp, vp, vp, i64] + [C.c_int] * 5 + [i64, vp, vp]),
     'bsig_signature_f64': (C.c_int, [vp, vp, vp, i64] + [C.c_int] * 4 + [i64, vp]),
@@ -228,31 +235,29 @@ _PROTOS_F64 = {
     'bsig_fit64_run': (C.c_int, [vp, i64, vp]),
     'bsig_fit64_pack_logs': (C.c_int, [vp, i64, i64, vp, vp]),
 }
-# include/bsig_matmul.h: the matmul precision of the fp32 products
-_PROTOS_MATMUL = {
-    'bsig_gemm_f32_ex': (C.c_int, _PROTOS['bsig_gemm_f32'][1] + [C.c_int]),
-    'bsig_rff_project_ex': (C.c_int, _PROTOS['bsig_rff_project'][1] + [C.c_int]),
+# the matmul precision of the fp32 products
+HEADERS['bsig_matmul.h'] = {
+    'bsig_gemm_f32_ex': (C.c_int, HEADERS['bsig.h']['bsig_gemm_f32'][1] + [C.c_int]),
+    'bsig_rff_project_ex': (C.c_int, HEADERS['bsig.h']['bsig_rff_project'][1] + [C.c_int]),
     'bsig_debug_gemm_path': (C.c_int, [i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, sz, C.c_int,
                                        C.POINTER(C.c_int32)]),
 }
-# include/bsig_signature.h: signatures beyond depth 3 and on a chosen subset of channels
-SIGNATURE_MAX_DEPTH = 6
-_PROTOS_SIGNATURE = {
+# signatures beyond depth 3 and on a chosen subset of channels
+HEADERS['bsig_signature.h'] = {
     'bsig_signature_ex_dim': (i64, [C.c_int, C.c_int]),
     'bsig_signature_ex_fits': (C.c_int, [C.c_int] * 4),
     'bsig_signature_ex': (C.c_int, [vp, vp, vp, C.c_int, vp, i64] + [C.c_int] * 4 + [i64, vp]),
     'bsig_signature_ex_f64': (C.c_int, [vp, vp, vp, C.c_int, vp, i64] + [C.c_int] * 4 + [i64, vp]),
 }
-# include/bsig_logsignature.h: the log-signature at the Lyndon words, on the general signature kernel
-_PROTOS_LOGSIGNATURE = {
+# the log-signature at the Lyndon words, on the general signature kernel
+HEADERS['bsig_logsignature.h'] = {
     'bsig_logsignature_dim': (i64, [C.c_int, C.c_int]),
     'bsig_logsignature_words': (C.c_int, [C.c_int, C.c_int, C.POINTER(i32), i64]),
     'bsig_logsignature': (C.c_int, [vp, vp, vp, C.c_int, vp, vp, i64] + [C.c_int] * 4 + [i64, vp]),
     'bsig_logsignature_f64': (C.c_int, [vp, vp, vp, C.c_int, vp, vp, i64] + [C.c_int] * 4 + [i64, vp]),
 }
-# include/bsig_input_norm.h: column statistics of the estimator's input rows and their standardisation
-INPUT_NORM_SLAB_ROWS = 64
-_PROTOS_INPUT_NORM = {
+# column statistics of the estimator's input rows and their standardisation
+HEADERS['bsig_input_norm.h'] = {
     'bsig_input_norm_workspace_bytes': (i64, [i64, i64]),
     'bsig_input_norm_stats': (C.c_int, [vp, i64, i64, i64, vp, vp, vp, sz, vp]),
     'bsig_input_norm_stats_f64': (C.c_int, [vp, i64, i64, i64, vp, vp, vp, sz, vp]),
@@ -263,37 +268,27 @@ COMM_ID_BYTES = 128
 EXCHANGE_SUM, EXCHANGE_BROADCAST = 0, 1
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int, vp, i64, C.c_int, vp)
 
+
+
+def _merged(headers):
+    """Every header's prototypes in one table.  A name belongs to one header: ImportError otherwise."""
+    protos = {}
+    for header, table in headers.items():
+        twice = sorted(set(table) & set(protos))
+        if twice:
+            raise ImportError('include/%s declares %s, which another header declares too' % (header, twice))
+        protos.update(table)
+    return protos
+
+
+PROTOS = _merged(HEADERS)
+
 _lib = None
 
 
-def exported_symbols():
-    """Names every declaration of include/bsig.h must resolve to."""
-    return sorted(_PROTOS)
-
-
-def exported_symbols_f64():
-    """Names every declaration of include/bsig_f64.h must resolve to."""
-    return sorted(_PROTOS_F64)
-
-
-def exported_symbols_matmul():
-    """Names every declaration of include/bsig_matmul.h must resolve to."""
-    return sorted(_PROTOS_MATMUL)
-
-
-def exported_symbols_signature():
-    """Names every declaration of include/bsig_signature.h must resolve to."""
-    return sorted(_PROTOS_SIGNATURE)
-
-
-def exported_symbols_logsignature():
-    """Names every declaration of include/bsig_logsignature.h must resolve to."""
-    return sorted(_PROTOS_LOGSIGNATURE)
-
-
-def exported_symbols_input_norm():
-    """Names every declaration of include/bsig_input_norm.h must resolve to."""
-    return sorted(_PROTOS_INPUT_NORM)
+def exported_symbols(header='bsig.h'):
+    """Names every declaration of include/<header> must resolve to; ``header=None``: those of every header."""
+    return sorted(PROTOS if header is None else HEADERS[header])
 
 
 def matmul_precision(name):
@@ -319,9 +314,7 @@ def load():
                 'libbsig_hip.so not built (%s): run ./build.sh or '
                 '__graft_entry__.build(); there is no CPU fallback' % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in (list(_PROTOS.items()) + list(_PROTOS_F64.items()) + list(_PROTOS_MATMUL.items()) +
-                                  list(_PROTOS_SIGNATURE.items()) + list(_PROTOS_LOGSIGNATURE.items()) +
-                                  list(_PROTOS_INPUT_NORM.items())):
+        for name, (res, args) in PROTOS.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _check_abi(lib)
@@ -390,7 +383,7 @@ class Precision:
     What an fp64 plan cannot do (persistent kernels, factor rows, handed-over features, block launches) it
     answers here, WITHOUT calling the library: no bsig_fit_* function ever sees a plan that
     bsig_fit64_create made."""
-    # operation -> (fp32 symbol, fp64 symbol)
+    # operation -> (fp32 symbol, fp64 symbol), whichever header declares them
     OPS = {
         'summary_start': ('bsig_summary_start', 'bsig_summary_start_f64'),
         'crosscorr': ('bsig_crosscorr', 'bsig_crosscorr_f64'),
@@ -404,14 +397,10 @@ class Precision:
         'adam_flat': ('bsig_adam_flat', 'bsig_adam_flat_f64'),
         'normalize_rows': ('bsig_normalize_rows', 'bsig_normalize_rows_f64'),
         'copy_rows': ('bsig_copy_rows', 'bsig_copy_rows_f64'),
-    }
-    # include/bsig_signature.h (the general signature kernel): resolved like OPS, from _PROTOS_SIGNATURE
-    SIGNATURE_OPS = {
         'signature_ex': ('bsig_signature_ex', 'bsig_signature_ex_f64'),
-        # include/bsig_logsignature.h, from _PROTOS_LOGSIGNATURE
         'logsignature': ('bsig_logsignature', 'bsig_logsignature_f64'),
-        # include/bsig_input_norm.h, from _PROTOS_INPUT_NORM: the input-side companions of normalize_rows /
-        # copy_rows (the statistics of rows, and the copy that standardises)
+        # the input-side companions of normalize_rows / copy_rows (the statistics of rows, and the copy that
+        # standardises)
         'input_norm_stats': ('bsig_input_norm_stats', 'bsig_input_norm_stats_f64'),
         'input_norm_apply': ('bsig_input_norm_apply', 'bsig_input_norm_apply_f64'),
     }
@@ -437,6 +426,10 @@ class Precision:
         'fit_set_features': ('bsig_fit_set_features', BSIG_EUNSUPPORTED),
     }
 
+    # every operation's pair: (fp32 symbol, fp64 symbol, or what an fp64 plan answers in its place)
+    _SYMBOLS = {**OPS, **FIT_OPS, **QUERIES}
+    assert len(_SYMBOLS) == len(OPS) + len(FIT_OPS) + len(QUERIES)
+
     def __init__(self, dtype):
         self.dtype = dtype
         self.itemsize = 8 if dtype == torch.float64 else 4
@@ -445,23 +438,22 @@ class Precision:
         # fp32 replays an update from a HIP graph, so a call's rows are staged at fixed addresses; fp64
         # has no graphs: it binds the rows where they lie and is never asked for one (FIT_GRAPH)
         self.replays_graphs = self.itemsize == 4
-        self._protos = dict(_PROTOS_F64 if self.itemsize == 8 else _PROTOS, **_PROTOS_SIGNATURE,
-                            **_PROTOS_LOGSIGNATURE, **_PROTOS_INPUT_NORM)
-        for op in (list(self.OPS) + list(self.SIGNATURE_OPS) + list(self.FIT_OPS) +
-                   list(self.QUERIES)):                                          # (a typo fails the import)
-            assert self.symbol(op) is None or self.symbol(op) in self._protos, op
+        other = _PROTOS if self.itemsize == 8 else _PROTOS_F64      # the other precision's own header
+        for op in self._SYMBOLS:                                                 # (a typo fails the import)
+            name = self.symbol(op)
+            assert name is None or (name in PROTOS and name not in other), op
 
     def __repr__(self):
         return 'Precision(%s)' % (self.dtype,)
 
     def symbol(self, op):
         """The library symbol behind ``op``; None where this precision answers without the library."""
-        if op in self.QUERIES:
-            return None if self.itemsize == 8 else self.QUERIES[op][0]
-        return (self.OPS.get(op) or self.SIGNATURE_OPS.get(op) or self.FIT_OPS[op])[self.itemsize == 8]
+        if op in self.QUERIES and self.itemsize == 8:
+            return None
+        return self._SYMBOLS[op][self.itemsize == 8]
 
     def __getattr__(self, op):       # the first use of an entry point
-        if op not in self.OPS and op not in self.SIGNATURE_OPS and op not in self.FIT_OPS and op not in self.QUERIES:
+        if op not in self._SYMBOLS:
             raise AttributeError(op)
         self._resolve()
         return vars(self)[op]
@@ -474,14 +466,16 @@ class Precision:
                 return lambda first, hyper, *rest: check(fn(first, *rest))
             return lambda *args: check(fn(*args))
 
-        for op in list(self.OPS) + list(self.SIGNATURE_OPS) + list(self.FIT_OPS):
+        for op in self._SYMBOLS:
             name = self.symbol(op)
-            fn = getattr(lib, name)
-            if self._protos[name][0] is C.c_int:      # a return code (the others: a size, nothing)
-                fn = checked(fn, drop_hyper=op in self.HYPER_OPS and not is64)
+            if name is None:                          # what an fp64 plan answers without the library
+                fn = (lambda *args, answer=self.QUERIES[op][1]: answer)
+            else:
+                fn = getattr(lib, name)
+                # a return code is checked (the others: a size, nothing; a query's answer is the caller's)
+                if op not in self.QUERIES and PROTOS[name][0] is C.c_int:
+                    fn = checked(fn, drop_hyper=op in self.HYPER_OPS and not is64)
             setattr(self, op, fn)
-        for op, (name, answer) in self.QUERIES.items():
-            setattr(self, op, (lambda *args, answer=answer: answer) if is64 else getattr(lib, name))
         create, pack = self.fit_create, self.fit_pack_logs
 
         def fit_create(cfg, hyper, batch, max_train, max_test, n_updates, flags):

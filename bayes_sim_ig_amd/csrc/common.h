@@ -68,8 +68,54 @@ inline bool aligned(const void* p, size_t bytes) {
   return (reinterpret_cast<uintptr_t>(p) % bytes) == 0;
 }
 
+// ---- launch helpers (host) --------------------------------------------------
+constexpr size_t kLdsBytes = 160 * 1024;     // the LDS of one workgroup on gfx950
+constexpr size_t kLdsUnraised = 64 * 1024;   // the dynamic LDS a kernel may be launched with before its limit is raised
+
+// One workgroup per trajectory, at most `cap` of them; the kernels grid-stride.
+inline int capped_grid(int64_t n, int64_t cap) { return (int)(n < cap ? n : cap); }
+constexpr int64_t kSummaryGridCap = 256 * 64;   // the fp32 summarizers' (fp64: BSIG_F64_SUMMARY_GRID_CAP)
+
+// The reference's default signature depth for a path of dimension d (summarizers.py:133-141).
+inline int ref_signature_depth(int64_t d) {
+  for (int depth = 3; depth >= 0; --depth) {
+    int64_t p = 1;
+    for (int q = 0; q < depth; ++q) p *= d;
+    if (p <= 110 * 110) return depth;
+  }
+  return 1;
+}
+
+// A launch with more than kLdsUnraised bytes of dynamic LDS needs the kernel's limit
+// (hipFuncAttributeMaxDynamicSharedMemorySize) raised first.  The attribute belongs to the function ON A
+// DEVICE: raise_lds_limit sets it on the current device, once per device and kernel -- `raised` is that
+// kernel's own, static next to its launcher.  A device index outside the flags is set every time.
+// The callers decide whether to ask (the summarizers: only above kLdsUnraised; gemm_wide and the
+// persistent engines: always) and for how much (gemm_wide: its exact size; the others: kLdsBytes).
+// The fp32 launchers of summarizers.hip do NOT ask: they launch up to their own 150 KB cap without the
+// attribute, which the runtime accepts (the cc_lds_edge / sig_d32_lds_edge cases of the GPU tests).
+// That asymmetry is as it was found; nothing here depends on it.
+struct LdsRaised { bool on_device[64] = {}; };
+template <typename K>
+inline int raise_lds_limit(K kernel, int bytes, LdsRaised* raised) {
+  constexpr int n_flags = (int)(sizeof(raised->on_device) / sizeof(raised->on_device[0]));
+  int dev = 0;
+  BSIG_HIP(hipGetDevice(&dev));
+  const bool flagged = dev >= 0 && dev < n_flags;
+  if (flagged && raised->on_device[dev]) return BSIG_OK;
+  BSIG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               bytes));
+  if (flagged) raised->on_device[dev] = true;
+  return BSIG_OK;
+}
+
 // ---- wave / block reductions (64-lane wavefronts) -------------------------
 __device__ inline float wave_sum(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;

@@ -35,11 +35,6 @@ struct HeadArgs {
   int32_t* nonfinite;
 };
 
-__device__ inline double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 // every thread gets the block's sum; `scratch` holds blockDim.x / 64 doubles
 __device__ inline double block_sum_f64(double v, double* scratch) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -319,7 +314,7 @@ static int head_geom(const bsig_head_dims* d, HeadGeom* g) {
   g->Ls = d->full_cov ? d->out_dim * (d->out_dim - 1) / 2 : 0;
   g->Nh = g->K + 2 * g->D * g->K + g->Ls * g->K;
   g->lds = (size_t)kRowsPerBlock * ((g->Ls ? 2 : 1) * (size_t)g->D * g->K + g->K) * sizeof(double);
-  if (g->lds > 64 * 1024) {
+  if (g->lds > kLdsUnraised) {
     set_error("mdn head f64: %zu B of LDS needed for one workgroup", g->lds);
     return BSIG_EUNSUPPORTED;
   }

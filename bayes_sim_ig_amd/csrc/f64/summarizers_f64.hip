@@ -10,9 +10,6 @@
 namespace bsig {
 namespace f64 {
 
-// the most LDS one workgroup can have on gfx950 (every byte of these kernels' is dynamic)
-constexpr size_t kLdsMax = 160 * 1024;
-
 // ------------------------------------------------------------------ K1
 // summary_start / summary_waypts: summarizers.py:65-87 after the crop/pad of :20-62.
 //   out[n, t*(sd+ad)+c] = c<sd ? s[n,min(t,Ts-1),c] : a[n,min(t,Ta-1),c-sd]
@@ -31,12 +28,6 @@ __global__ __launch_bounds__(256) void summary_start_f64_kernel(
         o[(int64_t)t * width + c] = c < sd ? srow[c] : arow[c - sd];
     }
   }
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 // ------------------------------------------------------------------ K2
@@ -78,13 +69,13 @@ __global__ __launch_bounds__(256) void crosscorr_f64_kernel(
     // itself, same values in the same order in each
     double part = 0.0;
     for (int i = ln; i < S; i += 64) part += sf[i];
-    const double mean = wave_sum(part) / (double)S;
+    const double mean = wave_sum_f64(part) / (double)S;
     part = 0.0;
     for (int i = ln; i < S; i += 64) {
       const double dv = sf[i] - mean;
       part += dv * dv;
     }
-    const double sdev = S < 2 ? 0.0 : sqrt(wave_sum(part) / (double)(S - 1));
+    const double sdev = S < 2 ? 0.0 : sqrt(wave_sum_f64(part) / (double)(S - 1));
     const int64_t total = (int64_t)S * A;
     bool bad = false;
     const int step_i = nt / A, step_j = nt % A;
@@ -239,45 +230,23 @@ __global__ __launch_bounds__(256) void signature12_f64_kernel(
   }
 }
 
-static int grid_for(int64_t n) {
-  // one workgroup per trajectory, capped; the kernels grid-stride
-  const int64_t cap = BSIG_F64_SUMMARY_GRID_CAP;
-  return (int)(n < cap ? n : cap);
-}
+static int grid_for(int64_t n) { return capped_grid(n, BSIG_F64_SUMMARY_GRID_CAP); }
 
-// A launch with more than 64 KB of dynamic LDS needs the function's limit raised first (the
-// attribute belongs to the function ON A DEVICE: once per device of this process and function).
+// (common.h: raise_lds_limit) only the launches that need it ask
 template <typename K>
-static int allow_lds(K kernel, size_t lds, bool* attr_set) {
-  if (lds <= 64 * 1024) return BSIG_OK;
-  int dev = 0;
-  BSIG_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-    BSIG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
-    if (dev >= 0 && dev < 64) attr_set[dev] = true;
-  }
-  return BSIG_OK;
+static int allow_lds(K kernel, size_t lds, LdsRaised* raised) {
+  return lds > kLdsUnraised ? raise_lds_limit(kernel, kLdsBytes, raised) : BSIG_OK;
 }
 
 template <int DMAX>
 static int launch_sig3(const double* states, const double* actions, double* out, int64_t n, int length,
                        int sd, int ad, int64_t ld_out, int threads, size_t lds, hipStream_t st) {
-  static bool attr_set[64] = {};
-  BSIG_TRY(allow_lds(signature3_f64_kernel<DMAX>, lds, attr_set));
+  static LdsRaised raised;
+  BSIG_TRY(allow_lds(signature3_f64_kernel<DMAX>, lds, &raised));
   hipLaunchKernelGGL((signature3_f64_kernel<DMAX>), dim3(grid_for(n)), dim3(threads), lds, st, states,
                      actions, out, n, length, sd, ad, ld_out);
   BSIG_CHECK_LAUNCH("signature_f64");
   return BSIG_OK;
-}
-
-static int ref_signature_depth(int64_t d) {  // summarizers.py:133-141
-  for (int depth = 3; depth >= 0; --depth) {
-    int64_t p = 1;
-    for (int q = 0; q < depth; ++q) p *= d;
-    if (p <= 110 * 110) return depth;
-  }
-  return 1;
 }
 
 }  // namespace f64
@@ -317,12 +286,12 @@ extern "C" int bsig_crosscorr_f64(const double* states, const double* actions, d
   const int64_t S = (int64_t)w * (sd - 1), A = (int64_t)w * ad;
   BSIG_REQUIRE(ld_out >= S * A + 2, "crosscorr_f64: ld_out too small");
   const size_t lds = (size_t)(S + A) * sizeof(double);
-  if (lds > f64::kLdsMax) {
+  if (lds > kLdsBytes) {
     set_error("crosscorr_f64: %zu B of LDS needed", lds);
     return BSIG_EUNSUPPORTED;
   }
-  static bool attr_set[64] = {};
-  BSIG_TRY(f64::allow_lds(f64::crosscorr_f64_kernel, lds, attr_set));
+  static LdsRaised raised;
+  BSIG_TRY(f64::allow_lds(f64::crosscorr_f64_kernel, lds, &raised));
   hipLaunchKernelGGL(f64::crosscorr_f64_kernel, dim3(f64::grid_for(n)), dim3(256), lds, as_stream(stream),
                      states, actions, out, n, t_states, t_actions, sd, ad, w, use_state_diff, ld_out,
                      nonfinite);
@@ -339,7 +308,7 @@ extern "C" int bsig_signature_f64(const double* states, const double* actions, d
   BSIG_REQUIRE(n >= 0 && length >= 2 && sd >= 1 && ad >= 1,
                "signature_f64: bad dims length=%d sd=%d ad=%d", length, sd, ad);
   const int d = 1 + sd + ad;
-  if (depth <= 0) depth = f64::ref_signature_depth(d);
+  if (depth <= 0) depth = ref_signature_depth(d);
   BSIG_REQUIRE(depth >= 1 && depth <= 3, "signature_f64: depth %d not in 1..3", depth);
   BSIG_REQUIRE(ld_out >= bsig_summary_dim(3, length, sd, ad, depth), "signature_f64: ld_out too small");
   const hipStream_t st = as_stream(stream);
@@ -352,8 +321,8 @@ extern "C" int bsig_signature_f64(const double* states, const double* actions, d
     }
     const size_t lds = ((size_t)((length * (int64_t)d + 1) & ~(int64_t)1) +
                         (size_t)(length - 1) * ((d + 1) & ~1) + (size_t)d * d * d) * sizeof(double);
-    if (lds > f64::kLdsMax) {
-      set_error("signature_f64: %zu B of LDS needed (%zu in a workgroup)", lds, f64::kLdsMax);
+    if (lds > kLdsBytes) {
+      set_error("signature_f64: %zu B of LDS needed (%zu in a workgroup)", lds, kLdsBytes);
       return BSIG_EUNSUPPORTED;
     }
     const int threads = (int)round_up<int64_t>((int64_t)d * d, 64);
@@ -364,12 +333,12 @@ extern "C" int bsig_signature_f64(const double* states, const double* actions, d
   size_t lds = 0;
   if (depth == 2) {
     lds = (size_t)length * d * sizeof(double);
-    if (lds > f64::kLdsMax) {
-      set_error("signature_f64: %zu B of LDS needed (%zu in a workgroup)", lds, f64::kLdsMax);
+    if (lds > kLdsBytes) {
+      set_error("signature_f64: %zu B of LDS needed (%zu in a workgroup)", lds, kLdsBytes);
       return BSIG_EUNSUPPORTED;
     }
-    static bool attr_set[64] = {};
-    BSIG_TRY(f64::allow_lds(f64::signature12_f64_kernel, lds, attr_set));
+    static LdsRaised raised;
+    BSIG_TRY(f64::allow_lds(f64::signature12_f64_kernel, lds, &raised));
   }
   hipLaunchKernelGGL(f64::signature12_f64_kernel, dim3(f64::grid_for(n)), dim3(256), lds, st, states,
                      actions, out, n, length, sd, ad, depth, ld_out);

@@ -182,7 +182,7 @@ int deferred_eval_run(const PersistShape& s, const UGeom& g, const PersistBuffer
   d.sx = reinterpret_cast<float*>(base + L.sx_off); d.sl = reinterpret_cast<float*>(base + L.sl_off);
   const size_t lds_tile = (size_t)u_snap_slot_floats(g.NT, g.WP) * sizeof(float);
   const size_t lds_rows = ((size_t)L.row_floats + 64) * sizeof(float);
-  BSIG_REQUIRE(lds_tile <= 64 * 1024 && lds_rows <= 64 * 1024, "deferred evaluations: tile or rows beyond 64 KB of LDS");
+  BSIG_REQUIRE(lds_tile <= kLdsUnraised && lds_rows <= kLdsUnraised, "deferred evaluations: tile or rows beyond 64 KB of LDS");
   for (int e0 = 0; e0 < n_evals; e0 += L.group) {
     const int ne = std::min(L.group, n_evals - e0);
     d.e0 = e0;

@@ -1390,9 +1390,9 @@ __global__ void spin_kernel(long long ticks, int* sink) {
   if (spin_lds[threadIdx.x] == 2.f) sink[0] = 1;
 }
 int debug_spin(int blocks, size_t lds_bytes, int ms, hipStream_t st) {
-  BSIG_REQUIRE(blocks >= 1 && ms >= 0 && lds_bytes <= (size_t)kULds, "debug_spin: bad args");
+  BSIG_REQUIRE(blocks >= 1 && ms >= 0 && lds_bytes <= kLdsBytes, "debug_spin: bad args");
   BSIG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(spin_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, kULds));
+                               hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
   hipLaunchKernelGGL(spin_kernel, dim3(blocks), dim3(256), std::max<size_t>(lds_bytes, 1024), st,
                      (long long)ms * 100000LL /* 100 MHz wall clock */, (int*)nullptr);
   BSIG_CHECK_LAUNCH("debug_spin");
@@ -1455,12 +1455,12 @@ static bool u_geom_try(const PersistShape& s, int NT, int KS, UGeom* g, double* 
     g->lds = ((size_t)g->KS * g->FP + (size_t)NBW * g->WP + g->xs_floats + 64 + NBW) * sizeof(float);
   };
   lds_of();
-  if (g->lds > (size_t)kULds && g->eval_passes > 0 && g->RE > g->R) {
+  if (g->lds > kLdsBytes && g->eval_passes > 0 && g->RE > g->R) {
     // (the evaluation rows may be what does not fit: retry without them)
     g->eval_passes = 0; g->NE = 1; g->RE = 1;
     lds_of();
   }
-  if (g->lds > (size_t)kULds) return false;
+  if (g->lds > kLdsBytes) return false;
   g->slab_floats = (size_t)g->k_slices * s.batch * g->NhP;
   g->dout_floats = (size_t)s.batch * g->NhP;
   g->eval_floats = (size_t)3 * g->eval_passes * g->slab_floats;
@@ -1509,8 +1509,8 @@ int persist_geometry(const PersistShape& s, int32_t* out) {
 
 // the > 64 KB dynamic-LDS limit of every instantiation this file launches
 static int u_allow_dynamic_lds() {
-  static bool done[64] = {};
-  const void* kernels[8] = {reinterpret_cast<const void*>(linear_head_updates_kernel<false, 1>),
+  static LdsRaised raised[8];
+  const void* const kernels[8] = {reinterpret_cast<const void*>(linear_head_updates_kernel<false, 1>),
                             reinterpret_cast<const void*>(linear_head_updates_kernel<false, 1, false, true>),
                             reinterpret_cast<const void*>(linear_head_updates_kernel<false, 2, false, true>),
                             reinterpret_cast<const void*>(linear_head_updates_kernel<false, 2>),
@@ -1518,7 +1518,7 @@ static int u_allow_dynamic_lds() {
                             reinterpret_cast<const void*>(linear_head_updates_kernel<false, 1, true>),
                             reinterpret_cast<const void*>(linear_head_updates_kernel<true, 2>),
                             reinterpret_cast<const void*>(linear_head_updates_kernel<false, 2, true>)};
-  return allow_dynamic_lds(done, kernels, 8, kULds);
+  return allow_dynamic_lds(raised, kernels, kLdsBytes);
 }
 
 template <int NT>

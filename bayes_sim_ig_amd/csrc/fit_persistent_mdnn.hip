@@ -105,7 +105,7 @@ static bool mdnn_geom(const PersistMdnnShape& s, MdnnGeom* g) {
                       g->Nh16 + (size_t)g->mr * (s.out_dim + 3 * s.n_comp + (full ? 3 * s.out_dim * s.n_comp : 0)) +
                       64 + (g->stream ? 0 : (kSumSub - 1) * kSumItems * 4)) * sizeof(float);
   size_t small_lds = ((size_t)g->FR * kMHP + (size_t)kMNB * (g->FR + 4) + 64) * sizeof(float);
-  g->wide = owner_lds > (size_t)kMLdsLimit ? 1 : 0;
+  g->wide = owner_lds > kLdsBytes ? 1 : 0;
   const char* force_wide = getenv("BSIG_MDNN_WIDE_HEADS");     // tests: the wide path on small heads
   if (force_wide && force_wide[0] == '1') g->wide = 1;
   if (g->wide) {
@@ -117,7 +117,7 @@ static bool mdnn_geom(const PersistMdnnShape& s, MdnnGeom* g) {
   g->lds = std::max(std::max(tile_lds, (size_t)128 * kMPitch * sizeof(float)),
                     std::max(owner_lds, small_lds));
   if (g->stream) g->lds = std::max(owner_lds, small_lds);   // + the tile workgroups' (S, A known at bind)
-  if (g->lds > (size_t)kMLdsLimit) return false;
+  if (g->lds > kLdsBytes) return false;
   g->slab_floats = g->stream ? (size_t)g->G1 * s.batch * kMNB : (size_t)g->k_slices * s.batch * kMH;
   g->act_floats = (size_t)s.batch * kMH;
   g->dout_floats = (size_t)s.batch * g->NhP;
@@ -147,8 +147,8 @@ static bool mdnn_device_can_host(const MdnnGeom& g) {
   if (prop.multiProcessorCount < g.G1 + g.n_owner + g.n_small || (size_t)prop.maxSharedMemoryPerMultiProcessor < g.lds)
     return false;
   // the runtime's own occupancy answer (registers, LDS, wave slots) must admit a workgroup per CU
-  static bool lds_set[64] = {};
-  const void* kernels[16] = {
+  static LdsRaised lds_set[16];
+  const void* const kernels[16] = {
 #define BSIG_K(a, b, c, d) reinterpret_cast<const void*>(mdnn_updates_kernel<a, b, c, d>)
       BSIG_K(false, false, false, false), BSIG_K(true, false, false, false), BSIG_K(false, true, false, false),
       BSIG_K(true, true, false, false),   BSIG_K(false, false, true, false), BSIG_K(true, false, true, false),
@@ -158,9 +158,9 @@ static bool mdnn_device_can_host(const MdnnGeom& g) {
       BSIG_K(true, true, true, true)};
 #undef BSIG_K
   int per_cu = 0;
-  if (allow_dynamic_lds(lds_set, kernels, 16, kMLdsLimit) != BSIG_OK ||
+  if (allow_dynamic_lds(lds_set, kernels, kLdsBytes) != BSIG_OK ||
       hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mdnn_updates_kernel<false, false, false, false>, kMT,
-                                                   std::min(g.lds, (size_t)kMLdsLimit)) != hipSuccess)
+                                                   std::min(g.lds, kLdsBytes)) != hipSuccess)
     return false;
   return per_cu >= 1;
 }

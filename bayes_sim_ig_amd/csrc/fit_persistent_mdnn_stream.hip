@@ -767,7 +767,7 @@ bool mdnn_stream_tile_geom(int FR, int chunks_per_wg, int S, int A, int* nip, in
   // (the chunk region also stages dz1 [FR][36], the k-half exchange [128][33] and the partial
   // sums [32][16][4]; the factor columns the [B][36] block of partial products; a factor row is
   // loaded as at most three 64-column groups)
-  return *lds_bytes <= (size_t)kMLdsLimit && FR <= 104 && *nip + A + 8 <= 192 &&
+  return *lds_bytes <= kLdsBytes && FR <= 104 && *nip + A + 8 <= 192 &&
          (size_t)kMNB * kSPitch >= (size_t)128 * kMPbuf && (size_t)kMNB * kSPitch >= (size_t)FR * kSBP &&
          (size_t)(*nip + A + 8) * kSTP >= (size_t)FR * kSBP;
 }
@@ -779,13 +779,13 @@ int mdnn_stream_chunks(int input_dim) { return ceil_div(input_dim, kSC); }
 // instantiation that is launched, at the LDS size it is launched with (it depends on the factor
 // dimensions), must admit a workgroup per CU.  Asked while a binding resolves the streamed tiles.
 int mdnn_stream_can_host(bool dp, bool wide, bool full, int grid, size_t lds) {
-  static bool lds_set[64] = {};
-  const void* kernels[8] = {
+  static LdsRaised lds_set[8];
+  const void* const kernels[8] = {
 #define BSIG_K(a, b, c) reinterpret_cast<const void*>(mdnn_stream_updates_kernel<a, b, c>)
       BSIG_K(false, false, false), BSIG_K(true, false, false), BSIG_K(false, true, false), BSIG_K(true, true, false),
       BSIG_K(false, false, true),  BSIG_K(true, false, true),  BSIG_K(false, true, true),  BSIG_K(true, true, true)};
 #undef BSIG_K
-  BSIG_TRY(allow_dynamic_lds(lds_set, kernels, 8, kMLdsLimit));
+  BSIG_TRY(allow_dynamic_lds(lds_set, kernels, kLdsBytes));
   int dev = 0, per_cu = 0;
   const int variant = (dp ? 1 : 0) | (wide ? 2 : 0) | (full ? 4 : 0);
   const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernels[variant], kMT, lds);

@@ -186,7 +186,7 @@ int run(const char* what, Level1 level1, int64_t max_grid, const T* states, cons
   BSIG_REQUIRE(!channels || n_channels >= 1, "%s: channels given with n_channels=%d", what, n_channels);
   const int64_t d = 1 + (channels ? (int64_t)n_channels : (int64_t)sd + ad);
   BSIG_REQUIRE(d <= INT32_MAX, "%s: path dim %lld too large", what, (long long)d);
-  if (depth <= 0) depth = sigex::ref_depth(d);
+  if (depth <= 0) depth = ref_signature_depth(d);
   if (depth <= 1)      // the log-signature is level 1: the signature's depth-1 branch, unchanged
     return level1(states, actions, channels, n_channels, out, n, length, sd, ad, depth, ld_out, stream);
   BSIG_REQUIRE(words, "%s: null words at depth %d", what, depth);
@@ -197,9 +197,9 @@ int run(const char* what, Level1 level1, int64_t max_grid, const T* states, cons
   size_t lds = 0;
   int threads = 0;
   BSIG_TRY(sigex::plan(what, d, length, depth, (int)sizeof(T), &g, &lds, &threads));
-  static bool attr_set[64] = {};
-  BSIG_TRY(sigex::allow_lds_of(reinterpret_cast<const void*>(logsignature_kernel<T>), attr_set, lds));
-  hipLaunchKernelGGL((logsignature_kernel<T>), dim3((unsigned)std::min<int64_t>(n, max_grid)),
+  static LdsRaised raised;
+  if (lds > kLdsUnraised) BSIG_TRY(raise_lds_limit(logsignature_kernel<T>, kLdsBytes, &raised));
+  hipLaunchKernelGGL((logsignature_kernel<T>), dim3(capped_grid(n, max_grid)),
                      dim3(threads), lds, as_stream(stream), states, actions, channels, words, (int)width,
                      out, n, length, sd, ad, ld_out, g);
   BSIG_CHECK_LAUNCH(what);

@@ -26,7 +26,7 @@ extern "C" int bsig_logsignature(const float* states, const float* actions, cons
                                  int n_channels, const int32_t* words, float* out, int64_t n, int length,
                                  int sd, int ad, int depth, int64_t ld_out, bsig_stream_t stream) {
   bsig::Range roctx_range("bsig_logsignature");
-  return logsig::run<float>("logsignature", bsig_signature_ex, n > 0 ? summary_grid_for(n) : 1, states,
+  return logsig::run<float>("logsignature", bsig_signature_ex, kSummaryGridCap, states,
                             actions, channels, n_channels, words, out, n, length, sd, ad, depth, ld_out,
                             stream);
 }

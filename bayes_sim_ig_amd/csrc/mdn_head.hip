@@ -518,7 +518,7 @@ static int head_geom(const bsig_head_dims* d, int64_t batch, HeadGeom* g) {
       }
     }
   }
-  if (g->lds > 64 * 1024) {
+  if (g->lds > kLdsUnraised) {
     set_error("mdn head: %zu B of LDS needed for one workgroup", g->lds);
     return BSIG_EUNSUPPORTED;
   }

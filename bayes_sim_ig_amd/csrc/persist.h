@@ -120,15 +120,11 @@ int persist_run(const PersistShape& s, const UGeom& g, const PersistBuffers& b, 
 // (diagnostics) the tiling fit_persistent.hip plans for a shape, bsig.h: bsig_debug_persist_geometry
 int persist_geometry(const PersistShape& s, int32_t* out);
 
-// The > 64 KB dynamic-LDS limit of a launcher's kernels is a per-device attribute: raised on the
-// current device (a plan's, while its engine is resolved) once per device and launcher (`done`).
-inline int allow_dynamic_lds(bool (&done)[64], const void* const* kernels, int n, int bytes) {
-  int dev = 0;
-  BSIG_HIP(hipGetDevice(&dev));
-  if (done[dev & 63]) return BSIG_OK;
-  for (int i = 0; i < n; ++i)
-    BSIG_HIP(hipFuncSetAttribute(kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  done[dev & 63] = true;
+// The > 64 KB dynamic-LDS limit of every kernel of a launcher, raised on the current device (a plan's,
+// while its engine is resolved): common.h's raise_lds_limit per kernel, `raised[i]` being kernels[i]'s.
+template <int N>
+inline int allow_dynamic_lds(LdsRaised (&raised)[N], const void* const (&kernels)[N], int bytes) {
+  for (int i = 0; i < N; ++i) BSIG_TRY(raise_lds_limit(kernels[i], bytes, &raised[i]));
   return BSIG_OK;
 }
 

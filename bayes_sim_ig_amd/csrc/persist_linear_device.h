@@ -17,7 +17,6 @@ constexpr int kUGroup = 6;           // k-slices are 1, 2 or 3 groups of 6 steps
                                      // unrolled step loops branch once per group, not once per step
 constexpr int kUMT = 7;              // 16-row m-tiles of the minibatch (<= 112 rows): fixed, so that the
                                      // dW product's loop over the minibatch has no run-time bound
-constexpr int kULds = 160 * 1024;
 constexpr int kUProf = 8;            // profiled updates per launch
 // Pitch of the F^T / d_out^T rows in LDS (floats): minibatches of up to 112 rows.  = 4 (mod 8):
 // conflict-free 16-byte reads down 8 rows and 4-byte writes across rows.  A compile-time constant:

@@ -24,7 +24,6 @@ constexpr int kMHP = kMH + 4;       // LDS pitch of a 128-wide activation row
 constexpr int kMR = 4;              // minibatch rows per owner workgroup (power of two <= 8; 2 where the chip has the CUs)
 constexpr int kStreamMR = 8;        // ... of a plan with a streamed first layer
 constexpr int kMPbuf = 33;
-constexpr int kMLdsLimit = 160 * 1024;
 constexpr int kFastRowsMaxInput = 4096;   // (mdnn_owner_workgroup: fast rows)
 
 struct MdnnArgs {

@@ -28,27 +28,14 @@
 #include "../../include/bsig_signature.h"
 
 namespace bsig {
-
-int summary_grid_for(int64_t n);      // csrc/summarizers.hip: the fp32 summarizers' workgroup count
-
 namespace sigex {
 
-constexpr size_t kLdsMax = 160 * 1024;      // one workgroup's LDS on gfx950
 constexpr int kMaxThreads = 1024;
 
 struct Layout {          // byte offsets into the dynamic LDS, each a multiple of 16
   int d = 0, depth = 0, low = 0, top = 0, rows = 0;
   int off_b = 0, off_top = 0, off_delta = 0, off_rcp = 0, off_rows = 0, off_src = 0;
 };
-
-inline int ref_depth(int64_t d) {  // summarizers.py:133-141
-  for (int depth = 3; depth >= 0; --depth) {
-    int64_t p = 1;
-    for (int q = 0; q < depth; ++q) p *= d;
-    if (p <= 110 * 110) return depth;
-  }
-  return 1;
-}
 
 inline int64_t row_width(int64_t d, int depth) {
   if (d < 2 || d > INT32_MAX || depth < 1 || depth > BSIG_SIGNATURE_MAX_DEPTH) return -1;
@@ -74,9 +61,9 @@ inline int plan(const char* what, int64_t d, int length, int depth, int itemsize
   int64_t top = 1;
   if (width > 0) for (int q = 0; q < depth; ++q) top *= d;
   // (a prefix digit is stored in 8 bits; d^2 elements alone exceed the LDS long before d = 256)
-  if (width < 0 || d > 255 || width * itemsize > (int64_t)kLdsMax) {
+  if (width < 0 || d > 255 || width * itemsize > (int64_t)kLdsBytes) {
     set_error("%s: depth %d on path dim %lld needs more than a workgroup's %zu B of LDS for its levels",
-              what, depth, (long long)d, kLdsMax);
+              what, depth, (long long)d, kLdsBytes);
     return BSIG_EUNSUPPORTED;
   }
   const int64_t low = width - top, rows = low + 1;
@@ -88,9 +75,9 @@ inline int plan(const char* what, int64_t d, int length, int depth, int itemsize
   const int64_t off_rows = off_rcp + r16(8 * itemsize);
   const int64_t off_src = off_rows + r16(rows * 8);
   const int64_t bytes = off_src + r16(d * 4);
-  if (bytes > (int64_t)kLdsMax) {
+  if (bytes > (int64_t)kLdsBytes) {
     set_error("%s: %lld B of LDS needed for depth %d on path dim %lld, length %d (%zu in a workgroup)",
-              what, (long long)bytes, depth, (long long)d, length, kLdsMax);
+              what, (long long)bytes, depth, (long long)d, length, kLdsBytes);
     return BSIG_EUNSUPPORTED;
   }
   g->d = (int)d; g->depth = depth; g->low = (int)low; g->top = (int)top; g->rows = (int)rows;
@@ -231,26 +218,6 @@ __global__ __launch_bounds__(kMaxThreads) void signature_ex_kernel(
                  StoreLevels<T>());
 }
 
-// A launch with more than 64 KB of dynamic LDS needs the function's limit raised first (once per
-// device of this process and function).
-// (`kernel` and its `attr_set[64]`, one flag per device, belong together.)
-inline int allow_lds_of(const void* kernel, bool* attr_set, size_t lds) {
-  if (lds <= 64 * 1024) return BSIG_OK;
-  int dev = 0;
-  BSIG_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-    BSIG_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
-    if (dev >= 0 && dev < 64) attr_set[dev] = true;
-  }
-  return BSIG_OK;
-}
-
-template <typename T>
-int allow_lds(size_t lds) {
-  static bool attr_set[64] = {};
-  return allow_lds_of(reinterpret_cast<const void*>(signature_ex_kernel<T>), attr_set, lds);
-}
-
 // The entry point of either precision: the argument checks, the routing of include/bsig_signature.h,
 // the launch.  `legacy` is bsig_signature / bsig_signature_f64; `max_grid` the precision's workgroup cap.
 template <typename T, typename Legacy>
@@ -267,7 +234,7 @@ int run(const char* what, Legacy legacy, int64_t max_grid, const T* states, cons
   BSIG_REQUIRE(!channels || n_channels >= 1, "%s: channels given with n_channels=%d", what, n_channels);
   const int64_t d = 1 + (channels ? (int64_t)n_channels : (int64_t)sd + ad);
   BSIG_REQUIRE(d <= INT32_MAX, "%s: path dim %lld too large", what, (long long)d);
-  if (depth <= 0) depth = ref_depth(d);
+  if (depth <= 0) depth = ref_signature_depth(d);
   if (!channels && depth <= 3)
     return legacy(states, actions, out, n, length, sd, ad, depth, ld_out, stream);
   const int64_t width = row_width(d, depth);
@@ -277,8 +244,9 @@ int run(const char* what, Legacy legacy, int64_t max_grid, const T* states, cons
   size_t lds = 0;
   int threads = 0;
   BSIG_TRY(plan(what, d, length, depth, (int)sizeof(T), &g, &lds, &threads));
-  BSIG_TRY(allow_lds<T>(lds));
-  hipLaunchKernelGGL((signature_ex_kernel<T>), dim3((unsigned)std::min<int64_t>(n, max_grid)),
+  static LdsRaised raised;
+  if (lds > kLdsUnraised) BSIG_TRY(raise_lds_limit(signature_ex_kernel<T>, kLdsBytes, &raised));
+  hipLaunchKernelGGL((signature_ex_kernel<T>), dim3(capped_grid(n, max_grid)),
                      dim3(threads), lds, as_stream(stream), states, actions, channels, out, n, length,
                      sd, ad, ld_out, g);
   BSIG_CHECK_LAUNCH(what);

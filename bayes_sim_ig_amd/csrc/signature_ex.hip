@@ -16,7 +16,7 @@ extern "C" int bsig_signature_ex_fits(int path_dim, int length, int depth, int i
   BSIG_REQUIRE(itemsize == 4 || itemsize == 8, "signature_ex_fits: itemsize %d is not 4 or 8", itemsize);
   BSIG_REQUIRE(depth <= BSIG_SIGNATURE_MAX_DEPTH, "signature_ex_fits: depth %d above %d", depth,
                BSIG_SIGNATURE_MAX_DEPTH);
-  if (depth <= 0) depth = sigex::ref_depth(path_dim);
+  if (depth <= 0) depth = ref_signature_depth(path_dim);
   sigex::Layout g;
   size_t lds = 0;
   int threads = 0;
@@ -29,6 +29,6 @@ extern "C" int bsig_signature_ex(const float* states, const float* actions, cons
                                  int n_channels, float* out, int64_t n, int length, int sd, int ad,
                                  int depth, int64_t ld_out, bsig_stream_t stream) {
   bsig::Range roctx_range("bsig_signature_ex");
-  return sigex::run<float>("signature_ex", bsig_signature, n > 0 ? summary_grid_for(n) : 1, states,
+  return sigex::run<float>("signature_ex", bsig_signature, kSummaryGridCap, states,
                            actions, channels, n_channels, out, n, length, sd, ad, depth, ld_out, stream);
 }

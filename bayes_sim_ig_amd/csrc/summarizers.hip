@@ -47,11 +47,6 @@ __global__ __launch_bounds__(256) void summary_start_kernel(
 // passes), taken by one wavefront from LDS.  Accumulated in fp64 and rounded once: the value every
 // fp32 summation order approximates (the reference's own order is a property of the torch build),
 // at 5 elements per lane.  Every lane returns the same value.
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 __device__ __forceinline__ void row_mean_std(const float* sf, int S, int ln, float& mean, float& sdev) {
   double part = 0.0;
   for (int i = ln; i < S; i += 64) part += (double)sf[i];
@@ -564,22 +559,9 @@ __global__ __launch_bounds__(256) void signature12_kernel(
   }
 }
 
-static int grid_for(int64_t n) {
-  // one workgroup per trajectory, capped; the kernels grid-stride
-  const int64_t cap = 256 * 64;
-  return (int)(n < cap ? n : cap);
-}
-
-int summary_grid_for(int64_t n) { return grid_for(n); }   // (csrc/signature_ex.hip launches as many)
-
-static int ref_signature_depth(int64_t d) {  // summarizers.py:133-141
-  for (int depth = 3; depth >= 0; --depth) {
-    int64_t p = 1;
-    for (int q = 0; q < depth; ++q) p *= d;
-    if (p <= 110 * 110) return depth;
-  }
-  return 1;
-}
+// The most dynamic LDS these launchers ask for.  They launch with it as it is, without raising the
+// kernels' limit (common.h: raise_lds_limit).
+constexpr size_t kSummaryLdsCap = 150 * 1024;
 
 }  // namespace bsig
 
@@ -630,7 +612,7 @@ static int start_path(int64_t n, int t_states, int t_actions, int sd, int ad, in
   p->kernel = kKStart;
   p->store = kStElem;
   p->threads = width >= 192 ? 256 : (width >= 96 ? 128 : 64);
-  p->grid = grid_for(n);
+  p->grid = capped_grid(n, kSummaryGridCap);
   p->steps = max_t;
   return BSIG_OK;
 }
@@ -647,7 +629,7 @@ static int crosscorr_path(int64_t n, int t_states, int t_actions, int sd, int ad
   BSIG_REQUIRE(!has_fac || ld_fac >= S + A + 3, "crosscorr: ld_factors too small (need S + A + 3 = %lld)",
                (long long)(S + A + 3));
   const size_t lds = (size_t)(S + A + 8) * sizeof(float);
-  if (lds > 150 * 1024) {
+  if (lds > kSummaryLdsCap) {
     set_error("crosscorr: %zu B of LDS needed", lds);
     return BSIG_EUNSUPPORTED;
   }
@@ -661,7 +643,7 @@ static int crosscorr_path(int64_t n, int t_states, int t_actions, int sd, int ad
     return BSIG_OK;
   }
   p->lds = lds;
-  p->grid = grid_for(n);
+  p->grid = capped_grid(n, kSummaryGridCap);
   p->vec4 = has_out && (ld_out % 4 == 0) && out_align16;
   const int qpr = (int)(A >> 2);
   // the materialised summary alone, quads of action features: the lean streaming kernel
@@ -704,7 +686,7 @@ static int signature_path(int64_t n, int length, int sd, int ad, int depth, int6
                "signature: ld_out too small");
   p->depth = depth;
   p->steps = length;
-  p->grid = grid_for(n);
+  p->grid = capped_grid(n, kSummaryGridCap);
   if (depth == 3) {
     if (d > 32) {
       set_error("signature: depth 3 needs path dim <= 32 (got %d)", d);
@@ -712,7 +694,7 @@ static int signature_path(int64_t n, int length, int sd, int ad, int depth, int6
     }
     const size_t lds = ((size_t)((length * d + 3) & ~3) + (size_t)(length - 1) * ((d + 3) & ~3) +
                         (size_t)d * d * d + 4) * sizeof(float);
-    if (lds > 150 * 1024) {
+    if (lds > kSummaryLdsCap) {
       set_error("signature: %zu B of LDS needed", lds);
       return BSIG_EUNSUPPORTED;
     }
@@ -727,7 +709,7 @@ static int signature_path(int64_t n, int length, int sd, int ad, int depth, int6
   size_t lds = 0;
   if (depth == 2) {
     lds = (size_t)length * d * sizeof(float);
-    if (lds > 150 * 1024) {
+    if (lds > kSummaryLdsCap) {
       set_error("signature: %zu B of LDS needed", lds);
       return BSIG_EUNSUPPORTED;
     }

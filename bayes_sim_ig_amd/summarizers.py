@@ -194,6 +194,22 @@ class CrossCorrFactors:
         return self.materialize().to(*args, **kwargs)
 
 
+def _finite_flag(check_finite, device):
+    """The flag word a cross-correlation kernel raises on a non-finite feature, and whether this call reads it
+    back.  ``check_finite`` may be a 1-element int32 device tensor: the kernel raises its flag there and the
+    caller asserts later (BayesSim.fit: one read-back for all chunks); None / False: no flag."""
+    if torch.is_tensor(check_finite):
+        return check_finite, False
+    if not check_finite:
+        return None, False
+    return torch.zeros(1, dtype=torch.int32, device=device), True
+
+
+def _assert_finite(flag, read_back):
+    if read_back:
+        assert int(flag.item()) == 0  # summarizers.py:120
+
+
 def cross_correlation(states, actions, use_state_diff=False, out=None,
                       check_finite=True, lazy=False, dtype=None):
     """Reference summarizers.py:90-122.  ``lazy=True`` returns a CrossCorrFactors handle
@@ -212,16 +228,11 @@ def cross_correlation(states, actions, use_state_diff=False, out=None,
     width = summary_dim('summary_corrdiff' if use_state_diff else 'summary_corr',
                         t, sd, ad)
     buf, ld = _alloc(n, width, s.device, out, prec)
-    # check_finite may be a 1-element int32 device tensor: the kernel raises its flag there
-    # and the caller asserts later (BayesSim.fit: one read-back for all chunks)
-    deferred = torch.is_tensor(check_finite)
-    flag = check_finite if deferred else (
-        torch.zeros(1, dtype=torch.int32, device=s.device) if check_finite else None)
+    flag, read_back = _finite_flag(check_finite, s.device)
     prec.crosscorr(
         _lib.ptr(s), _lib.ptr(a), _lib.ptr(buf), n, t, a.shape[1], sd, ad,
         1 if use_state_diff else 0, ld, _lib.ptr(flag), _lib.stream())
-    if check_finite is not None and check_finite is not False and not deferred:
-        assert int(flag.item()) == 0  # summarizers.py:120
+    _assert_finite(flag, read_back)
     return _finish(buf, n, width, home, out)
 
 
@@ -235,15 +246,12 @@ def _cross_correlation_factors(states, actions, use_state_diff, check_finite):
     _lib.check(lib.bsig_crosscorr_factor_dims(t, sd, ad, C.byref(s_dim), C.byref(a_dim)))
     ld = _lib.round_up(s_dim.value + a_dim.value + 3, 4)
     fac = torch.empty((n, ld), dtype=torch.float32, device=s.device)
-    deferred = torch.is_tensor(check_finite)
-    flag = check_finite if deferred else (
-        torch.zeros(1, dtype=torch.int32, device=s.device) if check_finite else None)
+    flag, read_back = _finite_flag(check_finite, s.device)
     with _lib.on_device(s.device):
         _lib.check(lib.bsig_crosscorr_factors(
             _lib.ptr(s), _lib.ptr(a), _lib.ptr(fac), n, t, a.shape[1], sd, ad,
             1 if use_state_diff else 0, ld, _lib.ptr(flag), _lib.stream(s.device)))
-    if check_finite is not None and check_finite is not False and not deferred:
-        assert int(flag.item()) == 0  # summarizers.py:120
+    _assert_finite(flag, read_back)
     return CrossCorrFactors(fac, s_dim.value, a_dim.value)
 
 
@@ -305,19 +313,10 @@ def _channel_vector(picked, device):
     return vec
 
 
-def summary_signatory(states, actions, depth=None, out=None, dtype=None, channels=None):
-    """Reference summarizers.py:144-168 with the signature computed by
-    csrc/summarizers.hip instead of ``signatory``.  All N rows are returned
-    (the reference drops N % 10 rows when N > 10000).
-
-    ``depth`` up to 6 and ``channels`` (include/bsig_signature.h): ``channels`` is a sequence of ints
-    that picks the path's columns after the time channel -- ``c < sd`` is ``states[..., c]``, any other
-    ``actions[..., c - sd]``; any order, repeats allowed -- so the path is ``[t | picked channels]`` and
-    the default depth is ``signature_depth(1 + len(channels))``.  The channels are gathered by the
-    kernel's loader: no sliced copy of the trajectories is made.  ``channels=None`` at depth <= 3 is the
-    call it always was (signature3_kernel / signature12_kernel); anything else, the identity list
-    included, runs the general kernel of csrc/signature_ex.h.  ValueError (before any GPU call) for a
-    bad channel list or a depth above 6; NotImplementedError when the levels do not fit a workgroup's LDS."""
+def _signature_args(states, actions, depth, dtype, channels):
+    """What summary_signatory and summary_logsignature do with their arguments: the host checks (asserts, then
+    ValueErrors, all before any GPU call), the trajectories on the device, the path and its default depth.
+    Returns (prec, s, a, home, n, length, sd, ad, picked, path_dim, depth)."""
     prec = _precision(dtype)
     assert len(states.shape) == 3, 'states should be batch x time x state_dim'
     assert len(actions.shape) == 3, 'Need actions: ntraj x n_steps x state_dim'
@@ -331,6 +330,24 @@ def summary_signatory(states, actions, depth=None, out=None, dtype=None, channel
     path_dim = 1 + (sd + ad if picked is None else len(picked))
     if depth is None:
         depth = signature_depth(path_dim)
+    return prec, s, a, home, n, length, sd, ad, picked, path_dim, depth
+
+
+def summary_signatory(states, actions, depth=None, out=None, dtype=None, channels=None):
+    """Reference summarizers.py:144-168 with the signature computed by
+    csrc/summarizers.hip instead of ``signatory``.  All N rows are returned
+    (the reference drops N % 10 rows when N > 10000).
+
+    ``depth`` up to 6 and ``channels`` (include/bsig_signature.h): ``channels`` is a sequence of ints
+    that picks the path's columns after the time channel -- ``c < sd`` is ``states[..., c]``, any other
+    ``actions[..., c - sd]``; any order, repeats allowed -- so the path is ``[t | picked channels]`` and
+    the default depth is ``signature_depth(1 + len(channels))``.  The channels are gathered by the
+    kernel's loader: no sliced copy of the trajectories is made.  ``channels=None`` at depth <= 3 is the
+    call it always was (signature3_kernel / signature12_kernel); anything else, the identity list
+    included, runs the general kernel of csrc/signature_ex.h.  ValueError (before any GPU call) for a
+    bad channel list or a depth above 6; NotImplementedError when the levels do not fit a workgroup's LDS."""
+    prec, s, a, home, n, length, sd, ad, picked, path_dim, depth = _signature_args(
+        states, actions, depth, dtype, channels)
     if picked is None and depth <= 3:
         width = summary_dim('summary_signatory', length, sd, ad, depth)
         buf, ld = _alloc(n, width, s.device, out, prec)
@@ -411,19 +428,8 @@ def summary_logsignature(states, actions, depth=None, out=None, dtype=None, chan
     are those of ``summary_signatory``.  Depth 1 is the signature's level 1; every other call, whatever
     ``channels``, runs the log-signature kernel.  In fp32 the log cancels: see the README for the error
     relative to the value at depth 6; ``dtype=torch.float64`` is the remedy."""
-    prec = _precision(dtype)
-    assert len(states.shape) == 3, 'states should be batch x time x state_dim'
-    assert len(actions.shape) == 3, 'Need actions: ntraj x n_steps x state_dim'
-    picked = None if channels is None else signature_channels(channels, states.shape[2], actions.shape[2])
-    if depth is not None and depth > _lib.SIGNATURE_MAX_DEPTH:
-        raise ValueError('depth %r is above %d' % (depth, _lib.SIGNATURE_MAX_DEPTH))
-    s, a, home = _prep(states, actions, prec)
-    n, length, sd = s.shape
-    ad = a.shape[2]
-    assert a.shape[1] == length
-    path_dim = 1 + (sd + ad if picked is None else len(picked))
-    if depth is None:
-        depth = signature_depth(path_dim)
+    prec, s, a, home, n, length, sd, ad, picked, path_dim, depth = _signature_args(
+        states, actions, depth, dtype, channels)
     width = logsignature_dim(path_dim, depth)
     buf, ld = _alloc(n, width, s.device, out, prec)
     vec = None if picked is None else _channel_vector(picked, s.device)

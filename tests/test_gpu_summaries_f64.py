@@ -73,8 +73,9 @@ def test_start_and_waypts_are_bitwise_the_oracle(B, shape, max_t):
 
 
 # ------------------------------------------------------------------ 2. cross-correlation
-# (N, T, Ta, sd, ad): shorter than the window | waypoint selection | sd > 50: five waypoints | the fewest features
-CC_SHAPES = [(2, 3, 3, 2, 1), (4, 20, 20, 3, 3), (2, 12, 12, 52, 1), (1, 2, 2, 2, 1)]
+# (N, T, Ta, sd, ad): shorter than the window | waypoint selection | sd > 50: five waypoints | the fewest features |
+# S + A = 8400 doubles, 67 200 B of LDS: the smallest launch that has to raise the kernel's dynamic-LDS limit
+CC_SHAPES = [(2, 3, 3, 2, 1), (4, 20, 20, 3, 3), (2, 12, 12, 52, 1), (1, 2, 2, 2, 1), (2, 4, 4, 2100, 1)]
 
 
 @pytest.mark.parametrize('use_diff', [False, True])
@@ -139,11 +140,14 @@ def _grid_cap():
     return int(re.search(r'#define\s+BSIG_F64_SUMMARY_GRID_CAP\s+(\d+)', header).group(1))
 
 
-# (N, L, sd, ad, depth): one segment | odd d | the cartpole_more row, width 258 | d = 22, the widest depth 3 |
-# d = 23: depth 2 | d = 111: depth 1 | depth 2 forced | more trajectories than workgroups (N filled in below)
+# (N, L, sd, ad, depth): one segment | odd d | the cartpole_more row, width 258 | d = 22, the widest depth 3
+# (86 064 B of LDS: above the 64 KB a launch gets without the kernel's limit raised) | d = 23: depth 2 |
+# d = 111: depth 1 | depth 2 forced | more trajectories than workgroups (N filled in below) | depth 2 forced on
+# L * d = 90 * 101 doubles, 72 720 B of LDS: the depth-1/2 kernel's limit raised
 SIG_CASES = [(3, 2, 1, 1, None), (3, 5, 2, 1, None), (2, 20, 4, 1, None), (2, 3, 18, 3, None),
-             (2, 4, 19, 3, None), (2, 3, 100, 10, None), (2, 5, 2, 1, 2), ('cap+37', 2, 1, 1, None)]
-SIG_DEPTHS = [3, 3, 3, 3, 2, 1, 2, 3]
+             (2, 4, 19, 3, None), (2, 3, 100, 10, None), (2, 5, 2, 1, 2), ('cap+37', 2, 1, 1, None),
+             (2, 90, 90, 10, 2)]
+SIG_DEPTHS = [3, 3, 3, 3, 2, 1, 2, 3, 2]
 
 
 def _signature_refs(paths, depth):

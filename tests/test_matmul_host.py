@@ -41,19 +41,15 @@ def fake(monkeypatch):
 
 
 def test_library_exports_every_matmul_symbol():
+    """(header == binding, every name resolves, no overlap with another header: tests/test_headers_host.py)"""
     header = open(os.path.join(ROOT, 'include', 'bsig_matmul.h')).read()
-    declared = set(re.findall(r'\b(bsig_[a-z0-9_]+)\s*\(', header))
-    assert declared == {'bsig_gemm_f32_ex', 'bsig_rff_project_ex', 'bsig_debug_gemm_path'}
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in sorted(declared):
-        assert hasattr(lib, name), name
-    assert declared == set(_lib.exported_symbols_matmul())
-    assert not declared & set(_lib.exported_symbols())
-    assert not declared & set(_lib.exported_symbols_f64())
+    assert set(_lib.exported_symbols('bsig_matmul.h')) == {'bsig_gemm_f32_ex', 'bsig_rff_project_ex',
+                                                           'bsig_debug_gemm_path'}
     # the _ex prototypes: the plain ones plus one int
+    matmul = _lib.HEADERS['bsig_matmul.h']
     for name in ('bsig_gemm_f32', 'bsig_rff_project'):
-        assert _lib._PROTOS_MATMUL[name + '_ex'][1] == _lib._PROTOS[name][1] + [ctypes.c_int]
-        assert list(getattr(_lib.load(), name + '_ex').argtypes) == _lib._PROTOS_MATMUL[name + '_ex'][1]
+        assert matmul[name + '_ex'][1] == _lib.HEADERS['bsig.h'][name][1] + [ctypes.c_int]
+        assert list(getattr(_lib.load(), name + '_ex').argtypes) == matmul[name + '_ex'][1]
     consts = dict(re.findall(r'#define (BSIG_[A-Z0-9_]+) (\d+)', header))
     assert consts == {'BSIG_MATMUL_FP32': '0', 'BSIG_MATMUL_SPLIT_BF16': '1', 'BSIG_PLAN_SPLIT_BF16': '2',
                       'BSIG_GEMM_PATH_SPLIT_BF16': '10'}

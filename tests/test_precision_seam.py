@@ -76,8 +76,10 @@ def test_both_precisions_resolve_to_the_library_and_differ_by_the_hyper_alone(op
     lib = _lib.load()
     n32, n64 = _lib.F32.symbol(op), _lib.F64.symbol(op)
     assert n64 == n32 + '_f64' and n32 == 'bsig_' + n32[5:]
-    res32, args32 = _lib._PROTOS[n32]
-    res64, args64 = _lib._PROTOS_F64[n64]
+    res32, args32 = _lib.PROTOS[n32]
+    res64, args64 = _lib.PROTOS[n64]
+    assert n32 not in _lib._PROTOS_F64 and n64 not in _lib._PROTOS       # (and each in its own header, where
+    assert (n32 in _lib._PROTOS) == (n64 in _lib._PROTOS_F64)            # the base headers declare the pair)
     widened = [_lib.f64 if a is _lib.f32 else a for a in args32]      # (a float scalar is a double there)
     want = widened[:1] + [HYPER] + widened[1:] if op in P.HYPER_OPS else widened
     assert res64 is res32 and args64 == want
@@ -102,7 +104,7 @@ def test_plan_lifecycle_symbols():
 
 @pytest.mark.parametrize('op', sorted(P.OPS))
 def test_every_operation_reaches_its_symbol_with_or_without_the_hyper(fake, op):
-    n_args = len(_lib._PROTOS_F64[_lib.F64.symbol(op)][1])      # the uniform signature is the fp64 one
+    n_args = len(_lib.PROTOS[_lib.F64.symbol(op)][1])      # the uniform signature is the fp64 one
     args = tuple('arg%d' % i for i in range(n_args))
     getattr(_lib.F32, op)(*args)
     getattr(_lib.F64, op)(*args)

@@ -5,7 +5,7 @@ L = B._lib
 def bench(libpath):
     lib = C.CDLL(libpath)
     for name in ('bsig_gemm_f32', 'bsig_gemm_workspace_bytes'):
-        fn = getattr(lib, name); fn.restype, fn.argtypes = L._PROTOS[name]
+        fn = getattr(lib, name); fn.restype, fn.argtypes = L.PROTOS[name]
     out = []
     for (m, n, k, rows) in ((8192, 2048, 2310, None), (10000, 2048, 2310, 800)):
         a = torch.randn(rows or m, 2312, device='cuda:0')[:, :2310]
