@@ -112,6 +112,8 @@ def fit_chunk_table(sizes, seeds, n_updates, batch_size, test_frac):
 _HD, _HY, _CFG = C.POINTER(HeadDims), C.POINTER(F64Hyper), C.POINTER(MdnCfg)
 SIGNATURE_MAX_DEPTH = 6        # include/bsig_signature.h
 INPUT_NORM_SLAB_ROWS = 64      # include/bsig_input_norm.h
+RFF_BANDWIDTH_MAX_ROWS = 1024                   # include/bsig_rff_bandwidth.h
+RFF_BANDWIDTH_SELECT_WORKSPACE_BYTES = 8448     # include/bsig_rff_bandwidth.h
 # public header -> the prototypes of its declarations: name -> (restype, argtypes).  A new header adds its
 # table here and nothing else; tests/test_headers_host.py holds every table against its header.  (The tables of
 # the two base headers also go by a name: an entry point Precision routes fp32 to must not be one of the fp64
@@ -264,6 +266,15 @@ HEADERS['bsig_input_norm.h'] = {
     'bsig_input_norm_apply': (C.c_int, [vp, i64, vp, vp, vp, i64, i64, i64, vp]),
     'bsig_input_norm_apply_f64': (C.c_int, [vp, i64, vp, vp, vp, i64, i64, i64, vp]),
 }
+# the kernel bandwidth of an RFF map by the median heuristic, and the coefficient from that device scalar
+HEADERS['bsig_rff_bandwidth.h'] = {
+    'bsig_rff_bandwidth_workspace_bytes': (i64, [i64, i64]),
+    'bsig_rff_bandwidth_median': (C.c_int, [vp, i64, i64, i64, f64, vp, vp, sz, vp]),
+    'bsig_rff_bandwidth_median_f64': (C.c_int, [vp, i64, i64, i64, f64, vp, vp, sz, vp]),
+    'bsig_rff_bandwidth_select': (C.c_int, [vp, i64, vp, vp, sz, vp]),
+    'bsig_rff_coeff_dev': (C.c_int, [vp, vp, vp, i64, i64, i64, vp]),
+    'bsig_rff_coeff_dev_f64': (C.c_int, [vp, vp, vp, i64, i64, i64, vp]),
+}
 COMM_ID_BYTES = 128
 EXCHANGE_SUM, EXCHANGE_BROADCAST = 0, 1
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int, vp, i64, C.c_int, vp)
@@ -403,6 +414,9 @@ class Precision:
         # standardises)
         'input_norm_stats': ('bsig_input_norm_stats', 'bsig_input_norm_stats_f64'),
         'input_norm_apply': ('bsig_input_norm_apply', 'bsig_input_norm_apply_f64'),
+        # the median bandwidth of rows of either type, and freqs / sigma in the model's precision
+        'rff_bandwidth_median': ('bsig_rff_bandwidth_median', 'bsig_rff_bandwidth_median_f64'),
+        'rff_coeff_dev': ('bsig_rff_coeff_dev', 'bsig_rff_coeff_dev_f64'),
     }
     HYPER_OPS = ('head_forward', 'head_outputs', 'nll_from_tuple', 'loss_grad')    # take the hyper in fp64
     # the plan lifecycle

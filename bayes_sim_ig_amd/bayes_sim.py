@@ -74,7 +74,12 @@ class BayesSim(object):
         made on the device, kept in ``state_dict`` and applied alike by ``fit``,
         ``run_training`` and ``predict``; constant columns become zero;
         include/bsig_input_norm.h.  Meant for ``sigDepth`` >= 3, whose raw terms
-        reach (trainTrajLen - 1)^k / k!)."""
+        reach (trainTrajLen - 1)^k / k!), ``rffSigmaScale`` (a positive float,
+        default 1.0, only with ``'modelClass': 'MDRFF_<kernel>_median'``: that model
+        class sets the RFF bandwidth by the median heuristic -- ``rffSigmaScale``
+        times the median pairwise distance of the first chunk's training rows,
+        standardised first under ``inputNorm``, made on the device, kept in
+        ``state_dict``; include/bsig_rff_bandwidth.h)."""
         self.prior = prior
         self.proposal = proposal
         model_class = model_cfg['modelClass']
@@ -127,9 +132,17 @@ class BayesSim(object):
                 parts = model_class.split('_')
                 model_class, kernel = parts[0], parts[1]
                 if len(parts) > 2:
-                    sigma = float(parts[2])
+                    sigma = 'median' if parts[2] == 'median' else float(parts[2])
             kwargs.update({'n_feat': int(model_cfg.get('nFeat', 200)),
                            'sigma': sigma, 'kernel': kernel})
+        if 'rffSigmaScale' in model_cfg:
+            scale = model_cfg['rffSigmaScale']
+            if kwargs.get('sigma') != 'median':
+                raise ValueError("model_cfg['rffSigmaScale'] applies to 'modelClass': 'MDRFF_<kernel>_median', "
+                                 "not to %r" % (model_cfg['modelClass'],))
+            if not isinstance(scale, float) or not (np.isfinite(scale) and scale > 0.0):
+                raise ValueError("model_cfg['rffSigmaScale'] must be a positive float, got %r" % (scale,))
+            kwargs['sigma_scale'] = scale
         if model_class not in _MODELS:
             raise NameError("name '%s' is not defined" % model_class)
         dtype = model_cfg.get('dtype', 'float32')
@@ -217,6 +230,19 @@ class BayesSim(object):
             raise AssertionError('non-finite value in the trajectory summaries')
         return self
 
+    def fit_rff_bandwidth(self, states, actions):
+        """The counterpart of ``fit_input_norm`` for the bandwidth of an ``'MDRFF_<kernel>_median'`` model: from
+        the summaries of the given trajectories (the first 1024 at most; ``fit`` by itself takes the first
+        chunk's training rows), standardised first under ``inputNorm``, frozen from here on.  Synchronises, and
+        asserts that the bandwidth is finite."""
+        bw = self.model._require_rffbw()
+        self.model.fit_rff_bandwidth(self._summarize(states, actions))
+        if not bool(torch.isfinite(bw.sigma).item()):
+            bw.count.zero_()
+            bw.ready = False
+            raise AssertionError('non-finite value in the trajectory summaries')
+        return self
+
     def _standardize_block(self, summ, n_first):
         """fit()'s block path for a model with input_norm: the statistics, where they do not exist yet, from
         the rows the chunk loop would have used -- the training rows of the first chunk, ``n_first`` pairs --
@@ -272,9 +298,12 @@ class BayesSim(object):
         block's chunks in ONE launch of the persistent update kernel where the model's plan can; else chunk
         by chunk.  The logs (and the isfinite asserts) are read back after the last chunk is enqueued: one
         host synchronisation for the whole fit.  A model with input_norm: each block is standardised once,
-        before an MDRFF's features are projected from it, and its chunks are handed over as standardised."""
+        before an MDRFF's features are projected from it, and its chunks are handed over as standardised.
+        An ``'MDRFF_<kernel>_median'`` model: the bandwidth is made from the first block, after that and
+        before the projection."""
         model, n, done, pending = self.model, params.shape[0], 0, []
         model._check_input_norm_dp()
+        model._check_rff_bandwidth_dp()
         self._check_equal_counts(n)
         on_gpu = torch.is_tensor(traj_states) and traj_states.is_cuda
         flag = torch.zeros(1, dtype=torch.int32, device=traj_states.device) if on_gpu else None
@@ -287,6 +316,11 @@ class BayesSim(object):
                 summ = self._summarize(traj_states[lo:hi], traj_actions[lo:hi], flag, lazy=True)
                 if model._inorm is not None:
                     summ = self._standardize_block(summ, BayesSim.get_n_trajs_per_batch(n, lo))
+                if model._rffbw is not None and not model.rff_bandwidth_ready:
+                    # the bandwidth of the rows the chunk loop would have used: the first chunk's training
+                    # rows, as the projection sees them; nothing is read back
+                    n_first = _lib.split_rows(BayesSim.get_n_trajs_per_batch(n, lo), BayesSim.TEST_FRACTION)[0]
+                    model._bandwidth_of_rows(summ[:n_first])
                 # (a double MDRFF projects in double inside each call: chunk by chunk, no block launch)
                 feats = model.rff.to_features(summ) if model.rff is not None and not model._f64 else None
                 sizes = self._block_launch_sizes(n, lo, hi) if feats is not None and model._dp is None else []

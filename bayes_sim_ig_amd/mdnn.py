@@ -22,6 +22,10 @@ are not bitwise the reference's fp32 arithmetic.  The default, 'float32', is.
 ``MDNN(..., input_norm=True)`` (not in the reference, which normalises the targets only) adds a standardisation
 of the summaries to the model: per-column mean and reciprocal standard deviation (include/bsig_input_norm.h),
 made once on the device, kept in ``state_dict`` and applied by every entry point that takes summaries.
+
+``MDRFF(..., sigma='median')`` (not in the reference either) sets the feature map's bandwidth by the median
+heuristic (include/bsig_rff_bandwidth.h): one double on the device, made once from the first training rows as
+the estimator sees them, frozen, kept in ``state_dict``; the section "kernel bandwidth" below is its plumbing.
 """
 import contextlib
 import ctypes as C
@@ -170,6 +174,32 @@ class InputNorm(nn.Module):
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
         if prefix + 'count' in state_dict:
             self.ready = int(state_dict[prefix + 'count']) > 0
+
+
+class RffBandwidth(InputNorm):
+    """The bandwidth of an ``MDRFF(sigma='median')``: ``sigma`` (float64 scalar: ``scale`` times the median
+    pairwise distance of the rows it was made from, include/bsig_rff_bandwidth.h) and ``count`` (int64 scalar:
+    the number of those rows, 0: not there yet).  Device, dtypes and ``ready`` as InputNorm's.  ``version``
+    counts the times the value was given: what was derived from an earlier one (freqs / sigma) is stale."""
+
+    def __init__(self, scale, device):
+        nn.Module.__init__(self)
+        self.scale = float(scale)
+        self.register_buffer('sigma', torch.ones((), dtype=torch.float64, device=device))
+        self.register_buffer('count', torch.zeros((), dtype=torch.int64, device=device))
+        self.ready = False
+        self.version = 0
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        self.version += 1
+
+    def require_ready(self):
+        if not self.ready:
+            raise RuntimeError("the kernel bandwidth of this model (sigma='median') does not exist yet: "
+                               'run_training / BayesSim.fit make it from their first training rows; or call '
+                               'fit_rff_bandwidth / set_rff_bandwidth / load_state_dict first')
+        return self
 
 
 class MDNN(nn.Module):
@@ -612,6 +642,80 @@ class MDNN(nn.Module):
         xs, _, _ = self._input_rows(x, self._prec.dtype)
         return self.normalize_inputs(xs)
 
+    # ------------------------------------------------------ kernel bandwidth
+    @property
+    def _rffbw(self):
+        """The RffBandwidth submodule of an ``MDRFF(sigma='median')``, else None."""
+        return self._modules.get('rff_bandwidth')
+
+    @property
+    def rff_bandwidth_ready(self):
+        """True once an ``MDRFF(sigma='median')`` has its bandwidth (``fit_rff_bandwidth``,
+        ``set_rff_bandwidth``, the first ``run_training``, ``load_state_dict``).  False for any other model."""
+        return self._rffbw is not None and self._rffbw.ready
+
+    def _require_rffbw(self, ready=False):
+        bw = self._rffbw
+        if bw is None:
+            raise RuntimeError("this model was built without sigma='median'")
+        return bw.require_ready() if ready else bw
+
+    def _bandwidth_of(self, xs, ld, n, prec):
+        """sigma <- scale x the median pairwise distance of the first ``n`` rows (at most
+        _lib.RFF_BANDWIDTH_MAX_ROWS of them) of ``xs``, device rows of ``prec``'s dtype as the projection will
+        see them; frozen from here on.  Asynchronous: sigma and ``count`` are written on the stream."""
+        lib, bw = self._gpu(), self._rffbw
+        need = int(lib.bsig_rff_bandwidth_workspace_bytes(n, self.input_dim))
+        assert need > 0, 'the median bandwidth needs at least two rows'
+        ws = self._buf('rffbw_ws', need // 8, torch.float64)
+        prec.rff_bandwidth_median(_lib.ptr(xs), ld, n, self.input_dim, bw.scale, _lib.ptr(bw.sigma), _lib.ptr(ws),
+                                  ws.numel() * 8, _lib.stream())
+        bw.count.fill_(min(n, _lib.RFF_BANDWIDTH_MAX_ROWS))
+        bw.ready = True
+        bw.version += 1
+
+    def _bandwidth_of_rows(self, x):
+        """``_bandwidth_of`` all rows of ``x`` (fp32 or double; anything else as fp32), taken in their own type:
+        a widened fp32 row gives the bits of the fp32 row."""
+        dtype = torch.float64 if x.dtype == torch.float64 else torch.float32
+        xs, ld = _lib.as_rows(x, self._flat.device, dtype)
+        assert xs.shape[1] == self.input_dim, 'expected rows of %d columns' % self.input_dim
+        self._bandwidth_of(xs, ld, xs.shape[0], _lib.F64 if dtype == torch.float64 else _lib.F32)
+
+    @_on_model_device
+    def fit_rff_bandwidth(self, x):
+        """Make the bandwidth from the rows of ``x`` (the first _lib.RFF_BANDWIDTH_MAX_ROWS at most) on the
+        device and freeze it: no later call refits.  A model with ``input_norm`` standardises the rows first,
+        in its own precision (RuntimeError while it has no statistics)."""
+        self._require_rffbw()
+        if self._inorm is not None:
+            self._require_inorm(ready=True)
+        self._gpu()
+        if hasattr(x, 'materialize'):
+            x = x.materialize()
+        x = x[:_lib.RFF_BANDWIDTH_MAX_ROWS]
+        self._bandwidth_of_rows(x if self._inorm is None else self._standardised(x))
+        return self
+
+    def set_rff_bandwidth(self, sigma):
+        """The host-given form of ``fit_rff_bandwidth``: ``sigma``, a positive finite number, taken as it is
+        (``sigma_scale`` is not applied to it)."""
+        bw = self._require_rffbw()
+        sigma = float(sigma)
+        if not (np.isfinite(sigma) and sigma > 0.0):
+            raise ValueError('set_rff_bandwidth: sigma must be a positive finite number, got %r' % (sigma,))
+        bw.sigma.fill_(sigma)
+        bw.count.fill_(1)
+        bw.ready = True
+        bw.version += 1
+        return self
+
+    def _check_rff_bandwidth_dp(self):
+        if self._rffbw is not None and not self._rffbw.ready and self._dp is not None:
+            raise ValueError("a data-parallel model with sigma='median' needs its bandwidth before run_training "
+                             '(every rank would fit it on its own first chunk): call fit_rff_bandwidth or '
+                             'set_rff_bandwidth with the same value on every rank first')
+
     # ----------------------------------------------------------- forward
     @_on_model_device
     def _head_forward(self, x, is_feat=False):
@@ -639,10 +743,13 @@ class MDNN(nn.Module):
         """Reference mdnn.py:89-125 -> (weights[B,K], mu[B,D,K], L_d[B,D,K],
         L[B,L_size,K] | None).  ``noise`` injects the rand_like draw.  Takes no plan: its products
         are fp32 whatever the model's matmul precision.  A model with ``input_norm`` standardises ``x``
-        first (RuntimeError while it has no statistics)."""
+        first (RuntimeError while it has no statistics; likewise an ``MDRFF(sigma='median')`` without its
+        bandwidth)."""
         norm = self._inorm if not _is_feat else None
         if norm is not None:
             self._require_inorm(ready=True)
+        if self._rffbw is not None and not _is_feat:
+            self._rffbw.require_ready()
         self._gpu()
         prec = self._prec
         cfg, out = self._head_forward(x if norm is None else self._standardised(x), _is_feat)
@@ -707,6 +814,8 @@ class MDNN(nn.Module):
         already normalised; ``x`` is not standardised yet (a model with ``input_norm`` does that here)."""
         if self._inorm is not None:
             self._require_inorm(ready=True)
+        if self._rffbw is not None:
+            self._rffbw.require_ready()
         self._gpu()
         prec = self._prec
         cfg = self._cfg()
@@ -778,10 +887,15 @@ class MDNN(nn.Module):
         from the first chunk's 800 training rows.  Under ``enable_data_parallel`` that would give every
         replica another scale: ValueError, before anything is enqueued.  A ``CrossCorrFactors`` input is
         materialised first (the standardised outer product does not factor): the call then behaves as under
-        BSIG_NO_FUSED_SUMMARY=1, on whatever plan the engine has for summary rows."""
+        BSIG_NO_FUSED_SUMMARY=1, on whatever plan the engine has for summary rows.
+
+        An ``MDRFF(sigma='median')`` without its bandwidth makes it here too, at the same point: from the
+        staged training rows, standardised where the model does that, before anything is projected; under
+        ``enable_data_parallel`` that is the same ValueError."""
         self._check_f64_dp()
         if not _standardized:
             self._check_input_norm_dp()
+        self._check_rff_bandwidth_dp()
 
         def once():
             return self._run_training_once(x_data, y_data, n_updates, batch_size, test_frac,
@@ -977,6 +1091,9 @@ class MDNN(nn.Module):
             x_data, ld_raw, _ = self._input_rows(x_data, prec.dtype)
             if not norm.ready:
                 self._stats_of(x_data, ld_raw, n_train, prec)
+        make_bw = self._rffbw is not None and not self._rffbw.ready
+        if make_bw and isinstance(x_data, CrossCorrFactors):
+            x_data = x_data.materialize()
         ldy = _lib.round_up(d, 4)
         ys, ldy_src = _lib.as_rows(y_data, dev, prec.dtype)
         assert x_data.shape[1] == self.input_dim and ys.shape[1] == d
@@ -1011,6 +1128,10 @@ class MDNN(nn.Module):
                                           _lib.ptr(x_stage), ldx, n_tot, self.input_dim, st)
                 else:
                     prec.copy_rows(_lib.ptr(xs), ldx_src, None, _lib.ptr(x_stage), ldx, n_tot, self.input_dim, st)
+        if make_bw:
+            # the bandwidth of the rows the projection is about to see: the staged training rows, never the
+            # held-out ones (BayesSim.fit makes it from the same rows of its first block, with the same bits)
+            self._bandwidth_of(x_stage, ldx, n_train, prec)
         y_stage = self._buf('y_stage', cap_rows * ldy)
         self._stage_targets(ys, ldy_src, y_stage, ldy, n_tot, st)
         n_ids = n_updates * batch_size
@@ -1093,6 +1214,8 @@ class MDNN(nn.Module):
         ntest, dim = xs.size()
         if self._inorm is not None:
             self._require_inorm(ready=True)
+        if self._rffbw is not None:
+            self._rffbw.require_ready()
         if self.rff is not None and self._matmul != 'float32':
             # the projection follows the model's matmul precision; the head products stay fp32
             feats = self.rff.to_features(xs if self._inorm is None else self._standardised(xs))

@@ -6,6 +6,10 @@ exactly like the reference (rff.py:111-120, 135-184), so seeded runs get
 bit-identical frequencies.  The projection ``a*[cos|sin](x (freqs/sigma)^T)``
 (rff.py:122-132) is the fp32-MFMA GEMM with fused sincos epilogue in
 csrc/gemm_f32.hip.
+
+``bandwidth`` (not in the reference): the RffBandwidth of an ``MDRFF(sigma='median')``.  The coefficient is then
+``freqs / sigma`` with the ONE double that submodule holds on the device (bsig_rff_coeff_dev,
+include/bsig_rff_bandwidth.h), and the reference's ``sigma`` attribute is filled from it when somebody reads it.
 """
 import numpy as np
 import torch
@@ -72,9 +76,11 @@ class RFF:
     """
 
     def __init__(self, n_feat, d, sigma, cos_only=False, quasi_random=True,
-                 kernel='RBF', device='cpu', freqs=None):
+                 kernel='RBF', device='cpu', freqs=None, bandwidth=None):
         self.n_feat, self.d, self.device = n_feat, int(d), device
         self.cos_only = bool(cos_only)
+        self.bandwidth = bandwidth      # (mdnn.RffBandwidth | None; ``sigma`` is then a placeholder)
+        self._coeff_version = None
         if isinstance(sigma, list):
             assert len(sigma) == d
             sig = np.array(sigma, dtype=np.float32)
@@ -106,8 +112,40 @@ class RFF:
     def m_feat(self):
         return self.freqs.shape[0]
 
+    @property
+    def sigma(self):
+        """The reference's [1, d] attribute.  With ``bandwidth``: filled from the device scalar when read (a
+        host read-back; nothing on the fit path asks)."""
+        if self.bandwidth is not None:
+            bw = self.bandwidth.require_ready()
+            return torch.full((1, self.d), float(bw.sigma.item()), dtype=torch.float32, device=self.device)
+        return self._sigma
+
+    @sigma.setter
+    def sigma(self, value):
+        self._sigma = value
+
+    def _coeff_from_bandwidth(self):
+        """freqs / sigma from the device scalar, in the one buffer the plans bind; redone when the bandwidth
+        has been given anew."""
+        bw = self.bandwidth.require_ready()
+        lib = _lib.require_gpu()
+        if self._coeff is None or self._coeff_version != bw.version:
+            dev = self.freqs.device if self.freqs.is_cuda else torch.device(
+                'cuda', torch.cuda.current_device())
+            fr = self.freqs.to(dev).contiguous()
+            ld = _lib.round_up(self.d, 4)
+            if self._coeff is None or self._coeff.device != dev:
+                self._coeff = torch.empty((self.m_feat, ld), dtype=torch.float32, device=dev)
+            _lib.check(lib.bsig_rff_coeff_dev(_lib.ptr(fr), _lib.ptr(bw.sigma.to(dev)), _lib.ptr(self._coeff),
+                                              self.m_feat, self.d, ld, _lib.stream()))
+            self._coeff_version = bw.version
+        return self._coeff
+
     def coeff(self, sigma=None):
         """freqs / sigma (rff.py:124,130), pitch rounded up to 4 floats."""
+        if sigma is None and self.bandwidth is not None:
+            return self._coeff_from_bandwidth()
         lib = _lib.require_gpu()
         if sigma is not None or self._coeff is None:
             dev = self.freqs.device if self.freqs.is_cuda else torch.device(
@@ -124,6 +162,8 @@ class RFF:
         return self._coeff
 
     def _project(self, x, sigma, cos_only):
+        if sigma is None and self.bandwidth is not None:
+            self.bandwidth.require_ready()
         lib = _lib.require_gpu()
         home = x.device
         co = self.coeff(sigma)
