@@ -14,4 +14,4 @@ from .rff import RFF                          # noqa: F401
 from .summarizers import (pad_states_actions, summary_start, summary_waypts,  # noqa: F401
                           summary_corr, summary_corrdiff, summary_signatory,
                           signature_depth, cross_correlation, summary_logsignature,
-                          logsignature_dim, lyndon_words)
+                          logsignature_dim, lyndon_words, summary_xcorr, xcorr_dim)

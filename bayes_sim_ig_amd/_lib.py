@@ -275,6 +275,14 @@ HEADERS['bsig_rff_bandwidth.h'] = {
     'bsig_rff_coeff_dev': (C.c_int, [vp, vp, vp, i64, i64, i64, vp]),
     'bsig_rff_coeff_dev_f64': (C.c_int, [vp, vp, vp, i64, i64, i64, vp]),
 }
+# the paper's time-lagged cross-correlation summary
+HEADERS['bsig_xcorr.h'] = {
+    'bsig_xcorr_dim': (i64, [C.c_int] * 3),
+    'bsig_xcorr_fits': (C.c_int, [C.c_int] * 7),
+    'bsig_xcorr_group': (C.c_int, [C.c_int] * 7),
+    'bsig_xcorr': (C.c_int, [vp, vp, vp, i64] + [C.c_int] * 6 + [i64, vp, vp]),
+    'bsig_xcorr_f64': (C.c_int, [vp, vp, vp, i64] + [C.c_int] * 6 + [i64, vp, vp]),
+}
 COMM_ID_BYTES = 128
 EXCHANGE_SUM, EXCHANGE_BROADCAST = 0, 1
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int, vp, i64, C.c_int, vp)
@@ -410,6 +418,7 @@ class Precision:
         'copy_rows': ('bsig_copy_rows', 'bsig_copy_rows_f64'),
         'signature_ex': ('bsig_signature_ex', 'bsig_signature_ex_f64'),
         'logsignature': ('bsig_logsignature', 'bsig_logsignature_f64'),
+        'xcorr': ('bsig_xcorr', 'bsig_xcorr_f64'),
         # the input-side companions of normalize_rows / copy_rows (the statistics of rows, and the copy that
         # standardises)
         'input_norm_stats': ('bsig_input_norm_stats', 'bsig_input_norm_stats_f64'),

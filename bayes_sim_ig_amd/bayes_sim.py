@@ -20,12 +20,14 @@ from .mdnn import MDNN
 from .mdrff import MDRFF
 from .summarizers import (pad_states_actions, summary_start, summary_waypts,  # noqa: F401
                           summary_corr, summary_corrdiff, summary_signatory,
-                          signature_depth, cross_correlation, summary_logsignature)
+                          signature_depth, cross_correlation, summary_logsignature,
+                          summary_xcorr)
 
 _SUMMARIZERS = {
     'summary_start': summary_start, 'summary_waypts': summary_waypts,
     'summary_corr': summary_corr, 'summary_corrdiff': summary_corrdiff,
     'summary_signatory': summary_signatory, 'summary_logsignature': summary_logsignature,
+    'summary_xcorr': summary_xcorr,
 }
 _SIGNATURES = ('summary_signatory', 'summary_logsignature')      # take sigDepth and sigChannels
 _MODELS = {'MDNN': MDNN, 'MDRFF': MDRFF}
@@ -62,7 +64,13 @@ class BayesSim(object):
         ``'summarizerFxn': 'summary_logsignature'`` -- not in the reference -- is the
         log-signature of the same path at the Lyndon words, ``logsignature_dim``
         inputs instead of ``signature_dim``, under the same LDS condition,
-        include/bsig_logsignature.h), ``dtype``
+        include/bsig_logsignature.h; ``'summarizerFxn': 'summary_xcorr'`` -- not in
+        the reference either -- is the paper's time-lagged cross-correlation of the
+        state differences in time with the actions plus their mean and standard
+        deviation, ``xcorr_dim`` inputs from the whole trajectory, with its own keys
+        ``xcorrLags`` (an int >= 0, default 0: the largest lag, below the number of
+        feature steps of ``trainTrajLen`` states) and ``xcorrStateDiff`` (a bool,
+        default True; False: the states themselves), include/bsig_xcorr.h), ``dtype``
         ('float32', the default, or 'float64': the estimator's fp64 mode, as
         ``bs.model.double()``), ``summaryDtype`` ('float32', the default in both
         modes: the summaries are made in fp32 and a double model gets them
@@ -97,6 +105,15 @@ class BayesSim(object):
             if name not in _SIGNATURES:
                 raise ValueError("model_cfg['sigChannels'] applies to 'summary_signatory', not to %r" % name)
             self._sig_channels = _summ.signature_channels(self._sig_channels, obs_dim, act_dim)
+        self._xcorr_lags = model_cfg.get('xcorrLags', 0)
+        self._xcorr_state_diff = model_cfg.get('xcorrStateDiff', True)
+        for key in ('xcorrLags', 'xcorrStateDiff'):
+            if key in model_cfg and name != 'summary_xcorr':
+                raise ValueError("model_cfg[%r] applies to 'summary_xcorr', not to %r" % (key, name))
+        if isinstance(self._xcorr_lags, bool) or not isinstance(self._xcorr_lags, int) or self._xcorr_lags < 0:
+            raise ValueError("model_cfg['xcorrLags'] must be an int >= 0, got %r" % (self._xcorr_lags,))
+        if not isinstance(self._xcorr_state_diff, bool):
+            raise ValueError("model_cfg['xcorrStateDiff'] must be a bool, got %r" % (self._xcorr_state_diff,))
         # the reference pushes a zero trajectory through the summarizer to get
         # the width (bayes_sim.py:57-60); the width is a closed form
         itemsize = 8 if model_cfg.get('summaryDtype', 'float32') == 'float64' else 4
@@ -113,6 +130,16 @@ class BayesSim(object):
             traj_summaries_dim = _summ.logsignature_dim(path_dim, depth)
             if depth > 1:
                 _lib.check(_lib.load().bsig_signature_ex_fits(path_dim, model_cfg['trainTrajLen'], depth, itemsize))
+        elif name == 'summary_xcorr':
+            # include/bsig_xcorr.h: the lags against the feature steps, then the trajectory against the LDS
+            length = model_cfg['trainTrajLen']
+            steps = length - (1 if self._xcorr_state_diff else 0)
+            if self._xcorr_lags > steps - 1:
+                raise ValueError("model_cfg['xcorrLags'] = %d is outside 0..%d: trainTrajLen = %d leaves %d "
+                                 "feature steps" % (self._xcorr_lags, steps - 1, length, steps))
+            traj_summaries_dim = _summ.xcorr_dim(obs_dim, act_dim, self._xcorr_lags)
+            _lib.check(_lib.load().bsig_xcorr_fits(length, length, obs_dim, act_dim, self._xcorr_lags,
+                                                   1 if self._xcorr_state_diff else 0, itemsize))
         else:
             traj_summaries_dim = _summ.summary_dim(
                 name, model_cfg['trainTrajLen'], obs_dim, act_dim,
@@ -194,6 +221,11 @@ class BayesSim(object):
             if lazy and self._lazy_summaries():
                 kw['lazy'] = True
             return self.summarizer_fxn(states, actions, **kw)
+        if self.summarizer_name == 'summary_xcorr':
+            if finite_flag is not None:
+                kw['check_finite'] = finite_flag
+            return self.summarizer_fxn(states, actions, max_lag=self._xcorr_lags,
+                                       state_diff=self._xcorr_state_diff, **kw)
         return self.summarizer_fxn(states, actions, **kw)
 
     def _lazy_summaries(self):

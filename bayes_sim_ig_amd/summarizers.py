@@ -265,6 +265,61 @@ def summary_corr(states, actions, out=None, check_finite=True, lazy=False, dtype
                              check_finite=check_finite, lazy=lazy, dtype=dtype)
 
 
+def xcorr_dim(obs_dim, act_dim, max_lag=0):
+    """Width of a ``summary_xcorr`` row, ``(max_lag + 1) * obs_dim * act_dim + 2 * obs_dim``, without touching
+    the GPU (bsig_xcorr_dim, include/bsig_xcorr.h).  ValueError for a dimension below 1, a negative
+    ``max_lag`` or a width past 2^31 - 1."""
+    width = int(_lib.load().bsig_xcorr_dim(int(obs_dim), int(act_dim), _xcorr_lag(max_lag)))
+    if width < 0:
+        raise ValueError('no cross-correlation row for obs_dim=%r, act_dim=%r, max_lag=%r (dimensions >= 1, '
+                         'max_lag >= 0, width below 2^31)' % (obs_dim, act_dim, max_lag))
+    return width
+
+
+def _xcorr_lag(max_lag):
+    """``max_lag`` as an int that fits the C ABI; ValueError if it is not an integer (a bool is not)."""
+    if isinstance(max_lag, bool):
+        raise ValueError('max_lag must be an int >= 0, got %r' % (max_lag,))
+    try:
+        lag = operator.index(max_lag)
+    except TypeError:
+        raise ValueError('max_lag must be an int >= 0, got %r' % (max_lag,)) from None
+    return max(min(lag, 2 ** 31 - 1), -1)
+
+
+def summary_xcorr(states, actions, max_lag=0, state_diff=True, out=None, check_finite=True, dtype=None):
+    """The time-lagged cross-correlation summary of the BayesSim paper (RSS 2019, section IV.F; not in the
+    reference, whose ``cross_correlation`` is another statistic): with ``f_t = s_(t+1) - s_t``, the difference
+    in TIME (``state_diff=False``: ``f_t = s_t``), M such steps, and the actions padded as
+    ``pad_states_actions`` leaves them, the row is ``[c_0 | ... | c_max_lag | mu | sigma]`` --
+    ``c_tau[i, j] = 1/(M - tau) * sum_t f_(t+tau),i * a_t,j`` flattened with i major, then the mean and the
+    population standard deviation of every ``f_.,i`` -- ``xcorr_dim(sd, ad, max_lag)`` numbers from the whole
+    trajectory, whatever its length (include/bsig_xcorr.h, csrc/xcorr.h).
+
+    ``out=``, ``check_finite`` and ``dtype=torch.float64`` are ``cross_correlation``'s.  ValueError (before
+    any GPU call) for a ``max_lag`` outside ``0..M-1``; NotImplementedError when a trajectory does not fit a
+    workgroup's LDS."""
+    prec = _precision(dtype)
+    lag = _xcorr_lag(max_lag)
+    assert len(states.shape) == 3, 'Need states: ntraj x n_steps x state_dim'
+    assert len(actions.shape) == 3, 'Need actions: ntraj x n_steps x state_dim'
+    m = states.shape[1] - (1 if state_diff else 0)
+    assert m >= 1, 'Need %d states or more' % (2 if state_diff else 1)
+    if not 0 <= lag <= m - 1:
+        raise ValueError('max_lag %r is outside 0..%d: the feature series has %d steps' % (max_lag, m - 1, m))
+    s, a, home = _prep(states, actions, prec)
+    n, t, sd = s.shape
+    ad = a.shape[2]
+    width = xcorr_dim(sd, ad, lag)
+    buf, ld = _alloc(n, width, s.device, out, prec)
+    flag, read_back = _finite_flag(check_finite, s.device)
+    prec.xcorr(
+        _lib.ptr(s), _lib.ptr(a), _lib.ptr(buf), n, t, a.shape[1], sd, ad, lag,
+        1 if state_diff else 0, ld, _lib.ptr(flag), _lib.stream())
+    _assert_finite(flag, read_back)
+    return _finish(buf, n, width, home, out)
+
+
 def signature_depth(ndim):
     """Reference summarizers.py:133-141."""
     max_output_dim = 110 ** 2
