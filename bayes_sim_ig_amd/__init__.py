@@ -6,12 +6,14 @@ Host-side mirror of the reference's Python interface for this path
 (include/bsig.h, csrc/*.hip).  ``compat.install()`` registers the
 reference's module paths (``bayes_sim_ig.models.mdnn`` ...) as aliases.
 """
-from . import _lib, pairs, pdf, summarizers   # noqa: F401
+from . import _lib, kme, pairs, pdf, summarizers   # noqa: F401
 from .bayes_sim import BayesSim               # noqa: F401
+from .kme import KernelMeanEmbedding          # noqa: F401
 from .mdnn import MDNN                        # noqa: F401
 from .mdrff import MDRFF                      # noqa: F401
 from .rff import RFF                          # noqa: F401
 from .summarizers import (pad_states_actions, summary_start, summary_waypts,  # noqa: F401
                           summary_corr, summary_corrdiff, summary_signatory,
                           signature_depth, cross_correlation, summary_logsignature,
-                          logsignature_dim, lyndon_words, summary_xcorr, xcorr_dim)
+                          logsignature_dim, lyndon_words, summary_xcorr, xcorr_dim,
+                          summary_kme, kme_row_dim)

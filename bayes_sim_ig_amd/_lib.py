@@ -283,6 +283,19 @@ HEADERS['bsig_xcorr.h'] = {
     'bsig_xcorr': (C.c_int, [vp, vp, vp, i64] + [C.c_int] * 6 + [i64, vp, vp]),
     'bsig_xcorr_f64': (C.c_int, [vp, vp, vp, i64] + [C.c_int] * 6 + [i64, vp, vp]),
 }
+# the random-feature kernel mean embedding summary
+KME_BLOCK_ROWS = 32            # include/bsig_kme.h
+HEADERS['bsig_kme.h'] = {
+    'bsig_kme_row_dim': (i64, [C.c_int] * 4),
+    'bsig_kme_fits': (C.c_int, [C.c_int] * 8),
+    'bsig_kme_group': (C.c_int, [C.c_int] * 8),
+    'bsig_kme_rows': (C.c_int, [vp, vp, vp, i64] + [C.c_int] * 6 + [i64, vp]),
+    'bsig_kme_rows_f64': (C.c_int, [vp, vp, vp, i64] + [C.c_int] * 6 + [i64, vp]),
+    'bsig_kme_coeff': (C.c_int, [vp, i64, vp, f64, vp, i64, i64, i64, vp]),
+    'bsig_kme_coeff_f64': (C.c_int, [vp, i64, vp, f64, vp, i64, i64, i64, vp]),
+    'bsig_kme': (C.c_int, [vp, vp, vp, i64, vp, i64] + [C.c_int] * 7 + [i64, vp, vp]),
+    'bsig_kme_f64': (C.c_int, [vp, vp, vp, i64, vp, i64] + [C.c_int] * 7 + [i64, vp, vp]),
+}
 COMM_ID_BYTES = 128
 EXCHANGE_SUM, EXCHANGE_BROADCAST = 0, 1
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int, vp, i64, C.c_int, vp)
@@ -419,6 +432,10 @@ class Precision:
         'signature_ex': ('bsig_signature_ex', 'bsig_signature_ex_f64'),
         'logsignature': ('bsig_logsignature', 'bsig_logsignature_f64'),
         'xcorr': ('bsig_xcorr', 'bsig_xcorr_f64'),
+        # the kernel mean embedding, its rows written out and its coefficients in the output precision
+        'kme': ('bsig_kme', 'bsig_kme_f64'),
+        'kme_rows': ('bsig_kme_rows', 'bsig_kme_rows_f64'),
+        'kme_coeff': ('bsig_kme_coeff', 'bsig_kme_coeff_f64'),
         # the input-side companions of normalize_rows / copy_rows (the statistics of rows, and the copy that
         # standardises)
         'input_norm_stats': ('bsig_input_norm_stats', 'bsig_input_norm_stats_f64'),

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import kme as _kme
 from . import pdf
 from . import summarizers as _summ
 from .mdnn import MDNN
@@ -21,15 +22,36 @@ from .mdrff import MDRFF
 from .summarizers import (pad_states_actions, summary_start, summary_waypts,  # noqa: F401
                           summary_corr, summary_corrdiff, summary_signatory,
                           signature_depth, cross_correlation, summary_logsignature,
-                          summary_xcorr)
+                          summary_xcorr, summary_kme)
 
 _SUMMARIZERS = {
     'summary_start': summary_start, 'summary_waypts': summary_waypts,
     'summary_corr': summary_corr, 'summary_corrdiff': summary_corrdiff,
     'summary_signatory': summary_signatory, 'summary_logsignature': summary_logsignature,
-    'summary_xcorr': summary_xcorr,
+    'summary_xcorr': summary_xcorr, 'summary_kme': summary_kme,
 }
 _SIGNATURES = ('summary_signatory', 'summary_logsignature')      # take sigDepth and sigChannels
+_KME_KEYS = ('kmeFeatures', 'kmeScale', 'kmeSeed', 'kmeDiff', 'kmeTime')      # 'summary_kme' only
+
+
+def _kme_arguments(model_cfg):
+    """The keys of ``'summarizerFxn': 'summary_kme'`` as KernelMeanEmbedding's arguments; ValueError on a value
+    of the wrong kind."""
+    n_feat = model_cfg.get('kmeFeatures', 256)
+    if isinstance(n_feat, bool) or not isinstance(n_feat, int) or n_feat < 2 or n_feat % 2:
+        raise ValueError("model_cfg['kmeFeatures'] must be an even int >= 2, got %r" % (n_feat,))
+    scale = model_cfg.get('kmeScale', 1.0)
+    if not isinstance(scale, float) or not (np.isfinite(scale) and scale > 0.0):
+        raise ValueError("model_cfg['kmeScale'] must be a positive float, got %r" % (scale,))
+    seed = model_cfg.get('kmeSeed', 0)
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 32:
+        raise ValueError("model_cfg['kmeSeed'] must be an int in 0..2^32 - 1, got %r" % (seed,))
+    flags = {}
+    for key, default in (('kmeDiff', True), ('kmeTime', False)):
+        flags[key] = model_cfg.get(key, default)
+        if not isinstance(flags[key], bool):
+            raise ValueError("model_cfg[%r] must be a bool, got %r" % (key, flags[key]))
+    return {'n_feat': n_feat, 'scale': scale, 'seed': seed, 'diff': flags['kmeDiff'], 'time': flags['kmeTime']}
 _MODELS = {'MDNN': MDNN, 'MDRFF': MDRFF}
 
 
@@ -70,7 +92,19 @@ class BayesSim(object):
         deviation, ``xcorr_dim`` inputs from the whole trajectory, with its own keys
         ``xcorrLags`` (an int >= 0, default 0: the largest lag, below the number of
         feature steps of ``trainTrajLen`` states) and ``xcorrStateDiff`` (a bool,
-        default True; False: the states themselves), include/bsig_xcorr.h), ``dtype``
+        default True; False: the states themselves), include/bsig_xcorr.h;
+        ``'summarizerFxn': 'summary_kme'`` -- not in the reference either -- is the
+        random-feature kernel mean embedding of the transitions ``[s_t | a_t |
+        s_(t+1) - s_t]``, ``kmeFeatures`` inputs from every step whatever the task's
+        dimensions and length, with its own keys ``kmeFeatures`` (an even int >= 2,
+        default 256), ``kmeScale`` (a positive float, default 1.0: times each
+        column's standard deviation times sqrt(d) is that column's bandwidth),
+        ``kmeSeed`` (an int >= 0, default 0: the frequencies' own generator),
+        ``kmeDiff`` (a bool, default True; False: no state differences in the rows)
+        and ``kmeTime`` (a bool, default False; True: the step's position leads the
+        row); the per-column scale is made on the device from the first chunk's first
+        training trajectories and kept, with the frequencies, in
+        ``bs.embedding.state_dict()``; include/bsig_kme.h), ``dtype``
         ('float32', the default, or 'float64': the estimator's fp64 mode, as
         ``bs.model.double()``), ``summaryDtype`` ('float32', the default in both
         modes: the summaries are made in fp32 and a double model gets them
@@ -114,6 +148,10 @@ class BayesSim(object):
             raise ValueError("model_cfg['xcorrLags'] must be an int >= 0, got %r" % (self._xcorr_lags,))
         if not isinstance(self._xcorr_state_diff, bool):
             raise ValueError("model_cfg['xcorrStateDiff'] must be a bool, got %r" % (self._xcorr_state_diff,))
+        self.embedding = None
+        for key in _KME_KEYS:
+            if key in model_cfg and name != 'summary_kme':
+                raise ValueError("model_cfg[%r] applies to 'summary_kme', not to %r" % (key, name))
         # the reference pushes a zero trajectory through the summarizer to get
         # the width (bayes_sim.py:57-60); the width is a closed form
         itemsize = 8 if model_cfg.get('summaryDtype', 'float32') == 'float64' else 4
@@ -140,6 +178,17 @@ class BayesSim(object):
             traj_summaries_dim = _summ.xcorr_dim(obs_dim, act_dim, self._xcorr_lags)
             _lib.check(_lib.load().bsig_xcorr_fits(length, length, obs_dim, act_dim, self._xcorr_lags,
                                                    1 if self._xcorr_state_diff else 0, itemsize))
+        elif name == 'summary_kme':
+            # include/bsig_kme.h: the keys, then a block of rows against the LDS; the module is built once the
+            # model below has made its draws (it has a generator of its own all the same)
+            kme_args = _kme_arguments(model_cfg)
+            traj_summaries_dim = kme_args['n_feat']
+            length = model_cfg['trainTrajLen']
+            if length - (1 if kme_args['diff'] else 0) < 1:
+                raise ValueError("model_cfg['trainTrajLen'] = %d leaves no transition row" % (length,))
+            _summ.kme_row_dim(obs_dim, act_dim, kme_args['diff'], kme_args['time'])
+            _lib.check(_lib.load().bsig_kme_fits(length, length, obs_dim, act_dim, traj_summaries_dim // 2,
+                                                 int(kme_args['diff']), int(kme_args['time']), itemsize))
         else:
             traj_summaries_dim = _summ.summary_dim(
                 name, model_cfg['trainTrajLen'], obs_dim, act_dim,
@@ -198,6 +247,8 @@ class BayesSim(object):
             self.model.set_matmul_precision(matmul)
         if dtype == 'float64':
             self.model.double()
+        if name == 'summary_kme':
+            self.embedding = _kme.KernelMeanEmbedding(obs_dim, act_dim, device=device, **kme_args)
 
     @staticmethod
     def get_n_trajs_per_batch(n_train_trajs, n_train_trajs_done):
@@ -226,6 +277,10 @@ class BayesSim(object):
                 kw['check_finite'] = finite_flag
             return self.summarizer_fxn(states, actions, max_lag=self._xcorr_lags,
                                        state_diff=self._xcorr_state_diff, **kw)
+        if self.summarizer_name == 'summary_kme':
+            if finite_flag is not None:
+                kw['check_finite'] = finite_flag
+            return self.summarizer_fxn(states, actions, self.embedding, **kw)
         return self.summarizer_fxn(states, actions, **kw)
 
     def _lazy_summaries(self):
@@ -239,6 +294,8 @@ class BayesSim(object):
                      _summaries=None, _feats=None, _standardized=False):
         """One chunk: summarize, then NUM_GRAD_UPDATES Adam updates of
         MINIBATCH_SIZE (reference bayes_sim.py:91-114)."""
+        if _summaries is None:
+            self._embedding_scale_of_chunk(traj_states, traj_actions)
         traj_summaries = _summaries if _summaries is not None else \
             self._summarize(traj_states, traj_actions, _finite_flag, lazy=True)
         kw = {} if _feats is None else {'_feats': _feats}
@@ -249,6 +306,40 @@ class BayesSim(object):
             n_updates=BayesSim.NUM_GRAD_UPDATES,
             batch_size=BayesSim.MINIBATCH_SIZE,
             test_frac=BayesSim.TEST_FRACTION, _defer=_defer, **kw)
+
+    def _require_embedding(self):
+        if self.embedding is None:
+            raise RuntimeError("this BayesSim was built without 'summarizerFxn': 'summary_kme'")
+        return self.embedding
+
+    def fit_embedding_scale(self, states, actions):
+        """The per-column scale of ``'summarizerFxn': 'summary_kme'`` from the given trajectories (the first
+        256 at most; ``fit`` and ``run_training`` by themselves take the first chunk's first training
+        trajectories), frozen from here on.  Synchronises, and asserts that the scale is finite."""
+        emb = self._require_embedding()
+        emb.fit_scale(states, actions, dtype=self._summary_dtype)
+        if not bool(torch.isfinite(emb.inv_std).all().item()):
+            emb.count.zero_()
+            emb.ready = False
+            raise AssertionError('non-finite value in the trajectories')
+        return self
+
+    def _embedding_scale_of_chunk(self, states, actions):
+        """The scale, where it does not exist yet, from the trajectories both paths of ``fit`` and
+        ``run_training`` use: the first ``min(n_train, 256)`` of the chunk ``states`` starts with (the chunk's
+        last rows are held out).  Nothing is read back: a non-finite trajectory among them makes every
+        summary non-finite, which the summaries' finite flag reports."""
+        emb = self.embedding
+        if emb is None or emb.ready:
+            return
+        if self.model._dp is not None:
+            raise ValueError("a data-parallel model on 'summary_kme' needs the embedding's scale before the fit "
+                             '(every rank would make it from its own first chunk): call fit_embedding_scale, '
+                             'bs.embedding.set_scale or bs.embedding.load_state_dict with the same values on '
+                             'every rank first')
+        n_chunk = BayesSim.get_n_trajs_per_batch(int(states.shape[0]), 0)
+        n_train = _lib.split_rows(n_chunk, BayesSim.TEST_FRACTION)[0]
+        emb.fit_scale(states[:n_train], actions[:n_train], dtype=self._summary_dtype)
 
     def fit_input_norm(self, states, actions):
         """The input statistics of a model built with ``'inputNorm': True`` from the summaries of ALL the
@@ -336,6 +427,7 @@ class BayesSim(object):
         model, n, done, pending = self.model, params.shape[0], 0, []
         model._check_input_norm_dp()
         model._check_rff_bandwidth_dp()
+        self._embedding_scale_of_chunk(traj_states, traj_actions)
         self._check_equal_counts(n)
         on_gpu = torch.is_tensor(traj_states) and traj_states.is_cuda
         flag = torch.zeros(1, dtype=torch.int32, device=traj_states.device) if on_gpu else None

@@ -1,0 +1,211 @@
+"""The random-feature kernel mean embedding of a trajectory's transitions (include/bsig_kme.h, csrc/kme.h): the
+summary ``(1/M) sum_t phi(x_t)`` with random Fourier features ``phi`` of the rows
+``x_t = [tau_t? | s_t | a_t | s_(t+1) - s_t]`` -- ``n_feat`` numbers whatever the task's dimensions and
+length, made from every step.  Not in the reference.
+
+``KernelMeanEmbedding`` holds what the summary depends on beside the trajectories: the frequencies (drawn
+once, from a generator of their own) and the per-column scale ``inv_std`` (made once on the device from sample
+trajectories, or given).  The coefficients the kernel reads, ``freqs * inv_std / (scale sqrt(d))``, follow from
+both on the device; nothing is read back.
+"""
+import math
+import operator
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import _lib
+from . import summarizers as _summ
+
+
+def _flag(value, name):
+    if not isinstance(value, (bool, np.bool_)):
+        raise ValueError('%s must be a bool, got %r' % (name, value))
+    return bool(value)
+
+
+def check_features(n_feat, name='n_feat'):
+    """``n_feat`` as an int: even and >= 2 (a cosine and a sine per frequency); ValueError otherwise."""
+    if isinstance(n_feat, bool):
+        raise ValueError('%s must be an even int >= 2, got %r' % (name, n_feat))
+    try:
+        n = operator.index(n_feat)
+    except TypeError:
+        raise ValueError('%s must be an even int >= 2, got %r' % (name, n_feat)) from None
+    if n < 2 or n % 2 or n > 2 ** 30:
+        raise ValueError('%s must be an even int >= 2, got %r' % (name, n_feat))
+    return n
+
+
+def check_scale(scale, name='scale'):
+    """``scale`` as a float: positive and finite; ValueError otherwise."""
+    if isinstance(scale, bool) or not isinstance(scale, (int, float, np.floating)) or \
+            not (np.isfinite(scale) and scale > 0):
+        raise ValueError('%s must be a positive float, got %r' % (name, scale))
+    return float(scale)
+
+
+class KernelMeanEmbedding(nn.Module):
+    """``emb(states, actions)`` -> ``[N, n_feat]``: ``[a/M sum_t cos z_t | a/M sum_t sin z_t]`` with
+    ``z_t,j = sum_k x_t,k coeff_j,k``, ``a = sqrt(2 / n_feat)``, ``coeff = freqs * inv_std / (scale sqrt(d))``.
+
+    Buffers: ``freqs`` (fp32 ``[n_feat / 2, d]``: ``np.random.RandomState(seed).standard_normal`` rounded to
+    fp32 -- the global numpy and torch generators are not touched -- or the given ``freqs``), ``inv_std``
+    (float64 ``[d]``: the reciprocal standard deviation of every column of ``x``, 0 for a flat column, which then
+    drops out of every ``z``) and ``count`` (int64 scalar: the trajectories the scale was made from, 0: not
+    there yet).  The buffers follow the module to its device and keep their dtypes through ``.float()`` /
+    ``.double()``.  ``ready`` is the host's copy of ``count > 0``: asking costs no read-back.
+
+    ``diff=False`` leaves the state differences out of the rows, ``time=True`` puts the step's position in
+    [0, 1] in front.  ``scale`` multiplies the bandwidth of every column (its standard deviation times
+    ``sqrt(d)``)."""
+    MAX_SCALE_TRAJECTORIES = 256      # fit_scale takes the first ones: their rows are written out for the statistics
+
+    def __init__(self, obs_dim, act_dim, n_feat=256, scale=1.0, seed=0, diff=True, time=False, freqs=None,
+                 device='cpu'):
+        super().__init__()
+        self.n_feat = check_features(n_feat)
+        self.scale = check_scale(scale)
+        self.diff, self.time = _flag(diff, 'diff'), _flag(time, 'time')
+        self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
+        self.row_dim = _summ.kme_row_dim(self.obs_dim, self.act_dim, self.diff, self.time)
+        m, d = self.n_feat // 2, self.row_dim
+        if freqs is None:
+            draw = np.random.RandomState(seed).standard_normal((m, d)).astype(np.float32)
+        else:
+            draw = np.asarray(torch.as_tensor(freqs).detach().cpu().numpy(), dtype=np.float32)
+            if draw.shape != (m, d):
+                raise ValueError('freqs must be [n_feat / 2, d] = [%d, %d], got %r' % (m, d, tuple(draw.shape)))
+        self.seed = seed
+        self.register_buffer('freqs', torch.from_numpy(np.ascontiguousarray(draw)).to(device))
+        self.register_buffer('inv_std', torch.ones(d, dtype=torch.float64, device=device))
+        self.register_buffer('count', torch.zeros((), dtype=torch.int64, device=device))
+        self.ready = False
+        self._coeff = {}                  # itemsize -> the coefficient rows [m, ld] of the current scale
+
+    def _apply(self, fn, *args, **kwargs):
+        # a change of device is followed, a change of dtype is not
+        for name, buf in list(self._buffers.items()):
+            self._buffers[name] = buf.to(fn(buf).device)
+        self._coeff = {}
+        return self
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        if prefix + 'count' in state_dict:
+            self.ready = int(state_dict[prefix + 'count']) > 0
+        self._coeff = {}
+
+    def require_ready(self):
+        if not self.ready:
+            raise RuntimeError('the scale of this kernel mean embedding does not exist yet: BayesSim.fit / '
+                               'run_training make it from their first training trajectories; or call fit_scale '
+                               '/ set_scale / load_state_dict first')
+        return self
+
+    def _on_gpu(self):
+        _lib.require_gpu()
+        if not self.freqs.is_cuda:
+            raise RuntimeError('a KernelMeanEmbedding computes on the GPU: build it with device= a GPU or move '
+                               'it there (no CPU fallback)')
+        return self.freqs.device
+
+    def rows(self, states, actions, dtype=None):
+        """The rows ``x_t`` of the trajectories as ``[N * M, d]`` device rows (bsig_kme_rows): what the scale's
+        statistics are made from; never on the fit path."""
+        prec = _summ._precision(dtype)
+        dev = self._on_gpu()
+        with _lib.on_device(dev):
+            s, a, _ = _summ._prep(states.to(dev), actions.to(dev), prec)
+            n, ts, sd = s.shape
+            assert (sd, a.shape[2]) == (self.obs_dim, self.act_dim), 'trajectories of other dimensions'
+            steps = ts - (1 if self.diff else 0)
+            assert steps >= 1, 'Need %d states or more' % (2 if self.diff else 1)
+            ld = _lib.round_up(self.row_dim, 16 // prec.itemsize)
+            buf = torch.empty((n * steps, ld), dtype=prec.dtype, device=dev)
+            prec.kme_rows(_lib.ptr(s), _lib.ptr(a), _lib.ptr(buf), n, ts, a.shape[1], sd, a.shape[2],
+                          int(self.diff), int(self.time), ld, _lib.stream())
+        return buf[:, :self.row_dim]
+
+    def fit_scale(self, states, actions, dtype=None):
+        """``inv_std`` <- the reciprocal standard deviation of every column of the rows ``x_t`` of the given
+        trajectories (the first MAX_SCALE_TRAJECTORIES at most; bsig_kme_rows, then bsig_input_norm_stats:
+        the flat rule of include/bsig_input_norm.h), in ``dtype`` (fp32 rows by default), frozen from here on.
+        Asynchronous: nothing is read back, ``count`` is written on the stream."""
+        n = min(int(states.shape[0]), self.MAX_SCALE_TRAJECTORIES)
+        assert n >= 1, 'the scale needs at least one trajectory'
+        prec = _summ._precision(dtype)
+        x = self.rows(states[:n], actions[:n], dtype)
+        dev, lib = x.device, _lib.load()
+        with _lib.on_device(dev):
+            need = int(lib.bsig_input_norm_workspace_bytes(x.shape[0], self.row_dim))
+            ws = torch.empty(need // 8, dtype=torch.float64, device=dev)
+            mean = torch.empty(self.row_dim, dtype=torch.float64, device=dev)
+            prec.input_norm_stats(_lib.ptr(x), x.stride(0), x.shape[0], self.row_dim, _lib.ptr(mean),
+                                  _lib.ptr(self.inv_std), _lib.ptr(ws), ws.numel() * 8, _lib.stream())
+            self.count.fill_(n)
+        self.ready = True
+        self._coeff = {}
+        return self
+
+    def set_scale(self, inv_std, count=1):
+        """The host-given form of ``fit_scale``: ``inv_std`` ``[d]``, finite and >= 0 (0: the column drops
+        out).  ``count``: the trajectories behind it where known (any positive number: ready)."""
+        inv = np.asarray(torch.as_tensor(inv_std).detach().cpu().numpy(), dtype=np.float64).reshape(-1)
+        if inv.shape != (self.row_dim,):
+            raise ValueError('set_scale: inv_std must hold %d values' % self.row_dim)
+        if not (np.isfinite(inv).all() and (inv >= 0).all()) or int(count) < 1:
+            raise ValueError('set_scale: inv_std must be finite and >= 0, and count >= 1')
+        self.inv_std.copy_(torch.from_numpy(inv))
+        self.count.fill_(int(count))
+        self.ready = True
+        self._coeff = {}
+        return self
+
+    @property
+    def kappa(self):
+        """1 / (scale sqrt(d)), in double: the factor of every coefficient beside ``inv_std``."""
+        return 1.0 / (self.scale * math.sqrt(float(self.row_dim)))
+
+    def coefficients(self, dtype=None):
+        """The coefficient rows ``[n_feat / 2, d]`` of the current scale in ``dtype`` (bsig_kme_coeff): made on
+        the device on first use, kept until the scale changes."""
+        prec = _summ._precision(dtype)
+        self.require_ready()
+        dev = self._on_gpu()
+        if prec.itemsize not in self._coeff:
+            m, d = self.n_feat // 2, self.row_dim
+            ld = _lib.round_up(d, 16 // prec.itemsize)
+            buf = torch.empty((m, ld), dtype=prec.dtype, device=dev)
+            with _lib.on_device(dev):
+                prec.kme_coeff(_lib.ptr(self.freqs), d, _lib.ptr(self.inv_std), self.kappa, _lib.ptr(buf), ld, m,
+                               d, _lib.stream())
+            self._coeff[prec.itemsize] = buf
+        return self._coeff[prec.itemsize][:, :self.row_dim]
+
+    def forward(self, states, actions, out=None, check_finite=True, dtype=None):
+        """The embedding rows ``[N, n_feat]``.  ``out=``, ``check_finite`` and ``dtype=torch.float64`` are
+        ``cross_correlation``'s.  RuntimeError before the scale exists; NotImplementedError when a block of
+        rows does not fit a workgroup's LDS."""
+        prec = _summ._precision(dtype)
+        self.require_ready()
+        assert len(states.shape) == 3, 'Need states: ntraj x n_steps x state_dim'
+        assert len(actions.shape) == 3, 'Need actions: ntraj x n_steps x state_dim'
+        assert (states.shape[2], actions.shape[2]) == (self.obs_dim, self.act_dim), \
+            'trajectories of other dimensions'
+        steps = states.shape[1] - (1 if self.diff else 0)
+        assert steps >= 1, 'Need %d states or more' % (2 if self.diff else 1)
+        dev = self._on_gpu()
+        home = states.device
+        with _lib.on_device(dev):
+            s, a, _ = _summ._prep(states.to(dev), actions.to(dev), prec)
+            n, ts, sd = s.shape
+            coeff = self.coefficients(dtype)
+            buf, ld = _summ._alloc(n, self.n_feat, dev, out, prec)
+            flag, read_back = _summ._finite_flag(check_finite, dev)
+            prec.kme(_lib.ptr(s), _lib.ptr(a), _lib.ptr(coeff), coeff.stride(0), _lib.ptr(buf), n, ts, a.shape[1],
+                     sd, a.shape[2], self.n_feat // 2, int(self.diff), int(self.time), ld, _lib.ptr(flag),
+                     _lib.stream())
+            _summ._assert_finite(flag, read_back)
+        return _summ._finish(buf, n, self.n_feat, home, out)

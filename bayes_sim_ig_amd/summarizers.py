@@ -320,6 +320,35 @@ def summary_xcorr(states, actions, max_lag=0, state_diff=True, out=None, check_f
     return _finish(buf, n, width, home, out)
 
 
+def kme_row_dim(obs_dim, act_dim, diff=True, time=False):
+    """Width d of a transition row ``[tau? | s | a | ds?]`` of ``summary_kme``: ``2 * obs_dim + act_dim`` with
+    the differences, ``obs_dim + act_dim`` without, one more with the time column -- without touching the GPU
+    (bsig_kme_row_dim, include/bsig_kme.h).  ValueError for a dimension below 1 or a width past 2^31 - 1."""
+    try:
+        sd, ad = operator.index(obs_dim), operator.index(act_dim)
+    except TypeError:
+        raise ValueError('obs_dim and act_dim must be ints >= 1, got %r, %r' % (obs_dim, act_dim)) from None
+    ok = 1 <= sd < 2 ** 31 and 1 <= ad < 2 ** 31
+    d = int(_lib.load().bsig_kme_row_dim(sd, ad, 1 if diff else 0, 1 if time else 0)) if ok else -1
+    if d < 0:
+        raise ValueError('no transition row for obs_dim=%r, act_dim=%r (dimensions >= 1, width below 2^31)'
+                         % (obs_dim, act_dim))
+    return d
+
+
+def summary_kme(states, actions, embedding, out=None, check_finite=True, dtype=None):
+    """The random-feature kernel mean embedding of the trajectories' transitions (not in the reference): with
+    the rows ``x_t = [tau_t? | s_t | a_t | s_(t+1) - s_t]``, M of them, the actions padded as
+    ``pad_states_actions`` leaves them, and ``z_t = coeff x_t``, the row is
+    ``[a/M sum_t cos z_t | a/M sum_t sin z_t]``: ``embedding.n_feat`` numbers from the whole trajectory,
+    whatever its length and dimensions (include/bsig_kme.h, csrc/kme.h).  ``embedding`` is a
+    ``kme.KernelMeanEmbedding``: the frequencies, the per-column scale and the row's layout.
+
+    ``out=``, ``check_finite`` and ``dtype=torch.float64`` are ``cross_correlation``'s.  RuntimeError while the
+    embedding has no scale; NotImplementedError when a block of rows does not fit a workgroup's LDS."""
+    return embedding(states, actions, out=out, check_finite=check_finite, dtype=dtype)
+
+
 def signature_depth(ndim):
     """Reference summarizers.py:133-141."""
     max_output_dim = 110 ** 2
