@@ -14,44 +14,15 @@ import numpy as np
 import torch
 
 from . import _lib
-from . import kme as _kme
 from . import pdf
-from . import summarizers as _summ
 from .mdnn import MDNN
 from .mdrff import MDRFF
+from .summarizer_table import SUMMARIZERS, given as _given
 from .summarizers import (pad_states_actions, summary_start, summary_waypts,  # noqa: F401
                           summary_corr, summary_corrdiff, summary_signatory,
                           signature_depth, cross_correlation, summary_logsignature,
                           summary_xcorr, summary_kme)
 
-_SUMMARIZERS = {
-    'summary_start': summary_start, 'summary_waypts': summary_waypts,
-    'summary_corr': summary_corr, 'summary_corrdiff': summary_corrdiff,
-    'summary_signatory': summary_signatory, 'summary_logsignature': summary_logsignature,
-    'summary_xcorr': summary_xcorr, 'summary_kme': summary_kme,
-}
-_SIGNATURES = ('summary_signatory', 'summary_logsignature')      # take sigDepth and sigChannels
-_KME_KEYS = ('kmeFeatures', 'kmeScale', 'kmeSeed', 'kmeDiff', 'kmeTime')      # 'summary_kme' only
-
-
-def _kme_arguments(model_cfg):
-    """The keys of ``'summarizerFxn': 'summary_kme'`` as KernelMeanEmbedding's arguments; ValueError on a value
-    of the wrong kind."""
-    n_feat = model_cfg.get('kmeFeatures', 256)
-    if isinstance(n_feat, bool) or not isinstance(n_feat, int) or n_feat < 2 or n_feat % 2:
-        raise ValueError("model_cfg['kmeFeatures'] must be an even int >= 2, got %r" % (n_feat,))
-    scale = model_cfg.get('kmeScale', 1.0)
-    if not isinstance(scale, float) or not (np.isfinite(scale) and scale > 0.0):
-        raise ValueError("model_cfg['kmeScale'] must be a positive float, got %r" % (scale,))
-    seed = model_cfg.get('kmeSeed', 0)
-    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 32:
-        raise ValueError("model_cfg['kmeSeed'] must be an int in 0..2^32 - 1, got %r" % (seed,))
-    flags = {}
-    for key, default in (('kmeDiff', True), ('kmeTime', False)):
-        flags[key] = model_cfg.get(key, default)
-        if not isinstance(flags[key], bool):
-            raise ValueError("model_cfg[%r] must be a bool, got %r" % (key, flags[key]))
-    return {'n_feat': n_feat, 'scale': scale, 'seed': seed, 'diff': flags['kmeDiff'], 'time': flags['kmeTime']}
 _MODELS = {'MDNN': MDNN, 'MDRFF': MDRFF}
 
 
@@ -71,128 +42,75 @@ class BayesSim(object):
 
     def __init__(self, model_cfg, obs_dim, act_dim, params_dim, params_lows,
                  params_highs, prior, proposal=None, device='cpu'):
-        """Arguments as in the reference (bayes_sim.py:27-52).  Optional
-        ``model_cfg`` keys beyond the reference's: ``nFeat`` (RFF features,
-        default 200 as hard-coded at bayes_sim.py:81), ``sigDepth`` (1..6: the
-        truncation depth of ``summary_signatory`` and ``summary_logsignature``;
-        default: the reference's rule, at most 3) and ``sigChannels`` (those two
-        summarizers only: the channels
-        of ``[states | actions]`` that make up the path after the time channel,
-        in any order -- index ``c < obs_dim`` is a state channel, any other action
-        channel ``c - obs_dim``; they are gathered by the kernel, the trajectories
-        are not sliced; ``input_dim`` follows from both keys, and a shape whose
-        levels do not fit a workgroup's LDS at ``trainTrajLen`` is a
-        NotImplementedError here, include/bsig_signature.h;
-        ``'summarizerFxn': 'summary_logsignature'`` -- not in the reference -- is the
-        log-signature of the same path at the Lyndon words, ``logsignature_dim``
-        inputs instead of ``signature_dim``, under the same LDS condition,
-        include/bsig_logsignature.h; ``'summarizerFxn': 'summary_xcorr'`` -- not in
-        the reference either -- is the paper's time-lagged cross-correlation of the
-        state differences in time with the actions plus their mean and standard
-        deviation, ``xcorr_dim`` inputs from the whole trajectory, with its own keys
-        ``xcorrLags`` (an int >= 0, default 0: the largest lag, below the number of
-        feature steps of ``trainTrajLen`` states) and ``xcorrStateDiff`` (a bool,
-        default True; False: the states themselves), include/bsig_xcorr.h;
-        ``'summarizerFxn': 'summary_kme'`` -- not in the reference either -- is the
-        random-feature kernel mean embedding of the transitions ``[s_t | a_t |
-        s_(t+1) - s_t]``, ``kmeFeatures`` inputs from every step whatever the task's
-        dimensions and length, with its own keys ``kmeFeatures`` (an even int >= 2,
-        default 256), ``kmeScale`` (a positive float, default 1.0: times each
-        column's standard deviation times sqrt(d) is that column's bandwidth),
-        ``kmeSeed`` (an int >= 0, default 0: the frequencies' own generator),
-        ``kmeDiff`` (a bool, default True; False: no state differences in the rows)
-        and ``kmeTime`` (a bool, default False; True: the step's position leads the
-        row); the per-column scale is made on the device from the first chunk's first
-        training trajectories and kept, with the frequencies, in
-        ``bs.embedding.state_dict()``; include/bsig_kme.h), ``dtype``
-        ('float32', the default, or 'float64': the estimator's fp64 mode, as
-        ``bs.model.double()``), ``summaryDtype`` ('float32', the default in both
-        modes: the summaries are made in fp32 and a double model gets them
-        widened; 'float64', only with ``'dtype': 'float64'``: the summarizers
-        compute in double too, so nothing between the trajectories and the
-        posterior is rounded to fp32), ``inputNorm`` (a bool, default False: the
-        model is built with ``input_norm=True`` and standardises the summaries --
-        per-column mean and standard deviation of the first chunk's training rows,
-        made on the device, kept in ``state_dict`` and applied alike by ``fit``,
-        ``run_training`` and ``predict``; constant columns become zero;
-        include/bsig_input_norm.h.  Meant for ``sigDepth`` >= 3, whose raw terms
-        reach (trainTrajLen - 1)^k / k!), ``rffSigmaScale`` (a positive float,
-        default 1.0, only with ``'modelClass': 'MDRFF_<kernel>_median'``: that model
-        class sets the RFF bandwidth by the median heuristic -- ``rffSigmaScale``
-        times the median pairwise distance of the first chunk's training rows,
-        standardised first under ``inputNorm``, made on the device, kept in
-        ``state_dict``; include/bsig_rff_bandwidth.h)."""
+        """Arguments as in the reference (bayes_sim.py:27-52).  Optional ``model_cfg`` keys beyond the
+        reference's, and values of ``'summarizerFxn'`` that the reference does not have:
+
+        - ``nFeat``: RFF features, default 200 as hard-coded at bayes_sim.py:81.
+        - ``sigDepth``: 1..6, the truncation depth of ``summary_signatory`` and ``summary_logsignature``;
+          default: the reference's rule, at most 3.
+        - ``sigChannels`` (those two summarizers only): the channels of ``[states | actions]`` that make up the
+          path after the time channel, in any order -- index ``c < obs_dim`` is a state channel, any other
+          action channel ``c - obs_dim``; they are gathered by the kernel, the trajectories are not sliced.
+          ``input_dim`` follows from both keys, and a shape whose levels do not fit a workgroup's LDS at
+          ``trainTrajLen`` is a NotImplementedError here; include/bsig_signature.h.
+        - ``'summarizerFxn': 'summary_logsignature'``: the log-signature of the same path at the Lyndon words,
+          ``logsignature_dim`` inputs instead of ``signature_dim``, under the same LDS condition;
+          include/bsig_logsignature.h.
+        - ``'summarizerFxn': 'summary_xcorr'``: the paper's time-lagged cross-correlation of the state
+          differences in time with the actions plus their mean and standard deviation, ``xcorr_dim`` inputs
+          from the whole trajectory; include/bsig_xcorr.h.  Its own keys:
+
+          - ``xcorrLags``: an int >= 0, default 0, the largest lag, below the number of feature steps of
+            ``trainTrajLen`` states;
+          - ``xcorrStateDiff``: a bool, default True; False: the states themselves.
+        - ``'summarizerFxn': 'summary_kme'``: the random-feature kernel mean embedding of the transitions
+          ``[s_t | a_t | s_(t+1) - s_t]``, ``kmeFeatures`` inputs from every step whatever the task's dimensions
+          and length; include/bsig_kme.h.  The per-column scale is made on the device from the first chunk's
+          first training trajectories and kept, with the frequencies, in ``bs.embedding.state_dict()``.  Its
+          own keys:
+
+          - ``kmeFeatures``: an even int >= 2, default 256;
+          - ``kmeScale``: a positive float, default 1.0; times each column's standard deviation times sqrt(d)
+            is that column's bandwidth;
+          - ``kmeSeed``: an int >= 0, default 0, the frequencies' own generator;
+          - ``kmeDiff``: a bool, default True; False: no state differences in the rows;
+          - ``kmeTime``: a bool, default False; True: the step's position leads the row.
+        - ``dtype``: 'float32', the default, or 'float64': the estimator's fp64 mode, as ``bs.model.double()``.
+        - ``summaryDtype``: 'float32', the default in both modes: the summaries are made in fp32 and a double
+          model gets them widened.  'float64', only with ``'dtype': 'float64'``: the summarizers compute in
+          double too, so nothing between the trajectories and the posterior is rounded to fp32.
+        - ``inputNorm``: a bool, default False.  True: the model is built with ``input_norm=True`` and
+          standardises the summaries -- per-column mean and standard deviation of the first chunk's training
+          rows, made on the device, kept in ``state_dict`` and applied alike by ``fit``, ``run_training`` and
+          ``predict``; constant columns become zero; include/bsig_input_norm.h.  Meant for ``sigDepth`` >= 3,
+          whose raw terms reach (trainTrajLen - 1)^k / k!.
+        - ``rffSigmaScale``: a positive float, default 1.0, only with ``'modelClass':
+          'MDRFF_<kernel>_median'``: that model class sets the RFF bandwidth by the median heuristic --
+          ``rffSigmaScale`` times the median pairwise distance of the first chunk's training rows, standardised
+          first under ``inputNorm``, made on the device, kept in ``state_dict``; include/bsig_rff_bandwidth.h.
+
+        ``bs.summary_kwargs`` holds the keyword arguments every summarizer call gets from these keys."""
         self.prior = prior
         self.proposal = proposal
         model_class = model_cfg['modelClass']
         name = model_cfg['summarizerFxn']
-        if name not in _SUMMARIZERS:
+        if name not in SUMMARIZERS:
             raise NameError("name '%s' is not defined" % name)   # eval() in the reference
+        entry = self._summarizer = SUMMARIZERS[name]
         self.summarizer_name = name
-        self.summarizer_fxn = _SUMMARIZERS[name]
-        self._sig_depth = model_cfg.get('sigDepth', None)
-        self._sig_channels = model_cfg.get('sigChannels', None)
-        if self._sig_depth is not None and not 1 <= self._sig_depth <= _lib.SIGNATURE_MAX_DEPTH:
+        self.summarizer_fxn = entry.fxn
+        sig_depth = model_cfg.get('sigDepth', None)        # owned by nobody: range-checked for every name
+        if sig_depth is not None and not 1 <= sig_depth <= _lib.SIGNATURE_MAX_DEPTH:
             raise ValueError("model_cfg['sigDepth'] must be in 1..%d, got %r"
-                             % (_lib.SIGNATURE_MAX_DEPTH, self._sig_depth))
-        if self._sig_channels is not None:
-            if name not in _SIGNATURES:
-                raise ValueError("model_cfg['sigChannels'] applies to 'summary_signatory', not to %r" % name)
-            self._sig_channels = _summ.signature_channels(self._sig_channels, obs_dim, act_dim)
-        self._xcorr_lags = model_cfg.get('xcorrLags', 0)
-        self._xcorr_state_diff = model_cfg.get('xcorrStateDiff', True)
-        for key in ('xcorrLags', 'xcorrStateDiff'):
-            if key in model_cfg and name != 'summary_xcorr':
-                raise ValueError("model_cfg[%r] applies to 'summary_xcorr', not to %r" % (key, name))
-        if isinstance(self._xcorr_lags, bool) or not isinstance(self._xcorr_lags, int) or self._xcorr_lags < 0:
-            raise ValueError("model_cfg['xcorrLags'] must be an int >= 0, got %r" % (self._xcorr_lags,))
-        if not isinstance(self._xcorr_state_diff, bool):
-            raise ValueError("model_cfg['xcorrStateDiff'] must be a bool, got %r" % (self._xcorr_state_diff,))
-        self.embedding = None
-        for key in _KME_KEYS:
-            if key in model_cfg and name != 'summary_kme':
-                raise ValueError("model_cfg[%r] applies to 'summary_kme', not to %r" % (key, name))
+                             % (_lib.SIGNATURE_MAX_DEPTH, sig_depth))
+        for other in SUMMARIZERS.values():
+            for key, owner in other.keys.items():
+                if key not in entry.keys and _given(model_cfg, key):
+                    raise ValueError("model_cfg[%r] applies to %r, not to %r" % (key, owner, name))
         # the reference pushes a zero trajectory through the summarizer to get
         # the width (bayes_sim.py:57-60); the width is a closed form
         itemsize = 8 if model_cfg.get('summaryDtype', 'float32') == 'float64' else 4
-        if name == 'summary_signatory' and (self._sig_channels is not None or (self._sig_depth or 0) > 3):
-            # include/bsig_signature.h: the general kernel; whether it covers the shape is host arithmetic
-            path_dim = 1 + (obs_dim + act_dim if self._sig_channels is None else len(self._sig_channels))
-            depth = self._sig_depth or _summ.signature_depth(path_dim)
-            traj_summaries_dim = _summ.signature_dim(path_dim, depth)
-            _lib.check(_lib.load().bsig_signature_ex_fits(path_dim, model_cfg['trainTrajLen'], depth, itemsize))
-        elif name == 'summary_logsignature':
-            # include/bsig_logsignature.h: the same kernel's LDS at every depth but 1 (level 1 needs none)
-            path_dim = 1 + (obs_dim + act_dim if self._sig_channels is None else len(self._sig_channels))
-            depth = self._sig_depth or _summ.signature_depth(path_dim)
-            traj_summaries_dim = _summ.logsignature_dim(path_dim, depth)
-            if depth > 1:
-                _lib.check(_lib.load().bsig_signature_ex_fits(path_dim, model_cfg['trainTrajLen'], depth, itemsize))
-        elif name == 'summary_xcorr':
-            # include/bsig_xcorr.h: the lags against the feature steps, then the trajectory against the LDS
-            length = model_cfg['trainTrajLen']
-            steps = length - (1 if self._xcorr_state_diff else 0)
-            if self._xcorr_lags > steps - 1:
-                raise ValueError("model_cfg['xcorrLags'] = %d is outside 0..%d: trainTrajLen = %d leaves %d "
-                                 "feature steps" % (self._xcorr_lags, steps - 1, length, steps))
-            traj_summaries_dim = _summ.xcorr_dim(obs_dim, act_dim, self._xcorr_lags)
-            _lib.check(_lib.load().bsig_xcorr_fits(length, length, obs_dim, act_dim, self._xcorr_lags,
-                                                   1 if self._xcorr_state_diff else 0, itemsize))
-        elif name == 'summary_kme':
-            # include/bsig_kme.h: the keys, then a block of rows against the LDS; the module is built once the
-            # model below has made its draws (it has a generator of its own all the same)
-            kme_args = _kme_arguments(model_cfg)
-            traj_summaries_dim = kme_args['n_feat']
-            length = model_cfg['trainTrajLen']
-            if length - (1 if kme_args['diff'] else 0) < 1:
-                raise ValueError("model_cfg['trainTrajLen'] = %d leaves no transition row" % (length,))
-            _summ.kme_row_dim(obs_dim, act_dim, kme_args['diff'], kme_args['time'])
-            _lib.check(_lib.load().bsig_kme_fits(length, length, obs_dim, act_dim, traj_summaries_dim // 2,
-                                                 int(kme_args['diff']), int(kme_args['time']), itemsize))
-        else:
-            traj_summaries_dim = _summ.summary_dim(
-                name, model_cfg['trainTrajLen'], obs_dim, act_dim,
-                self._sig_depth or 0)
+        traj_summaries_dim, self._summary_kwargs = entry.configure(model_cfg, obs_dim, act_dim, itemsize)
         full_covariance = bool(model_cfg.get('fullCovariance', False))
         kwargs = {'input_dim': traj_summaries_dim, 'output_dim': params_dim,
                   'output_lows': params_lows, 'output_highs': params_highs,
@@ -247,8 +165,14 @@ class BayesSim(object):
             self.model.set_matmul_precision(matmul)
         if dtype == 'float64':
             self.model.double()
-        if name == 'summary_kme':
-            self.embedding = _kme.KernelMeanEmbedding(obs_dim, act_dim, device=device, **kme_args)
+        # the summarizer's module, where it has one, is built once the model above has made its draws (it has a
+        # generator of its own all the same)
+        self.embedding = entry.embedding(model_cfg, obs_dim, act_dim, device) if entry.embedding else None
+
+    @property
+    def summary_kwargs(self):
+        """The keyword arguments every call of the summarizer gets from ``model_cfg`` (its ``configure``'s)."""
+        return self._summary_kwargs
 
     @staticmethod
     def get_n_trajs_per_batch(n_train_trajs, n_train_trajs_done):
@@ -258,30 +182,19 @@ class BayesSim(object):
         return n
 
     def _summarize(self, states, actions, finite_flag=None, lazy=False):
+        entry, kw = self._summarizer, dict(self._summary_kwargs)
         # ('summaryDtype': 'float64' -- the summarizers' fp64 kernels; else no keyword: the fp32 path)
-        kw = {} if self._summary_dtype is None else {'dtype': self._summary_dtype}
-        if self.summarizer_name in _SIGNATURES and (self._sig_depth or self._sig_channels is not None):
-            return self.summarizer_fxn(states, actions, depth=self._sig_depth or None,
-                                       channels=self._sig_channels, **kw)
-        if self.summarizer_name in ('summary_corr', 'summary_corrdiff'):
-            if finite_flag is not None:
-                # the isfinite assert of summarizers.py:120, deferred with the chunk's logs
-                kw['check_finite'] = finite_flag
-            # training never needs the outer product itself: the estimator's first layer forms
-            # it from the factor rows (summarizers.CrossCorrFactors)
-            if lazy and self._lazy_summaries():
-                kw['lazy'] = True
-            return self.summarizer_fxn(states, actions, **kw)
-        if self.summarizer_name == 'summary_xcorr':
-            if finite_flag is not None:
-                kw['check_finite'] = finite_flag
-            return self.summarizer_fxn(states, actions, max_lag=self._xcorr_lags,
-                                       state_diff=self._xcorr_state_diff, **kw)
-        if self.summarizer_name == 'summary_kme':
-            if finite_flag is not None:
-                kw['check_finite'] = finite_flag
-            return self.summarizer_fxn(states, actions, self.embedding, **kw)
-        return self.summarizer_fxn(states, actions, **kw)
+        if self._summary_dtype is not None:
+            kw['dtype'] = self._summary_dtype
+        if entry.check_finite and finite_flag is not None:
+            # the isfinite assert of summarizers.py:120, deferred with the chunk's logs
+            kw['check_finite'] = finite_flag
+        # training never needs the outer product itself: the estimator's first layer forms
+        # it from the factor rows (summarizers.CrossCorrFactors)
+        if entry.lazy and lazy and self._lazy_summaries():
+            kw['lazy'] = True
+        args = (states, actions) if entry.embedding is None else (states, actions, self.embedding)
+        return self.summarizer_fxn(*args, **kw)
 
     def _lazy_summaries(self):
         # (a double model takes summary rows only: materialised by the summarizer kernels -- in fp32 and
@@ -318,27 +231,36 @@ class BayesSim(object):
         trajectories), frozen from here on.  Synchronises, and asserts that the scale is finite."""
         emb = self._require_embedding()
         emb.fit_scale(states, actions, dtype=self._summary_dtype)
-        if not bool(torch.isfinite(emb.inv_std).all().item()):
-            emb.count.zero_()
-            emb.ready = False
-            raise AssertionError('non-finite value in the trajectories')
+        return self._keep_if_finite(emb, (emb.inv_std,), 'non-finite value in the trajectories')
+
+    def _keep_if_finite(self, stat, values, message):
+        """The end of every ``fit_*`` below: one read-back of whether the ``values`` just made for the frozen
+        statistic ``stat`` are all finite; if not, ``stat`` is back to "not there yet" and ``message`` is an
+        AssertionError."""
+        finite = torch.isfinite(values[0]).all()
+        for value in values[1:]:
+            finite = finite & torch.isfinite(value).all()
+        if not bool(finite.item()):
+            stat.reset()
+            raise AssertionError(message)
         return self
+
+    @staticmethod
+    def _first_training_rows(n, done=0):
+        """How many rows of the chunk that starts at pair ``done`` of ``n`` are training rows (the chunk's last
+        rows are held out): what a statistic that does not exist yet is made from, on every path."""
+        return _lib.split_rows(BayesSim.get_n_trajs_per_batch(n, done), BayesSim.TEST_FRACTION)[0]
 
     def _embedding_scale_of_chunk(self, states, actions):
         """The scale, where it does not exist yet, from the trajectories both paths of ``fit`` and
-        ``run_training`` use: the first ``min(n_train, 256)`` of the chunk ``states`` starts with (the chunk's
-        last rows are held out).  Nothing is read back: a non-finite trajectory among them makes every
-        summary non-finite, which the summaries' finite flag reports."""
+        ``run_training`` use: the first ``min(n_train, 256)`` of the chunk ``states`` starts with.  Nothing is
+        read back: a non-finite trajectory among them makes every summary non-finite, which the summaries'
+        finite flag reports."""
         emb = self.embedding
         if emb is None or emb.ready:
             return
-        if self.model._dp is not None:
-            raise ValueError("a data-parallel model on 'summary_kme' needs the embedding's scale before the fit "
-                             '(every rank would make it from its own first chunk): call fit_embedding_scale, '
-                             'bs.embedding.set_scale or bs.embedding.load_state_dict with the same values on '
-                             'every rank first')
-        n_chunk = BayesSim.get_n_trajs_per_batch(int(states.shape[0]), 0)
-        n_train = _lib.split_rows(n_chunk, BayesSim.TEST_FRACTION)[0]
+        emb.refuse_data_parallel(self.model._dp)
+        n_train = self._first_training_rows(int(states.shape[0]))
         emb.fit_scale(states[:n_train], actions[:n_train], dtype=self._summary_dtype)
 
     def fit_input_norm(self, states, actions):
@@ -347,11 +269,7 @@ class BayesSim(object):
         Synchronises, and asserts that the statistics are finite."""
         norm = self.model._require_inorm()
         self.model.fit_input_norm(self._summarize(states, actions))
-        if not bool((torch.isfinite(norm.mean).all() & torch.isfinite(norm.inv_std).all()).item()):
-            norm.count.zero_()
-            norm.ready = False
-            raise AssertionError('non-finite value in the trajectory summaries')
-        return self
+        return self._keep_if_finite(norm, (norm.mean, norm.inv_std), 'non-finite value in the trajectory summaries')
 
     def fit_rff_bandwidth(self, states, actions):
         """The counterpart of ``fit_input_norm`` for the bandwidth of an ``'MDRFF_<kernel>_median'`` model: from
@@ -360,20 +278,16 @@ class BayesSim(object):
         asserts that the bandwidth is finite."""
         bw = self.model._require_rffbw()
         self.model.fit_rff_bandwidth(self._summarize(states, actions))
-        if not bool(torch.isfinite(bw.sigma).item()):
-            bw.count.zero_()
-            bw.ready = False
-            raise AssertionError('non-finite value in the trajectory summaries')
-        return self
+        return self._keep_if_finite(bw, (bw.sigma,), 'non-finite value in the trajectory summaries')
 
-    def _standardize_block(self, summ, n_first):
+    def _standardize_block(self, summ, n_train):
         """fit()'s block path for a model with input_norm: the statistics, where they do not exist yet, from
-        the rows the chunk loop would have used -- the training rows of the first chunk, ``n_first`` pairs --
-        then the block standardised in place, once, in the model's precision.  Nothing is read back."""
+        the rows the chunk loop would have used -- the ``n_train`` training rows of the first chunk -- then the
+        block standardised in place, once, in the model's precision.  Nothing is read back."""
         model = self.model
         summ, ld, prec = model._input_rows(summ, model._prec.dtype)
         if not model.input_norm_ready:
-            model._stats_of(summ, ld, _lib.split_rows(n_first, BayesSim.TEST_FRACTION)[0], prec)
+            model._stats_of(summ, ld, n_train, prec)
         return model.normalize_inputs(summ, out=summ)
 
     FIT_BLOCK_BYTES = 4 << 30        # (not in the reference) bound on a block's summaries in fit()
@@ -425,8 +339,7 @@ class BayesSim(object):
         An ``'MDRFF_<kernel>_median'`` model: the bandwidth is made from the first block, after that and
         before the projection."""
         model, n, done, pending = self.model, params.shape[0], 0, []
-        model._check_input_norm_dp()
-        model._check_rff_bandwidth_dp()
+        model._check_statistics_dp()
         self._embedding_scale_of_chunk(traj_states, traj_actions)
         self._check_equal_counts(n)
         on_gpu = torch.is_tensor(traj_states) and traj_states.is_cuda
@@ -439,12 +352,11 @@ class BayesSim(object):
                 lo, hi = done, min(n, done + block)
                 summ = self._summarize(traj_states[lo:hi], traj_actions[lo:hi], flag, lazy=True)
                 if model._inorm is not None:
-                    summ = self._standardize_block(summ, BayesSim.get_n_trajs_per_batch(n, lo))
+                    summ = self._standardize_block(summ, self._first_training_rows(n, lo))
                 if model._rffbw is not None and not model.rff_bandwidth_ready:
                     # the bandwidth of the rows the chunk loop would have used: the first chunk's training
                     # rows, as the projection sees them; nothing is read back
-                    n_first = _lib.split_rows(BayesSim.get_n_trajs_per_batch(n, lo), BayesSim.TEST_FRACTION)[0]
-                    model._bandwidth_of_rows(summ[:n_first])
+                    model._bandwidth_of_rows(summ[:self._first_training_rows(n, lo)])
                 # (a double MDRFF projects in double inside each call: chunk by chunk, no block launch)
                 feats = model.rff.to_features(summ) if model.rff is not None and not model._f64 else None
                 sizes = self._block_launch_sizes(n, lo, hi) if feats is not None and model._dp is None else []

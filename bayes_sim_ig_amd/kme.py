@@ -13,10 +13,10 @@ import operator
 
 import numpy as np
 import torch
-from torch import nn
 
 from . import _lib
 from . import summarizers as _summ
+from .frozen import FrozenStatistic, column_statistics
 
 
 def _flag(value, name):
@@ -46,63 +46,51 @@ def check_scale(scale, name='scale'):
     return float(scale)
 
 
-class KernelMeanEmbedding(nn.Module):
+class KernelMeanEmbedding(FrozenStatistic):
     """``emb(states, actions)`` -> ``[N, n_feat]``: ``[a/M sum_t cos z_t | a/M sum_t sin z_t]`` with
     ``z_t,j = sum_k x_t,k coeff_j,k``, ``a = sqrt(2 / n_feat)``, ``coeff = freqs * inv_std / (scale sqrt(d))``.
 
     Buffers: ``freqs`` (fp32 ``[n_feat / 2, d]``: ``np.random.RandomState(seed).standard_normal`` rounded to
     fp32 -- the global numpy and torch generators are not touched -- or the given ``freqs``), ``inv_std``
     (float64 ``[d]``: the reciprocal standard deviation of every column of ``x``, 0 for a flat column, which then
-    drops out of every ``z``) and ``count`` (int64 scalar: the trajectories the scale was made from, 0: not
-    there yet).  The buffers follow the module to its device and keep their dtypes through ``.float()`` /
-    ``.double()``.  ``ready`` is the host's copy of ``count > 0``: asking costs no read-back.
+    drops out of every ``z``) and ``count`` (the trajectories the scale was made from).  Device, dtypes and
+    ``ready`` are FrozenStatistic's.
 
     ``diff=False`` leaves the state differences out of the rows, ``time=True`` puts the step's position in
     [0, 1] in front.  ``scale`` multiplies the bandwidth of every column (its standard deviation times
     ``sqrt(d)``)."""
     MAX_SCALE_TRAJECTORIES = 256      # fit_scale takes the first ones: their rows are written out for the statistics
+    NOT_READY = ('the scale of this kernel mean embedding does not exist yet: BayesSim.fit / '
+                 'run_training make it from their first training trajectories; or call fit_scale '
+                 '/ set_scale / load_state_dict first')
+    NOT_READY_PARALLEL = ("a data-parallel model on 'summary_kme' needs the embedding's scale before the fit "
+                          '(every rank would make it from its own first chunk): call fit_embedding_scale, '
+                          'bs.embedding.set_scale or bs.embedding.load_state_dict with the same values on '
+                          'every rank first')
 
     def __init__(self, obs_dim, act_dim, n_feat=256, scale=1.0, seed=0, diff=True, time=False, freqs=None,
                  device='cpu'):
-        super().__init__()
-        self.n_feat = check_features(n_feat)
-        self.scale = check_scale(scale)
-        self.diff, self.time = _flag(diff, 'diff'), _flag(time, 'time')
-        self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
-        self.row_dim = _summ.kme_row_dim(self.obs_dim, self.act_dim, self.diff, self.time)
-        m, d = self.n_feat // 2, self.row_dim
+        n_feat, scale = check_features(n_feat), check_scale(scale)
+        diff, time = _flag(diff, 'diff'), _flag(time, 'time')
+        m, d = n_feat // 2, _summ.kme_row_dim(int(obs_dim), int(act_dim), diff, time)
         if freqs is None:
             draw = np.random.RandomState(seed).standard_normal((m, d)).astype(np.float32)
         else:
             draw = np.asarray(torch.as_tensor(freqs).detach().cpu().numpy(), dtype=np.float32)
             if draw.shape != (m, d):
                 raise ValueError('freqs must be [n_feat / 2, d] = [%d, %d], got %r' % (m, d, tuple(draw.shape)))
-        self.seed = seed
-        self.register_buffer('freqs', torch.from_numpy(np.ascontiguousarray(draw)).to(device))
-        self.register_buffer('inv_std', torch.ones(d, dtype=torch.float64, device=device))
-        self.register_buffer('count', torch.zeros((), dtype=torch.int64, device=device))
-        self.ready = False
+        super().__init__(device, freqs=torch.from_numpy(np.ascontiguousarray(draw)),
+                         inv_std=torch.ones(d, dtype=torch.float64))
+        self.n_feat, self.scale, self.seed, self.diff, self.time = n_feat, scale, seed, diff, time
+        self.obs_dim, self.act_dim, self.row_dim = int(obs_dim), int(act_dim), d
         self._coeff = {}                  # itemsize -> the coefficient rows [m, ld] of the current scale
 
     def _apply(self, fn, *args, **kwargs):
-        # a change of device is followed, a change of dtype is not
-        for name, buf in list(self._buffers.items()):
-            self._buffers[name] = buf.to(fn(buf).device)
         self._coeff = {}
-        return self
+        return super()._apply(fn, *args, **kwargs)
 
-    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
-        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
-        if prefix + 'count' in state_dict:
-            self.ready = int(state_dict[prefix + 'count']) > 0
+    def _value_changed(self):
         self._coeff = {}
-
-    def require_ready(self):
-        if not self.ready:
-            raise RuntimeError('the scale of this kernel mean embedding does not exist yet: BayesSim.fit / '
-                               'run_training make it from their first training trajectories; or call fit_scale '
-                               '/ set_scale / load_state_dict first')
-        return self
 
     def _on_gpu(self):
         _lib.require_gpu()
@@ -137,16 +125,12 @@ class KernelMeanEmbedding(nn.Module):
         assert n >= 1, 'the scale needs at least one trajectory'
         prec = _summ._precision(dtype)
         x = self.rows(states[:n], actions[:n], dtype)
-        dev, lib = x.device, _lib.load()
+        dev = x.device
         with _lib.on_device(dev):
-            need = int(lib.bsig_input_norm_workspace_bytes(x.shape[0], self.row_dim))
-            ws = torch.empty(need // 8, dtype=torch.float64, device=dev)
             mean = torch.empty(self.row_dim, dtype=torch.float64, device=dev)
-            prec.input_norm_stats(_lib.ptr(x), x.stride(0), x.shape[0], self.row_dim, _lib.ptr(mean),
-                                  _lib.ptr(self.inv_std), _lib.ptr(ws), ws.numel() * 8, _lib.stream())
-            self.count.fill_(n)
-        self.ready = True
-        self._coeff = {}
+            column_statistics(prec, x, x.stride(0), x.shape[0], self.row_dim, mean, self.inv_std,
+                              lambda numel: torch.empty(numel, dtype=torch.float64, device=dev))
+            self.made_from(n)
         return self
 
     def set_scale(self, inv_std, count=1):
@@ -158,9 +142,7 @@ class KernelMeanEmbedding(nn.Module):
         if not (np.isfinite(inv).all() and (inv >= 0).all()) or int(count) < 1:
             raise ValueError('set_scale: inv_std must be finite and >= 0, and count >= 1')
         self.inv_std.copy_(torch.from_numpy(inv))
-        self.count.fill_(int(count))
-        self.ready = True
-        self._coeff = {}
+        self.made_from(int(count))
         return self
 
     @property

@@ -41,6 +41,7 @@ import torch.nn as nn
 from . import _lib
 from . import pdf
 from . import dp as _dp
+from .frozen import FrozenStatistic, column_statistics
 from .protocol import eval_updates, split_rows
 from .summarizers import CrossCorrFactors
 
@@ -150,56 +151,42 @@ def _flat_rule(mean, std, dtype):
         return np.where(flat, 0.0, 1.0 / np.where(flat, 1.0, std))
 
 
-class InputNorm(nn.Module):
+class InputNorm(FrozenStatistic):
     """The statistics of a model built with ``input_norm=True``: ``mean`` and ``inv_std`` (float64
-    [input_dim]: include/bsig_input_norm.h) and ``count`` (int64 scalar: the number of rows they were made
-    from, 0: not there yet).  The buffers follow the model to its device and keep their dtypes through
-    ``.float()`` / ``.double()``.  ``ready`` is the host's copy of ``count > 0``: asking costs no read-back."""
+    [input_dim]: include/bsig_input_norm.h) and ``count`` (the number of rows they were made from).  Device,
+    dtypes and ``ready`` are FrozenStatistic's."""
+    NOT_READY = ('the input statistics of this model do not exist yet: run_training makes them '
+                 'from its first training rows; or call fit_input_norm / set_input_norm / '
+                 'load_state_dict first')
+    NOT_READY_PARALLEL = ('a data-parallel model with input_norm needs its input statistics before '
+                          'run_training (every rank would fit them on its own first chunk): call '
+                          'fit_input_norm or set_input_norm with the same values on every rank first')
 
     def __init__(self, width, device):
-        super().__init__()
+        super().__init__(device, mean=torch.zeros(int(width), dtype=torch.float64),
+                         inv_std=torch.ones(int(width), dtype=torch.float64))
         self.width = int(width)
-        self.register_buffer('mean', torch.zeros(self.width, dtype=torch.float64, device=device))
-        self.register_buffer('inv_std', torch.ones(self.width, dtype=torch.float64, device=device))
-        self.register_buffer('count', torch.zeros((), dtype=torch.int64, device=device))
-        self.ready = False
-
-    def _apply(self, fn, *args, **kwargs):
-        # a change of device is followed, a change of dtype is not
-        for name, buf in list(self._buffers.items()):
-            self._buffers[name] = buf.to(fn(buf).device)
-        return self
-
-    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
-        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
-        if prefix + 'count' in state_dict:
-            self.ready = int(state_dict[prefix + 'count']) > 0
 
 
-class RffBandwidth(InputNorm):
+class RffBandwidth(FrozenStatistic):
     """The bandwidth of an ``MDRFF(sigma='median')``: ``sigma`` (float64 scalar: ``scale`` times the median
-    pairwise distance of the rows it was made from, include/bsig_rff_bandwidth.h) and ``count`` (int64 scalar:
-    the number of those rows, 0: not there yet).  Device, dtypes and ``ready`` as InputNorm's.  ``version``
-    counts the times the value was given: what was derived from an earlier one (freqs / sigma) is stale."""
+    pairwise distance of the rows it was made from, include/bsig_rff_bandwidth.h) and ``count`` (the number of
+    those rows).  Device, dtypes and ``ready`` are FrozenStatistic's.  ``version`` counts the times the value
+    was given or loaded: what was derived from an earlier one (freqs / sigma) is stale."""
+    NOT_READY = ("the kernel bandwidth of this model (sigma='median') does not exist yet: "
+                 'run_training / BayesSim.fit make it from their first training rows; or call '
+                 'fit_rff_bandwidth / set_rff_bandwidth / load_state_dict first')
+    NOT_READY_PARALLEL = ("a data-parallel model with sigma='median' needs its bandwidth before run_training "
+                          '(every rank would fit it on its own first chunk): call fit_rff_bandwidth or '
+                          'set_rff_bandwidth with the same value on every rank first')
 
     def __init__(self, scale, device):
-        nn.Module.__init__(self)
+        super().__init__(device, sigma=torch.ones((), dtype=torch.float64))
         self.scale = float(scale)
-        self.register_buffer('sigma', torch.ones((), dtype=torch.float64, device=device))
-        self.register_buffer('count', torch.zeros((), dtype=torch.int64, device=device))
-        self.ready = False
         self.version = 0
 
-    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
-        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+    def _value_changed(self):
         self.version += 1
-
-    def require_ready(self):
-        if not self.ready:
-            raise RuntimeError("the kernel bandwidth of this model (sigma='median') does not exist yet: "
-                               'run_training / BayesSim.fit make it from their first training rows; or call '
-                               'fit_rff_bandwidth / set_rff_bandwidth / load_state_dict first')
-        return self
 
 
 class MDNN(nn.Module):
@@ -557,23 +544,30 @@ class MDNN(nn.Module):
         norm = self._inorm
         if norm is None:
             raise RuntimeError('this model was built without input_norm=True')
-        if ready and not norm.ready:
-            raise RuntimeError('the input statistics of this model do not exist yet: run_training makes them '
-                               'from its first training rows; or call fit_input_norm / set_input_norm / '
-                               'load_state_dict first')
-        return norm
+        return norm.require_ready() if ready else norm
+
+    def _require_statistics(self, bandwidth=True):
+        """RuntimeError while a statistic this model standardises or projects by does not exist yet
+        (``bandwidth=False``: the bandwidth is about to be made)."""
+        for stat in (self._inorm, self._rffbw if bandwidth else None):
+            if stat is not None:
+                stat.require_ready()
+
+    def _check_statistics_dp(self, input_norm=True):
+        """ValueError, before anything is enqueued, where this call would make a statistic under data parallel
+        (``input_norm=False``: the rows come standardised)."""
+        for stat in (self._inorm if input_norm else None, self._rffbw):
+            if stat is not None:
+                stat.refuse_data_parallel(self._dp)
 
     def _stats_of(self, xs, ld, n, prec):
         """mean / inv_std <- the statistics of the first ``n`` rows of ``xs`` (a device tensor of
         ``prec``'s dtype), frozen from here on.  Asynchronous: ``count`` is written on the stream."""
-        lib, norm = self._gpu(), self._inorm
-        need = int(lib.bsig_input_norm_workspace_bytes(n, norm.width))
-        assert need > 0, 'input statistics need at least one row'
-        ws = self._buf('inorm_ws', need // 8, torch.float64)
-        prec.input_norm_stats(_lib.ptr(xs), ld, n, norm.width, _lib.ptr(norm.mean), _lib.ptr(norm.inv_std),
-                              _lib.ptr(ws), ws.numel() * 8, _lib.stream())
-        norm.count.fill_(n)
-        norm.ready = True
+        self._gpu()
+        norm = self._inorm
+        column_statistics(prec, xs, ld, n, norm.width, norm.mean, norm.inv_std,
+                          lambda numel: self._buf('inorm_ws', numel, torch.float64))
+        norm.made_from(n)
 
     def _input_rows(self, x, dtype=None):
         """``x`` as device rows of ``dtype`` (default: its own where that is fp32 or fp64, else fp32)."""
@@ -610,8 +604,7 @@ class MDNN(nn.Module):
         inv = _flat_rule(mean, std, dtype or self._dtype)
         norm.mean.copy_(torch.from_numpy(mean))
         norm.inv_std.copy_(torch.from_numpy(inv))
-        norm.count.fill_(int(count))
-        norm.ready = True
+        norm.made_from(int(count))
         return self
 
     @_on_model_device
@@ -630,12 +623,6 @@ class MDNN(nn.Module):
         prec.input_norm_apply(_lib.ptr(xs), ld, _lib.ptr(norm.mean), _lib.ptr(norm.inv_std), _lib.ptr(out),
                               ld_out, xs.shape[0], norm.width, _lib.stream())
         return out
-
-    def _check_input_norm_dp(self):
-        if self._inorm is not None and not self._inorm.ready and self._dp is not None:
-            raise ValueError('a data-parallel model with input_norm needs its input statistics before '
-                             'run_training (every rank would fit them on its own first chunk): call '
-                             'fit_input_norm or set_input_norm with the same values on every rank first')
 
     def _standardised(self, x):
         """Fresh rows of the model's precision: ``x`` standardised (the model has ready statistics)."""
@@ -670,9 +657,7 @@ class MDNN(nn.Module):
         ws = self._buf('rffbw_ws', need // 8, torch.float64)
         prec.rff_bandwidth_median(_lib.ptr(xs), ld, n, self.input_dim, bw.scale, _lib.ptr(bw.sigma), _lib.ptr(ws),
                                   ws.numel() * 8, _lib.stream())
-        bw.count.fill_(min(n, _lib.RFF_BANDWIDTH_MAX_ROWS))
-        bw.ready = True
-        bw.version += 1
+        bw.made_from(min(n, _lib.RFF_BANDWIDTH_MAX_ROWS))
 
     def _bandwidth_of_rows(self, x):
         """``_bandwidth_of`` all rows of ``x`` (fp32 or double; anything else as fp32), taken in their own type:
@@ -688,8 +673,7 @@ class MDNN(nn.Module):
         device and freeze it: no later call refits.  A model with ``input_norm`` standardises the rows first,
         in its own precision (RuntimeError while it has no statistics)."""
         self._require_rffbw()
-        if self._inorm is not None:
-            self._require_inorm(ready=True)
+        self._require_statistics(bandwidth=False)
         self._gpu()
         if hasattr(x, 'materialize'):
             x = x.materialize()
@@ -705,16 +689,8 @@ class MDNN(nn.Module):
         if not (np.isfinite(sigma) and sigma > 0.0):
             raise ValueError('set_rff_bandwidth: sigma must be a positive finite number, got %r' % (sigma,))
         bw.sigma.fill_(sigma)
-        bw.count.fill_(1)
-        bw.ready = True
-        bw.version += 1
+        bw.made_from(1)
         return self
-
-    def _check_rff_bandwidth_dp(self):
-        if self._rffbw is not None and not self._rffbw.ready and self._dp is not None:
-            raise ValueError("a data-parallel model with sigma='median' needs its bandwidth before run_training "
-                             '(every rank would fit it on its own first chunk): call fit_rff_bandwidth or '
-                             'set_rff_bandwidth with the same value on every rank first')
 
     # ----------------------------------------------------------- forward
     @_on_model_device
@@ -746,10 +722,8 @@ class MDNN(nn.Module):
         first (RuntimeError while it has no statistics; likewise an ``MDRFF(sigma='median')`` without its
         bandwidth)."""
         norm = self._inorm if not _is_feat else None
-        if norm is not None:
-            self._require_inorm(ready=True)
-        if self._rffbw is not None and not _is_feat:
-            self._rffbw.require_ready()
+        if not _is_feat:
+            self._require_statistics()
         self._gpu()
         prec = self._prec
         cfg, out = self._head_forward(x if norm is None else self._standardised(x), _is_feat)
@@ -812,10 +786,7 @@ class MDNN(nn.Module):
         (mdnn.py:229-233): returns the 0-dim loss; gradients land in every
         parameter's ``.grad`` (views of the flat gradient buffer).  ``y`` is
         already normalised; ``x`` is not standardised yet (a model with ``input_norm`` does that here)."""
-        if self._inorm is not None:
-            self._require_inorm(ready=True)
-        if self._rffbw is not None:
-            self._rffbw.require_ready()
+        self._require_statistics()
         self._gpu()
         prec = self._prec
         cfg = self._cfg()
@@ -893,9 +864,7 @@ class MDNN(nn.Module):
         staged training rows, standardised where the model does that, before anything is projected; under
         ``enable_data_parallel`` that is the same ValueError."""
         self._check_f64_dp()
-        if not _standardized:
-            self._check_input_norm_dp()
-        self._check_rff_bandwidth_dp()
+        self._check_statistics_dp(input_norm=not _standardized)
 
         def once():
             return self._run_training_once(x_data, y_data, n_updates, batch_size, test_frac,
@@ -1212,10 +1181,7 @@ class MDNN(nn.Module):
         instead of ``L[pt, :, comp_id]``) is not reproduced.  A model with ``input_norm`` standardises
         ``xs`` first (before an MDRFF's projection)."""
         ntest, dim = xs.size()
-        if self._inorm is not None:
-            self._require_inorm(ready=True)
-        if self._rffbw is not None:
-            self._rffbw.require_ready()
+        self._require_statistics()
         if self.rff is not None and self._matmul != 'float32':
             # the projection follows the model's matmul precision; the head products stay fp32
             feats = self.rff.to_features(xs if self._inorm is None else self._standardised(xs))

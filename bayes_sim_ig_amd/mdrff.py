@@ -98,7 +98,7 @@ class MDRFF(MDNN):
         the global numpy RNG (rff.py:111-120), which ranks may have seeded differently, and
         are not part of the flat parameter buffer -- rank 0's are broadcast."""
         rff = self.rff
-        # (a median bandwidth is not broadcast: _check_rff_bandwidth_dp asks for the same value on every rank)
+        # (a median bandwidth is not broadcast: _check_statistics_dp asks for the same value on every rank)
         for name in ('freqs', 'offset') if self._rffbw is not None else ('freqs', 'sigma', 'offset'):
             t = getattr(rff, name)
             if t is None:

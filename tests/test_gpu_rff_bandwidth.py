@@ -355,8 +355,10 @@ def test_fit_reports_non_finite_rows(B):
     theta, states, actions = _sim_pairs()
     bad = states.clone()
     bad[3, 0, 1] = NAN
+    bs = _sim(B)
     with pytest.raises(AssertionError):
-        _sim(B).fit_rff_bandwidth(bad, actions)
+        bs.fit_rff_bandwidth(bad, actions)
+    assert not bs.model.rff_bandwidth_ready and int(bs.model.rff_bandwidth.count) == 0
     with pytest.raises(AssertionError):
         _sim(B).fit(theta, bad, actions)
 

@@ -136,7 +136,7 @@ def test_python_refuses_a_bad_channel_list_or_depth_before_it_asks_for_a_gpu(dty
 def test_bayessim_sizes_its_first_layer_by_the_log_signature():
     pend = dict(obs_dim=3, act_dim=1, **KW)
     bs = B.BayesSim(model_cfg=dict(CFG, sigDepth=4, sigChannels=[0, 1, 3]), **pend)
-    assert bs.model.input_dim == 90 == LC.witt(4, 4) and bs._sig_channels == (0, 1, 3)
+    assert bs.model.input_dim == 90 == LC.witt(4, 4) and bs.summary_kwargs['channels'] == (0, 1, 3)
     assert bs.summarizer_fxn is B.summary_logsignature
     assert B.BayesSim(model_cfg=dict(CFG, sigDepth=5), **pend).model.input_dim == LC.witt(5, 5) == 829
     assert B.BayesSim(model_cfg=CFG, **pend).model.input_dim == LC.witt(5, 3) == 55           # default depth 3

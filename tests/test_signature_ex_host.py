@@ -130,7 +130,7 @@ def test_bayessim_takes_sig_depth_and_sig_channels():
     picked = [0, 210, 211, 230] + list(range(5, 22))
     assert len(picked) == 21
     hand = B.BayesSim(model_cfg=dict(CFG, sigChannels=picked, sigDepth=3), obs_dim=211, act_dim=20, **KW)
-    assert hand.model.input_dim == 11154 and hand._sig_channels == tuple(picked)
+    assert hand.model.input_dim == 11154 and hand.summary_kwargs['channels'] == tuple(picked)
     assert B.BayesSim(model_cfg=dict(CFG, sigChannels=picked), obs_dim=211, act_dim=20, **KW).model.input_dim == 11154
     pend = dict(obs_dim=3, act_dim=1, **KW)
     assert B.BayesSim(model_cfg=dict(CFG, sigDepth=4, sigChannels=[0, 1, 3]), **pend).model.input_dim == 340

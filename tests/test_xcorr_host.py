@@ -215,7 +215,8 @@ def test_bayessim_sizes_its_first_layer_by_xcorr_dim():
     assert _bayes_sim(dict(CFG, trainTrajLen=50, xcorrLags=1), obs_dim=211, act_dim=20).model.input_dim == 8862
     bs = _bayes_sim(dict(CFG, xcorrLags=19))
     assert bs.model.input_dim == 66 and bs.summarizer_fxn is B.summary_xcorr
-    assert bs.summarizer_name == 'summary_xcorr' and bs._xcorr_lags == 19 and bs._xcorr_state_diff is True
+    assert bs.summarizer_name == 'summary_xcorr' and bs.summary_kwargs['max_lag'] == 19
+    assert bs.summary_kwargs['state_diff'] is True
     assert 'summary_xcorr' not in bs.model.state_dict() and not any('xcorr' in k for k in bs.model.state_dict())
 
 
