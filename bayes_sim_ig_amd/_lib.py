@@ -296,6 +296,15 @@ HEADERS['bsig_kme.h'] = {
     'bsig_kme': (C.c_int, [vp, vp, vp, i64, vp, i64] + [C.c_int] * 7 + [i64, vp, vp]),
     'bsig_kme_f64': (C.c_int, [vp, vp, vp, i64, vp, i64] + [C.c_int] * 7 + [i64, vp, vp]),
 }
+# per-trajectory lengths for the two summaries above: the lengths (and the rows' offsets) follow the trajectories
+HEADERS['bsig_ragged.h'] = {
+    'bsig_xcorr_ragged': (C.c_int, [vp, vp, vp, vp, i64] + [C.c_int] * 6 + [i64, vp, vp]),
+    'bsig_xcorr_ragged_f64': (C.c_int, [vp, vp, vp, vp, i64] + [C.c_int] * 6 + [i64, vp, vp]),
+    'bsig_kme_ragged': (C.c_int, [vp, vp, vp, vp, i64, vp, i64] + [C.c_int] * 7 + [i64, vp, vp]),
+    'bsig_kme_ragged_f64': (C.c_int, [vp, vp, vp, vp, i64, vp, i64] + [C.c_int] * 7 + [i64, vp, vp]),
+    'bsig_kme_rows_ragged': (C.c_int, [vp, vp, vp, vp, vp, i64] + [C.c_int] * 6 + [i64, vp]),
+    'bsig_kme_rows_ragged_f64': (C.c_int, [vp, vp, vp, vp, vp, i64] + [C.c_int] * 6 + [i64, vp]),
+}
 COMM_ID_BYTES = 128
 EXCHANGE_SUM, EXCHANGE_BROADCAST = 0, 1
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int, vp, i64, C.c_int, vp)
@@ -436,6 +445,10 @@ class Precision:
         'kme': ('bsig_kme', 'bsig_kme_f64'),
         'kme_rows': ('bsig_kme_rows', 'bsig_kme_rows_f64'),
         'kme_coeff': ('bsig_kme_coeff', 'bsig_kme_coeff_f64'),
+        # both summaries, and the embedding's rows, with a length per trajectory (include/bsig_ragged.h)
+        'xcorr_ragged': ('bsig_xcorr_ragged', 'bsig_xcorr_ragged_f64'),
+        'kme_ragged': ('bsig_kme_ragged', 'bsig_kme_ragged_f64'),
+        'kme_rows_ragged': ('bsig_kme_rows_ragged', 'bsig_kme_rows_ragged_f64'),
         # the input-side companions of normalize_rows / copy_rows (the statistics of rows, and the copy that
         # standardises)
         'input_norm_stats': ('bsig_input_norm_stats', 'bsig_input_norm_stats_f64'),

@@ -18,6 +18,7 @@ from . import pdf
 from .mdnn import MDNN
 from .mdrff import MDRFF
 from .summarizer_table import SUMMARIZERS, given as _given
+from .summarizers import check_lengths as _check_lengths
 from .summarizers import (pad_states_actions, summary_start, summary_waypts,  # noqa: F401
                           summary_corr, summary_corrdiff, summary_signatory,
                           signature_depth, cross_correlation, summary_logsignature,
@@ -89,7 +90,16 @@ class BayesSim(object):
           ``rffSigmaScale`` times the median pairwise distance of the first chunk's training rows, standardised
           first under ``inputNorm``, made on the device, kept in ``state_dict``; include/bsig_rff_bandwidth.h.
 
-        ``bs.summary_kwargs`` holds the keyword arguments every summarizer call gets from these keys."""
+        ``bs.summary_kwargs`` holds the keyword arguments every summarizer call gets from these keys.
+
+        Recorded episodes that end early (the recorder fills the tail with the last state): ``fit`` and
+        ``run_training`` take ``traj_lengths``, ``predict`` and the three ``fit_*`` below ``lengths`` -- the valid
+        STATES of every trajectory, an int32 / int64 tensor, a numpy integer array or a list -- with
+        ``'summary_xcorr'`` and ``'summary_kme'``, whose rows are then those of the trajectories cut at their
+        lengths (include/bsig_ragged.h); ValueError with any other summarizer.  Lengths on the host are
+        range-checked, lengths on the device are never read back -- one outside the range makes its summary NaN,
+        which the deferred finite assert reports -- but for the embedding's scale, which reads back the first
+        256 at most, once."""
         self.prior = prior
         self.proposal = proposal
         model_class = model_cfg['modelClass']
@@ -181,8 +191,22 @@ class BayesSim(object):
             n = n_train_trajs - n_train_trajs_done
         return n
 
-    def _summarize(self, states, actions, finite_flag=None, lazy=False):
+    def _ragged_lengths(self, lengths, states):
+        """``lengths`` as the summarizer takes them, checked before any GPU call (None stays None); ValueError
+        where the summarizer takes none."""
+        if lengths is None:
+            return None
+        if not self._summarizer.ragged:
+            raise ValueError("lengths apply to 'summary_xcorr' and 'summary_kme', not to %r"
+                             % (self.summarizer_name,))
+        diff = self.embedding.diff if self.embedding is not None else self._summary_kwargs.get('state_diff', True)
+        return _check_lengths(lengths, int(states.shape[0]), int(states.shape[1]), diff)
+
+    def _summarize(self, states, actions, finite_flag=None, lazy=False, lengths=None):
         entry, kw = self._summarizer, dict(self._summary_kwargs)
+        lengths = self._ragged_lengths(lengths, states)
+        if lengths is not None:       # (without lengths: no keyword, the call it always was)
+            kw['lengths'] = lengths
         # ('summaryDtype': 'float64' -- the summarizers' fp64 kernels; else no keyword: the fp32 path)
         if self._summary_dtype is not None:
             kw['dtype'] = self._summary_dtype
@@ -204,13 +228,15 @@ class BayesSim(object):
                 self.model._inorm is None and os.environ.get('BSIG_NO_FUSED_SUMMARY') != '1')
 
     def run_training(self, params, traj_states, traj_actions, _defer=False, _finite_flag=None,
-                     _summaries=None, _feats=None, _standardized=False):
+                     _summaries=None, _feats=None, _standardized=False, traj_lengths=None):
         """One chunk: summarize, then NUM_GRAD_UPDATES Adam updates of
-        MINIBATCH_SIZE (reference bayes_sim.py:91-114)."""
+        MINIBATCH_SIZE (reference bayes_sim.py:91-114).  ``traj_lengths``: the valid states of every
+        trajectory ('summary_xcorr' and 'summary_kme'; see the constructor)."""
         if _summaries is None:
-            self._embedding_scale_of_chunk(traj_states, traj_actions)
+            traj_lengths = self._ragged_lengths(traj_lengths, traj_states)
+            self._embedding_scale_of_chunk(traj_states, traj_actions, traj_lengths)
         traj_summaries = _summaries if _summaries is not None else \
-            self._summarize(traj_states, traj_actions, _finite_flag, lazy=True)
+            self._summarize(traj_states, traj_actions, _finite_flag, lazy=True, lengths=traj_lengths)
         kw = {} if _feats is None else {'_feats': _feats}
         if _standardized:       # fit() has standardised the block these rows come from
             kw['_standardized'] = True
@@ -225,12 +251,18 @@ class BayesSim(object):
             raise RuntimeError("this BayesSim was built without 'summarizerFxn': 'summary_kme'")
         return self.embedding
 
-    def fit_embedding_scale(self, states, actions):
+    def fit_embedding_scale(self, states, actions, lengths=None):
         """The per-column scale of ``'summarizerFxn': 'summary_kme'`` from the given trajectories (the first
         256 at most; ``fit`` and ``run_training`` by themselves take the first chunk's first training
-        trajectories), frozen from here on.  Synchronises, and asserts that the scale is finite."""
+        trajectories), frozen from here on.  Synchronises, and asserts that the scale is finite.  ``lengths``:
+        from the valid rows only (``KernelMeanEmbedding.fit_scale``: lengths on the device are read back, 1 KB
+        at most)."""
         emb = self._require_embedding()
-        emb.fit_scale(states, actions, dtype=self._summary_dtype)
+        lengths = self._ragged_lengths(lengths, states)
+        if lengths is None:
+            emb.fit_scale(states, actions, dtype=self._summary_dtype)
+        else:
+            emb.fit_scale(states, actions, dtype=self._summary_dtype, lengths=lengths)
         return self._keep_if_finite(emb, (emb.inv_std,), 'non-finite value in the trajectories')
 
     def _keep_if_finite(self, stat, values, message):
@@ -251,33 +283,38 @@ class BayesSim(object):
         rows are held out): what a statistic that does not exist yet is made from, on every path."""
         return _lib.split_rows(BayesSim.get_n_trajs_per_batch(n, done), BayesSim.TEST_FRACTION)[0]
 
-    def _embedding_scale_of_chunk(self, states, actions):
+    def _embedding_scale_of_chunk(self, states, actions, lengths=None):
         """The scale, where it does not exist yet, from the trajectories both paths of ``fit`` and
         ``run_training`` use: the first ``min(n_train, 256)`` of the chunk ``states`` starts with.  Nothing is
         read back: a non-finite trajectory among them makes every summary non-finite, which the summaries'
-        finite flag reports."""
+        finite flag reports.  With ``lengths`` (checked already): from those trajectories' valid rows; lengths
+        on the device are read back here, the first 256 at most, once per embedding."""
         emb = self.embedding
         if emb is None or emb.ready:
             return
         emb.refuse_data_parallel(self.model._dp)
         n_train = self._first_training_rows(int(states.shape[0]))
-        emb.fit_scale(states[:n_train], actions[:n_train], dtype=self._summary_dtype)
+        if lengths is None:
+            emb.fit_scale(states[:n_train], actions[:n_train], dtype=self._summary_dtype)
+        else:
+            emb.fit_scale(states[:n_train], actions[:n_train], dtype=self._summary_dtype,
+                          lengths=lengths[:n_train])
 
-    def fit_input_norm(self, states, actions):
+    def fit_input_norm(self, states, actions, lengths=None):
         """The input statistics of a model built with ``'inputNorm': True`` from the summaries of ALL the
         given trajectories (``fit`` by itself takes the first chunk's training rows), frozen from here on.
         Synchronises, and asserts that the statistics are finite."""
         norm = self.model._require_inorm()
-        self.model.fit_input_norm(self._summarize(states, actions))
+        self.model.fit_input_norm(self._summarize(states, actions, lengths=lengths))
         return self._keep_if_finite(norm, (norm.mean, norm.inv_std), 'non-finite value in the trajectory summaries')
 
-    def fit_rff_bandwidth(self, states, actions):
+    def fit_rff_bandwidth(self, states, actions, lengths=None):
         """The counterpart of ``fit_input_norm`` for the bandwidth of an ``'MDRFF_<kernel>_median'`` model: from
         the summaries of the given trajectories (the first 1024 at most; ``fit`` by itself takes the first
         chunk's training rows), standardised first under ``inputNorm``, frozen from here on.  Synchronises, and
         asserts that the bandwidth is finite."""
         bw = self.model._require_rffbw()
-        self.model.fit_rff_bandwidth(self._summarize(states, actions))
+        self.model.fit_rff_bandwidth(self._summarize(states, actions, lengths=lengths))
         return self._keep_if_finite(bw, (bw.sigma,), 'non-finite value in the trajectory summaries')
 
     def _standardize_block(self, summ, n_train):
@@ -292,14 +329,16 @@ class BayesSim(object):
 
     FIT_BLOCK_BYTES = 4 << 30        # (not in the reference) bound on a block's summaries in fit()
 
-    def fit(self, params, traj_states, traj_actions):
+    def fit(self, params, traj_states, traj_actions, traj_lengths=None):
         """The caller-side loop of bayes_sim_main.py:157-167 over
         pre-recorded pairs: consecutive chunks of at most
         NUM_TRAIN_TRAJ_PER_BATCH pairs, ``run_training`` on each.
-        Returns the list of per-chunk log dicts."""
+        Returns the list of per-chunk log dicts.  ``traj_lengths``: the valid states of every trajectory
+        ('summary_xcorr' and 'summary_kme'; see the constructor), sliced with the trajectories."""
+        traj_lengths = self._ragged_lengths(traj_lengths, traj_states)
         # the chunks' logs are read after the last chunk is enqueued: if a persistent launch turns out not
         # to have had the GPU to itself, the whole loop is repeated from here (MDNN._retrying)
-        return self.model._retrying(lambda: self._fit_once(params, traj_states, traj_actions))
+        return self.model._retrying(lambda: self._fit_once(params, traj_states, traj_actions, traj_lengths))
 
     def _check_equal_counts(self, n):
         """One all-reduce per update: every rank of a data-parallel group must run the same chunk
@@ -330,7 +369,7 @@ class BayesSim(object):
             at += sizes[-1]
         return sizes[:self.model.block_prefix(sizes, BayesSim.TEST_FRACTION)]
 
-    def _fit_once(self, params, traj_states, traj_actions):
+    def _fit_once(self, params, traj_states, traj_actions, traj_lengths=None):
         """Block by block: the block's summaries and features when ``done`` leaves the block before; the
         block's chunks in ONE launch of the persistent update kernel where the model's plan can; else chunk
         by chunk.  The logs (and the isfinite asserts) are read back after the last chunk is enqueued: one
@@ -340,7 +379,11 @@ class BayesSim(object):
         before the projection."""
         model, n, done, pending = self.model, params.shape[0], 0, []
         model._check_statistics_dp()
-        self._embedding_scale_of_chunk(traj_states, traj_actions)
+        self._embedding_scale_of_chunk(traj_states, traj_actions, traj_lengths)
+        if traj_lengths is not None and torch.is_tensor(traj_states) and traj_states.is_cuda:
+            # (the scale above took them where they were: lengths on the host are not read back)
+            traj_lengths = traj_lengths.to(traj_states.device)      # once, not once per chunk
+        cut = lambda a, b: None if traj_lengths is None else traj_lengths[a:b]      # noqa: E731
         self._check_equal_counts(n)
         on_gpu = torch.is_tensor(traj_states) and traj_states.is_cuda
         flag = torch.zeros(1, dtype=torch.int32, device=traj_states.device) if on_gpu else None
@@ -350,7 +393,7 @@ class BayesSim(object):
         while done < n:
             if block and done >= hi:
                 lo, hi = done, min(n, done + block)
-                summ = self._summarize(traj_states[lo:hi], traj_actions[lo:hi], flag, lazy=True)
+                summ = self._summarize(traj_states[lo:hi], traj_actions[lo:hi], flag, lazy=True, lengths=cut(lo, hi))
                 if model._inorm is not None:
                     summ = self._standardize_block(summ, self._first_training_rows(n, lo))
                 if model._rffbw is not None and not model.rff_bandwidth_ready:
@@ -378,18 +421,19 @@ class BayesSim(object):
                 pending.append(self.run_training(params[done:done + m],
                                                  traj_states[done:done + m],
                                                  traj_actions[done:done + m], _defer=True,
-                                                 _finite_flag=flag))
+                                                 _finite_flag=flag, traj_lengths=cut(done, done + m)))
             done += m
         logs = [p.result() for p in pending]
         assert flag is None or int(flag.item()) == 0   # summarizers.py:120
         return logs
 
-    def predict(self, states, actions, threshold=0.005):
+    def predict(self, states, actions, threshold=0.005, lengths=None):
         """Posterior for the given real trajectories (the contract of reference bayes_sim.py:116-179):
         ONE trajectory -> the model's mixture for it (divided by the proposal when there is one);
         SEVERAL -> REFIT_SAMPLES draws from their mixtures, refitted by a fresh unconditional MDNN
-        (input: a constant) whose single mixture is returned."""
-        summaries = self._summarize(states, actions)
+        (input: a constant) whose single mixture is returned.  ``lengths``: the valid states of every
+        trajectory ('summary_xcorr' and 'summary_kme'; see the constructor)."""
+        summaries = self._summarize(states, actions, lengths=lengths)
         mixtures = [self._correct_for_proposal(m, threshold) for m in self.model.predict_MoGs(summaries)]
         return mixtures[0] if len(mixtures) == 1 else self._refit(mixtures)
 

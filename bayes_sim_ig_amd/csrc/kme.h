@@ -26,13 +26,19 @@
 // once per kWaves tiles (re-read through the cache); no register array is indexed by a run-time tile.
 // The constants tau_r = 1 / max(M - 1, 1) (a division in T) and a / M = (T)(sqrt(1.0 / m) / M) (made in
 // double, rounded once) come from the host.
+// With lengths (include/bsig_ragged.h, kRagged) the same kernels take M per trajectory: G and the blocks' layout
+// are those of ts; a row is masked, and its loads are clamped, by its own trajectory's M; a longer trajectory
+// walks ceil(M_n / kBlock) blocks (G > 1 only where the M of ts is one block, so the members of a group never
+// differ in that); and the two constants are made on the device by the host's own divisions in the host's
+// types (the root of a / M comes from the host), so a row has the bits of the fixed-length launch on its slice.
 #pragma once
 #include <algorithm>
 #include <climits>
 #include <cmath>
 
 #include "common.h"
-#include "../../include/bsig_kme.h"
+#include "ragged.h"
+#include "../../include/bsig_ragged.h"
 
 namespace bsig {
 namespace kme {
@@ -148,6 +154,29 @@ __global__ __launch_bounds__(kThreads) void kme_rows_kernel(const T* __restrict_
     const int t = (int)(q - i * g.steps);
     rows[q * ld_rows + k] = element_at<T>(states + i * (int64_t)g.ts * g.sd,
                                           actions + i * (int64_t)g.ta * g.ad, g, t, k);
+  }
+}
+
+// The valid rows only, compacted (bsig_kme_rows_ragged): a workgroup takes a trajectory at a time and writes its
+// M_n rows from row offsets[n] on, an element a thread.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void kme_rows_ragged_kernel(const T* __restrict__ states,
+                                                                   const T* __restrict__ actions,
+                                                                   const int32_t* __restrict__ lengths,
+                                                                   const int64_t* __restrict__ offsets,
+                                                                   T* __restrict__ rows, int64_t n, int64_t ld_rows,
+                                                                   Shape<T> g) {
+  for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
+    Shape<T> own = g;
+    own.steps = ragged::steps_of(lengths, i, g.ts, g.diff).steps;
+    own.tau_r = (T)1 / (T)max(own.steps - 1, 1);
+    const T* s = states + i * (int64_t)g.ts * g.sd;
+    const T* a = actions + i * (int64_t)g.ta * g.ad;
+    T* o = rows + offsets[i] * ld_rows;
+    for (int e = threadIdx.x; e < own.steps * g.d; e += blockDim.x) {
+      const int t = e / g.d, k = e - t * g.d;
+      o[(int64_t)t * ld_rows + k] = element_at<T>(s, a, own, t, k);
+    }
   }
 }
 
@@ -346,12 +375,15 @@ __device__ __forceinline__ void tile_sums(const double* __restrict__ X, const do
   *sn_out = h == 0 ? sn + so : so + sn;
 }
 
-template <typename T>
+// (kRagged: `lengths` holds every trajectory's own length and `a_root` is sqrt(1 / m), a_over_m is not read; else
+// neither is read)
+template <typename T, bool kRagged>
 __global__ __launch_bounds__(kThreads) void kme_kernel(const T* __restrict__ states, const T* __restrict__ actions,
+                                                       const int32_t* __restrict__ lengths,
                                                        const T* __restrict__ coeff, int64_t ld_coeff, int vec_ok,
                                                        T* __restrict__ out, int64_t n, int m, int64_t ld_out,
-                                                       T a_over_m, int32_t* __restrict__ nonfinite, Shape<T> g,
-                                                       Plan p) {
+                                                       T a_over_m, double a_root, int32_t* __restrict__ nonfinite,
+                                                       Shape<T> g, Plan p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char kme_smem[];
   T* X = reinterpret_cast<T*>(kme_smem);
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -366,7 +398,13 @@ __global__ __launch_bounds__(kThreads) void kme_kernel(const T* __restrict__ sta
   // stride, so that an element is two loads and a few selects WITHOUT a branch (a plain column loads its value
   // twice): kStageBatch elements a thread are then on their way from memory before the first is stored.  (With a
   // branch per kind the compiler waits for an element's loads where its branches meet, one element after the other.)
-  auto stage = [&](int64_t first, int t0, int nrows) {
+  // kRagged: `own_steps` is the M of the one trajectory the rows come from, or -1: the rows of a group, each
+  // trajectory's M looked up per row (a load more in the batch; the length is clamped before it indexes).
+  auto stage = [&](int64_t first, int t0, int nrows, int own_steps) {
+    T own_tau_r = g.tau_r;
+    if constexpr (kRagged) {
+      if (own_steps >= 0) own_tau_r = (T)1 / (T)max(own_steps - 1, 1);
+    }
     const int cols = 1 << p.stage_shift, col = tid & (cols - 1), row0 = tid >> p.stage_shift;
     const int rpp = kThreads >> p.stage_shift, iters = nrows / rpp;
     for (int k = col; k < dpad; k += cols) {
@@ -394,11 +432,22 @@ __global__ __launch_bounds__(kThreads) void kme_kernel(const T* __restrict__ sta
         for (int u = 0; u < kStageBatch; ++u) {
           const int vr = min(row0 + (i0 + u) * rpp, nrows - 1);      // (beyond the last: read again, not stored)
           const int t = t0 + vr % kBlock;
-          const int64_t off = (first + vr / kBlock) * per_traj + (int64_t)min(t, tmax) * stride;
+          int steps = g.steps, tlast = tmax;
+          T tau_r = g.tau_r;
+          if constexpr (kRagged) {
+            steps = own_steps;
+            tau_r = own_tau_r;
+            if (own_steps < 0) {
+              steps = ragged::steps_of(lengths, first + vr / kBlock, g.ts, g.diff).steps;
+              if (kind == kTau) tau_r = (T)1 / (T)max(steps - 1, 1);
+            }
+            tlast = min(tmax, steps - 1);      // (the actions' min(M, ta) - 1 included: M_n <= M)
+          }
+          const int64_t off = (first + vr / kBlock) * per_traj + (int64_t)min(t, tlast) * stride;
           const T x1 = hi[off], x0 = lo[off];
           T x = kind == kDiff ? x1 - x0 : x1;
-          x = kind == kTau ? (T)t * g.tau_r : x;
-          v[u] = (kind == kZero || t >= g.steps) ? (T)0 : x;
+          x = kind == kTau ? (T)t * tau_r : x;
+          v[u] = (kind == kZero || t >= steps) ? (T)0 : x;
         }
 #pragma unroll
         for (int u = 0; u < kStageBatch; ++u)
@@ -406,10 +455,11 @@ __global__ __launch_bounds__(kThreads) void kme_kernel(const T* __restrict__ sta
       }
     }
   };
-  auto store = [&](int64_t traj, int tile, T cs, T sn) {
+  // (`scale`: a / M of the trajectory; `valid`: its length was inside the range, else the row is NaN)
+  auto store = [&](int64_t traj, int tile, T cs, T sn, T scale, bool valid) {
     const int j = tile * kTile + (lane & 31);
     if (lane < 32 && j < m) {
-      const T c = cs * a_over_m, s = sn * a_over_m;
+      const T c = valid ? cs * scale : (T)NAN, s = valid ? sn * scale : (T)NAN;
       T* o = out + traj * ld_out;
       o[j] = c;
       o[m + j] = s;
@@ -421,31 +471,51 @@ __global__ __launch_bounds__(kThreads) void kme_kernel(const T* __restrict__ sta
     if (p.n_blocks == 1) {
       const int ng = (int)min((int64_t)G, n - base);
       __syncthreads();                            // the items before are done with the LDS
-      stage(base, 0, ng * kBlock);
+      stage(base, 0, ng * kBlock, -1);
       __syncthreads();
       for (int item = wave; item < ng * p.tiles; item += kWaves) {
         const int gi = item / p.tiles, tile = item - gi * p.tiles;
+        int steps = g.steps;
+        T scale = a_over_m;
+        bool valid = true;
+        if constexpr (kRagged) {
+          const ragged::Steps own = ragged::steps_of(lengths, base + gi, g.ts, g.diff);
+          steps = own.steps;
+          valid = own.valid;
+          scale = (T)(a_root / (double)steps);
+        }
         T cs, sn;
-        tile_sums(X + gi * p.block_elems, coeff, ld_coeff, vec_ok, tile, m, g.d, dpad, pitch, g.steps, &cs, &sn);
-        store(base + gi, tile, cs, sn);
+        tile_sums(X + gi * p.block_elems, coeff, ld_coeff, vec_ok, tile, m, g.d, dpad, pitch, steps, &cs, &sn);
+        store(base + gi, tile, cs, sn, scale, valid);
       }
     } else {
+      // (one trajectory a workgroup here: its length is the same for every thread, and so are the barriers)
+      int steps = g.steps, n_blocks = p.n_blocks;
+      T scale = a_over_m;
+      bool valid = true;
+      if constexpr (kRagged) {
+        const ragged::Steps own = ragged::steps_of(lengths, base, g.ts, g.diff);
+        steps = own.steps;
+        valid = own.valid;
+        n_blocks = ceil_div(steps, kBlock);
+        scale = (T)(a_root / (double)steps);
+      }
       for (int tile0 = 0; tile0 < p.tiles; tile0 += kWaves) {
         const int tile = tile0 + wave;
         T cs = (T)0, sn = (T)0;
-        for (int b = 0; b < p.n_blocks; ++b) {
+        for (int b = 0; b < n_blocks; ++b) {
           __syncthreads();
-          stage(base, b * kBlock, kBlock);
+          stage(base, b * kBlock, kBlock, steps);
           __syncthreads();
           if (tile < p.tiles) {
             T c1, s1;
-            tile_sums(X, coeff, ld_coeff, vec_ok, tile, m, g.d, dpad, pitch, min(kBlock, g.steps - b * kBlock),
+            tile_sums(X, coeff, ld_coeff, vec_ok, tile, m, g.d, dpad, pitch, min(kBlock, steps - b * kBlock),
                       &c1, &s1);
             cs += c1;
             sn += s1;
           }
         }
-        if (tile < p.tiles) store(base, tile, cs, sn);
+        if (tile < p.tiles) store(base, tile, cs, sn, scale, valid);
       }
     }
   }
@@ -462,12 +532,12 @@ inline Shape<T> shape_of(int ts, int ta, int sd, int ad, int diff, int time, int
   return g;
 }
 
-// bsig_kme / bsig_kme_f64: the argument checks, the plan, the constants, the launch.  `max_grid`: the
-// precision's workgroup cap.
-template <typename T>
-int run(const char* what, int64_t max_grid, const T* states, const T* actions, const T* coeff, int64_t ld_coeff,
-        T* out, int64_t n, int ts, int ta, int sd, int ad, int m, int diff, int time, int64_t ld_out,
-        int32_t* nonfinite, bsig_stream_t stream) {
+// bsig_kme / bsig_kme_f64 and, with lengths, bsig_kme_ragged / bsig_kme_ragged_f64: the argument checks, the
+// plan, the constants, the launch.  `max_grid`: the precision's workgroup cap.
+template <typename T, bool kRagged>
+int run_any(const char* what, int64_t max_grid, const T* states, const T* actions, const int32_t* lengths,
+            const T* coeff, int64_t ld_coeff, T* out, int64_t n, int ts, int ta, int sd, int ad, int m, int diff,
+            int time, int64_t ld_out, int32_t* nonfinite, bsig_stream_t stream) {
   if (n == 0) return BSIG_OK;
   BSIG_REQUIRE(n > 0, "%s: bad n=%lld", what, (long long)n);
   Plan p;
@@ -476,15 +546,26 @@ int run(const char* what, int64_t max_grid, const T* states, const T* actions, c
                2 * (long long)m);
   BSIG_REQUIRE(ld_coeff >= p.d, "%s: ld_coeff %lld below the row width %d", what, (long long)ld_coeff, p.d);
   BSIG_REQUIRE(states && actions && coeff && out, "%s: null pointer", what);
+  if (kRagged) BSIG_REQUIRE(lengths, "%s: null lengths", what);
   static LdsRaised raised;
-  if (p.lds > kLdsUnraised) BSIG_TRY(raise_lds_limit(kme_kernel<T>, kLdsBytes, &raised));
+  if (p.lds > kLdsUnraised) BSIG_TRY(raise_lds_limit(kme_kernel<T, kRagged>, kLdsBytes, &raised));
   const int vec_ok = ld_coeff % 4 == 0 && aligned(coeff, 16);
-  const T a_over_m = (T)(std::sqrt(1.0 / (double)m) / (double)p.steps);
-  hipLaunchKernelGGL((kme_kernel<T>), dim3(capped_grid(ceil_div<int64_t>(n, p.group), max_grid)), dim3(kThreads),
-                     p.lds, as_stream(stream), states, actions, coeff, ld_coeff, vec_ok, out, n, m, ld_out,
-                     a_over_m, nonfinite, shape_of<T>(ts, ta, sd, ad, diff, time, p.steps, p.d), p);
+  const double a_root = std::sqrt(1.0 / (double)m);
+  const T a_over_m = (T)(a_root / (double)p.steps);
+  hipLaunchKernelGGL((kme_kernel<T, kRagged>), dim3(capped_grid(ceil_div<int64_t>(n, p.group), max_grid)),
+                     dim3(kThreads), p.lds, as_stream(stream), states, actions, lengths, coeff, ld_coeff, vec_ok, out,
+                     n, m, ld_out, a_over_m, a_root, nonfinite,
+                     shape_of<T>(ts, ta, sd, ad, diff, time, p.steps, p.d), p);
   BSIG_CHECK_LAUNCH(what);
   return BSIG_OK;
+}
+
+template <typename T>
+int run(const char* what, int64_t max_grid, const T* states, const T* actions, const T* coeff, int64_t ld_coeff,
+        T* out, int64_t n, int ts, int ta, int sd, int ad, int m, int diff, int time, int64_t ld_out,
+        int32_t* nonfinite, bsig_stream_t stream) {
+  return run_any<T, false>(what, max_grid, states, actions, nullptr, coeff, ld_coeff, out, n, ts, ta, sd, ad, m, diff,
+                           time, ld_out, nonfinite, stream);
 }
 
 template <typename T>
@@ -501,6 +582,29 @@ int run_rows(const char* what, const T* states, const T* actions, T* rows, int64
   const int64_t total = n * steps * d;
   hipLaunchKernelGGL((kme_rows_kernel<T>), dim3(capped_grid(ceil_div<int64_t>(total, kThreads), kSummaryGridCap)),
                      dim3(kThreads), 0, as_stream(stream), states, actions, rows, total, ld_rows,
+                     shape_of<T>(ts, ta, sd, ad, diff, time, steps, d));
+  BSIG_CHECK_LAUNCH(what);
+  return BSIG_OK;
+}
+
+template <typename T>
+int run_rows_ragged(const char* what, const T* states, const T* actions, const int32_t* lengths,
+                    const int64_t* offsets, T* rows, int64_t n, int ts, int ta, int sd, int ad, int diff, int time,
+                    int64_t ld_rows, bsig_stream_t stream) {
+  if (n == 0) return BSIG_OK;
+  BSIG_REQUIRE(n > 0, "%s: bad n=%lld", what, (long long)n);
+  int steps = 0, d = 0;
+  BSIG_TRY(dims(what, ts, ta, sd, ad, diff, time, &steps, &d));
+  BSIG_REQUIRE(ld_rows >= d, "%s: ld_rows %lld below the row width %d", what, (long long)ld_rows, d);
+  BSIG_REQUIRE(states && actions && rows, "%s: null pointer", what);
+  BSIG_REQUIRE(lengths, "%s: null lengths", what);
+  BSIG_REQUIRE(offsets, "%s: null offsets", what);
+  BSIG_REQUIRE(n <= INT64_MAX / ((int64_t)steps * d), "%s: n=%lld rows of %d x %d elements are past 2^63", what,
+               (long long)n, steps, d);
+  BSIG_REQUIRE((int64_t)steps * d <= INT32_MAX, "%s: a trajectory of %d x %d elements is past 2^31 - 1", what, steps,
+               d);
+  hipLaunchKernelGGL((kme_rows_ragged_kernel<T>), dim3(capped_grid(n, kSummaryGridCap)), dim3(kThreads), 0,
+                     as_stream(stream), states, actions, lengths, offsets, rows, n, ld_rows,
                      shape_of<T>(ts, ta, sd, ad, diff, time, steps, d));
   BSIG_CHECK_LAUNCH(what);
   return BSIG_OK;

@@ -28,13 +28,19 @@
 // idle the memory path meanwhile: where a thread's share is at most kPfS states and kPfA actions
 // (Plan::prefetch: Pendulum, Ant; not ShadowHand's 42 states a thread) the NEXT trajectories'
 // elements are fetched into registers before this one's differences, chains and stores.
+// With lengths (include/bsig_ragged.h, kRagged) the same kernel takes M per trajectory: the launch shape and
+// the staging are those of ts (the rows beyond a length are in bounds, staged and never read again), the run
+// length of the in-place differences and every chain's trip count follow the trajectory's own M, whose
+// reciprocals its threads make in LDS, one set per trajectory of the workgroup (Plan: per_traj_rcp); a lag
+// with no term gets the reciprocal 0.  The barriers do not depend on a length.
 #pragma once
 #include <algorithm>
 #include <climits>
 #include <cmath>
 
 #include "common.h"
-#include "../../include/bsig_xcorr.h"
+#include "ragged.h"
+#include "../../include/bsig_ragged.h"
 
 namespace bsig {
 namespace xcorr {
@@ -59,7 +65,7 @@ struct Plan {
   int prefetch = 0;
   int slot = 0;            // bytes of LDS of one trajectory; the actions start at off_a
   int off_a = 0;
-  size_t lds = 0;          // the workgroup's: the reciprocals, then G slots
+  size_t lds = 0;          // the workgroup's: the reciprocals (with lengths: of each of the G), then G slots
   int off_slots = 0;
 };
 
@@ -71,9 +77,11 @@ inline int64_t row_width(int64_t sd, int64_t ad, int64_t max_lag) {
   return w > INT32_MAX ? -1 : w;
 }
 
-// The launch shape, or why there is none (the checks both entry points and bsig_xcorr_fits share).
+// The launch shape, or why there is none (the checks every entry point and bsig_xcorr_fits share).
+// `per_traj_rcp`: every trajectory of a workgroup has reciprocals of its own (what is covered does not change:
+// one trajectory, one set).
 inline int plan(const char* what, int ts, int ta, int sd, int ad, int max_lag, int state_diff,
-                int itemsize, Plan* p) {
+                int itemsize, Plan* p, bool per_traj_rcp = false) {
   BSIG_REQUIRE(ts >= 1, "%s: ts %d below 1", what, ts);
   BSIG_REQUIRE(ta >= 1, "%s: ta %d below 1", what, ta);
   BSIG_REQUIRE(sd >= 1 && ad >= 1, "%s: bad dims sd=%d ad=%d", what, sd, ad);
@@ -92,7 +100,8 @@ inline int plan(const char* what, int ts, int ta, int sd, int ad, int max_lag, i
   auto r16 = [](int64_t b) { return (b + 15) & ~(int64_t)15; };
   const int64_t off_a = r16((int64_t)ts * sd * itemsize);
   const int64_t slot = off_a + r16((int64_t)m * ad * itemsize);
-  const int64_t off_slots = r16((int64_t)(max_lag + 2) * itemsize);
+  auto rcp_bytes = [&](int group) { return r16((int64_t)(per_traj_rcp ? group : 1) * (max_lag + 2) * itemsize); };
+  int64_t off_slots = rcp_bytes(1);
   if (off_slots + slot > (int64_t)kLdsBytes) {
     set_error("%s: %lld B of LDS needed for one trajectory of %d steps, sd=%d ad=%d (%zu in a workgroup)",
               what, (long long)(off_slots + slot), ts, sd, ad, kLdsBytes);
@@ -101,7 +110,8 @@ inline int plan(const char* what, int ts, int ta, int sd, int ad, int max_lag, i
   int per_traj = kMinPerTraj;
   while (per_traj < kThreads && per_traj < width) per_traj *= 2;
   int group = kThreads / per_traj;
-  while (group > 1 && off_slots + group * slot > (int64_t)kLdsUnraised) group /= 2;
+  while (group > 1 && rcp_bytes(group) + group * slot > (int64_t)kLdsUnraised) group /= 2;
+  off_slots = rcp_bytes(group);
   per_traj = kThreads / group;
   // a trajectory beyond half the LDS has the CU to itself: twice the wavefronts to hide its LDS reads behind
   if (group == 1 && 2 * (off_slots + slot) > (int64_t)kLdsBytes) per_traj = kMaxThreads;
@@ -249,26 +259,32 @@ __device__ __forceinline__ void statistics(const T* f, T rm, int r0, int sd, int
 
 // (kBound, the workgroup's size, is a template argument because the bound decides the code: compiled for up to
 // kMaxThreads threads the workgroups of kThreads ran Ant 1.1 to 2.1 times as long, profiles/xcorr_NOTES.md)
-template <typename T, int kVec, int kBound>
+// (kRagged: `lengths` holds every trajectory's own length and `rc` is not read; else `lengths` is not read)
+template <typename T, int kVec, int kBound, bool kRagged>
 __global__ __launch_bounds__(kBound) void xcorr_kernel(
-    const T* __restrict__ states, const T* __restrict__ actions, T* __restrict__ out, int64_t n, int ts,
-    int ta, int sd, int ad, int max_lag, int state_diff, int64_t ld_out, int vec_ok,
-    int32_t* __restrict__ nonfinite, Plan g, Rcp<T> rc) {
+    const T* __restrict__ states, const T* __restrict__ actions, const int32_t* __restrict__ lengths,
+    T* __restrict__ out, int64_t n, int ts, int ta, int sd, int ad, int max_lag, int state_diff,
+    int64_t ld_out, int vec_ok, int32_t* __restrict__ nonfinite, Plan g, Rcp<T> rc) {
   extern __shared__ __attribute__((aligned(16))) unsigned char xcorr_smem[];
   const int tid = threadIdx.x;
-  const int P = g.per_traj, G = g.group, m = g.m;
+  const int P = g.per_traj, G = g.group;
   const int grp = tid / P, lt = tid - grp * P;
-  T* rcp = reinterpret_cast<T*>(xcorr_smem);
+  T* rcp = reinterpret_cast<T*>(xcorr_smem) + (kRagged ? grp * (max_lag + 2) : 0);
   T* f = reinterpret_cast<T*>(xcorr_smem + g.off_slots + grp * g.slot);
   T* a = reinterpret_cast<T*>(xcorr_smem + g.off_slots + grp * g.slot + g.off_a);
-  const int n_s = ts * sd, n_a = m * ad, n_a_own = min(ta, m) * ad;
+  // what is staged: the steps of ts, whatever a trajectory's own length
+  const int n_s = ts * sd, n_a = g.m * ad, n_a_own = min(ta, g.m) * ad;
   const int n_cross = (max_lag + 1) * sd * ad, width = (int)g.width;
   // the in-place differences: runs per column, steps per run
   const int nseg = sd >= P ? 1 : P / sd;
-  const int seg_len = ceil_div(m, nseg);
+  // M, and what follows from it: the trajectory's own under kRagged
+  int m = g.m, seg_len = ceil_div(m, nseg);
+  bool valid = true;
 
-  for (int k = tid; k <= max_lag; k += blockDim.x) rcp[k] = rc.lag[k];
-  if (tid == 0) rcp[max_lag + 1] = rc.all;
+  if constexpr (!kRagged) {
+    for (int k = tid; k <= max_lag; k += blockDim.x) rcp[k] = rc.lag[k];
+    if (tid == 0) rcp[max_lag + 1] = rc.all;
+  }
 
   // element e of the padded actions of a trajectory: beyond its own steps the last one again
   auto action_at = [&](const T* arow, int e) { return arow[e < n_a_own ? e : (ta - 1) * ad + e % ad]; };
@@ -292,7 +308,20 @@ __global__ __launch_bounds__(kBound) void xcorr_kernel(
   for (int64_t base = first; base < n; base += step) {
     const int64_t traj = base + grp;
     const bool active = traj < n;
+    if constexpr (kRagged) {
+      // the length is clamped before it indexes anything; one outside the range makes the row NaN below
+      const ragged::Steps own = active ? ragged::steps_of(lengths, traj, ts, state_diff) : ragged::Steps{g.m, true};
+      m = own.steps;
+      valid = own.valid;
+      seg_len = ceil_div(m, nseg);
+    }
     __syncthreads();          // the reciprocals above / the trajectories before are done with the LDS
+    if constexpr (kRagged) {
+      // the host's (T)1 / (T)(M - tau) and (T)1 / (T)M, here by the same correctly rounded division; a lag with
+      // no term: 0, times its empty chain's 0
+      for (int k = lt; k <= max_lag; k += P) rcp[k] = k < m ? (T)1 / (T)(m - k) : (T)0;
+      if (lt == 0) rcp[max_lag + 1] = (T)1 / (T)m;
+    }
     if (active) {
       if (g.prefetch) {
 #pragma unroll
@@ -360,6 +389,12 @@ __global__ __launch_bounds__(kBound) void xcorr_kernel(
         for (int v = 0; v < kVec; ++v)
           r[v] = e0 + v < width ? output<T>(f, a, rcp, e0 + v, sd, ad, m, max_lag, n_cross) : (T)0;
       }
+      if constexpr (kRagged) {
+        if (!valid) {
+#pragma unroll
+          for (int v = 0; v < kVec; ++v) r[v] = (T)NAN;
+        }
+      }
 #pragma unroll
       for (int v = 0; v < kVec; ++v)
         if (e0 + v < width) bad |= !isfinite(r[v]);
@@ -383,45 +418,59 @@ __global__ __launch_bounds__(kBound) void xcorr_kernel(
   }
 }
 
-template <typename T, int kVec, int kBound>
-inline int launch(const char* what, int64_t max_grid, const T* states, const T* actions, T* out,
-                  int64_t n, int ts, int ta, int sd, int ad, int max_lag, int state_diff, int64_t ld_out,
+template <typename T, int kVec, int kBound, bool kRagged>
+inline int launch(const char* what, int64_t max_grid, const T* states, const T* actions, const int32_t* lengths,
+                  T* out, int64_t n, int ts, int ta, int sd, int ad, int max_lag, int state_diff, int64_t ld_out,
                   int32_t* nonfinite, const Plan& g, const Rcp<T>& rc, bsig_stream_t stream) {
   static LdsRaised raised;
-  if (g.lds > kLdsUnraised) BSIG_TRY(raise_lds_limit(xcorr_kernel<T, kVec, kBound>, kLdsBytes, &raised));
+  if (g.lds > kLdsUnraised)
+    BSIG_TRY(raise_lds_limit(xcorr_kernel<T, kVec, kBound, kRagged>, kLdsBytes, &raised));
   const int vec_ok = ld_out % kVec == 0 && aligned(out, 16);
-  hipLaunchKernelGGL((xcorr_kernel<T, kVec, kBound>), dim3(capped_grid(ceil_div<int64_t>(n, g.group), max_grid)),
-                     dim3(kBound), g.lds, as_stream(stream), states, actions, out, n, ts, ta, sd, ad,
-                     max_lag, state_diff, ld_out, vec_ok, nonfinite, g, rc);
+  hipLaunchKernelGGL((xcorr_kernel<T, kVec, kBound, kRagged>),
+                     dim3(capped_grid(ceil_div<int64_t>(n, g.group), max_grid)), dim3(kBound), g.lds,
+                     as_stream(stream), states, actions, lengths, out, n, ts, ta, sd, ad, max_lag, state_diff,
+                     ld_out, vec_ok, nonfinite, g, rc);
   BSIG_CHECK_LAUNCH(what);
   return BSIG_OK;
 }
 
-// The entry point of either precision: the argument checks, the plan, the reciprocals, the launch.
+// The entry point of either precision, without lengths (bsig_xcorr.h) and with (bsig_ragged.h): the argument
+// checks, the plan, the reciprocals (with lengths the kernel makes them per trajectory), the launch.
 // `max_grid`: the precision's workgroup cap.
-template <typename T>
-int run(const char* what, int64_t max_grid, const T* states, const T* actions, T* out, int64_t n, int ts,
-        int ta, int sd, int ad, int max_lag, int state_diff, int64_t ld_out, int32_t* nonfinite,
-        bsig_stream_t stream) {
+template <typename T, bool kRagged>
+int run_any(const char* what, int64_t max_grid, const T* states, const T* actions, const int32_t* lengths, T* out,
+            int64_t n, int ts, int ta, int sd, int ad, int max_lag, int state_diff, int64_t ld_out,
+            int32_t* nonfinite, bsig_stream_t stream) {
   if (n == 0) return BSIG_OK;
   BSIG_REQUIRE(n > 0, "%s: bad n=%lld", what, (long long)n);
   Plan g;
-  BSIG_TRY(plan(what, ts, ta, sd, ad, max_lag, state_diff, (int)sizeof(T), &g));
+  BSIG_TRY(plan(what, ts, ta, sd, ad, max_lag, state_diff, (int)sizeof(T), &g, kRagged));
   BSIG_REQUIRE(ld_out >= g.width, "%s: ld_out %lld below the width %lld", what, (long long)ld_out,
                (long long)g.width);
   BSIG_REQUIRE(states && actions && out, "%s: null pointer", what);
-  Rcp<T> rc;
-  for (int tau = 0; tau <= BSIG_XCORR_MAX_LAG; ++tau)
-    rc.lag[tau] = tau <= max_lag ? (T)1 / (T)(g.m - tau) : (T)0;
-  rc.all = (T)1 / (T)g.m;
+  if (kRagged) BSIG_REQUIRE(lengths, "%s: null lengths", what);
+  Rcp<T> rc = {};
+  if (!kRagged) {
+    for (int tau = 0; tau <= BSIG_XCORR_MAX_LAG; ++tau)
+      rc.lag[tau] = tau <= max_lag ? (T)1 / (T)(g.m - tau) : (T)0;
+    rc.all = (T)1 / (T)g.m;
+  }
   constexpr int kWide = 16 / (int)sizeof(T);
-#define BSIG_XCORR_LAUNCH(vec, bound)                                                                   \
-  launch<T, vec, bound>(what, max_grid, states, actions, out, n, ts, ta, sd, ad, max_lag, state_diff, \
-                        ld_out, nonfinite, g, rc, stream)
+#define BSIG_XCORR_LAUNCH(vec, bound)                                                                    \
+  launch<T, vec, bound, kRagged>(what, max_grid, states, actions, lengths, out, n, ts, ta, sd, ad, max_lag, \
+                                 state_diff, ld_out, nonfinite, g, rc, stream)
   const bool big = g.group * g.per_traj == kMaxThreads;
   if (g.vec == 1) return big ? BSIG_XCORR_LAUNCH(1, kMaxThreads) : BSIG_XCORR_LAUNCH(1, kThreads);
   return big ? BSIG_XCORR_LAUNCH(kWide, kMaxThreads) : BSIG_XCORR_LAUNCH(kWide, kThreads);
 #undef BSIG_XCORR_LAUNCH
+}
+
+template <typename T>
+int run(const char* what, int64_t max_grid, const T* states, const T* actions, T* out, int64_t n, int ts,
+        int ta, int sd, int ad, int max_lag, int state_diff, int64_t ld_out, int32_t* nonfinite,
+        bsig_stream_t stream) {
+  return run_any<T, false>(what, max_grid, states, actions, nullptr, out, n, ts, ta, sd, ad, max_lag, state_diff,
+                           ld_out, nonfinite, stream);
 }
 
 }  // namespace xcorr

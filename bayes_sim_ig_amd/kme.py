@@ -99,10 +99,15 @@ class KernelMeanEmbedding(FrozenStatistic):
                                'it there (no CPU fallback)')
         return self.freqs.device
 
-    def rows(self, states, actions, dtype=None):
+    def rows(self, states, actions, dtype=None, lengths=None):
         """The rows ``x_t`` of the trajectories as ``[N * M, d]`` device rows (bsig_kme_rows): what the scale's
-        statistics are made from; never on the fit path."""
+        statistics are made from; never on the fit path.  ``lengths`` (``summarizers.check_lengths``): the valid
+        rows only, compacted, ``[sum_n M_n, d]``, trajectory after trajectory (bsig_kme_rows_ragged); their
+        offsets and their number are made on the host, so lengths that live on the device are READ BACK here
+        (4 bytes a trajectory; one outside the range counts as the nearest inside, as in the kernel)."""
         prec = _summ._precision(dtype)
+        if lengths is not None:
+            return self._valid_rows(states, actions, prec, lengths)
         dev = self._on_gpu()
         with _lib.on_device(dev):
             s, a, _ = _summ._prep(states.to(dev), actions.to(dev), prec)
@@ -116,15 +121,46 @@ class KernelMeanEmbedding(FrozenStatistic):
                           int(self.diff), int(self.time), ld, _lib.stream())
         return buf[:, :self.row_dim]
 
-    def fit_scale(self, states, actions, dtype=None):
+    def _valid_rows(self, states, actions, prec, lengths):
+        assert len(states.shape) == 3 and len(actions.shape) == 3, 'Need trajectories: ntraj x n_steps x dim'
+        n, ts = int(states.shape[0]), int(states.shape[1])
+        lengths = _summ.check_lengths(lengths, n, ts, self.diff)
+        if lengths.is_cuda:
+            # the one read-back: the offsets and the number of rows are host arithmetic.  A length outside the
+            # range is clamped as the kernel clamps it: the summaries' NaN row and finite flag report it
+            lengths = lengths.cpu().clamp(min=2 if self.diff else 1, max=ts)
+        steps = lengths.to(torch.int64) - (1 if self.diff else 0)
+        offsets = torch.cumsum(steps, 0) - steps
+        total = int(steps.sum())
+        dev = self._on_gpu()
+        with _lib.on_device(dev):
+            s, a, _ = _summ._prep(states.to(dev), actions.to(dev), prec)
+            sd = s.shape[2]
+            assert (sd, a.shape[2]) == (self.obs_dim, self.act_dim), 'trajectories of other dimensions'
+            ld = _lib.round_up(self.row_dim, 16 // prec.itemsize)
+            buf = torch.empty((total, ld), dtype=prec.dtype, device=dev)
+            lens, offs = _summ._lengths_on(lengths, dev), offsets.to(dev)
+            prec.kme_rows_ragged(_lib.ptr(s), _lib.ptr(a), _lib.ptr(lens), _lib.ptr(offs), _lib.ptr(buf), n, ts,
+                                 a.shape[1], sd, a.shape[2], int(self.diff), int(self.time), ld, _lib.stream())
+        return buf[:, :self.row_dim]
+
+    def fit_scale(self, states, actions, dtype=None, lengths=None):
         """``inv_std`` <- the reciprocal standard deviation of every column of the rows ``x_t`` of the given
         trajectories (the first MAX_SCALE_TRAJECTORIES at most; bsig_kme_rows, then bsig_input_norm_stats:
         the flat rule of include/bsig_input_norm.h), in ``dtype`` (fp32 rows by default), frozen from here on.
-        Asynchronous: nothing is read back, ``count`` is written on the stream."""
+        Asynchronous: nothing is read back, ``count`` is written on the stream.
+
+        ``lengths``: the statistics are made from the VALID rows only (bsig_kme_rows_ragged into compacted rows,
+        then the same statistics).  The rows' offsets and their number come from the first
+        MAX_SCALE_TRAJECTORIES lengths on the host: lengths that live on the device cost ONE read-back of at
+        most 1 KB, once per embedding -- the only read-back lengths add anywhere; lengths on the host add
+        none."""
         n = min(int(states.shape[0]), self.MAX_SCALE_TRAJECTORIES)
         assert n >= 1, 'the scale needs at least one trajectory'
         prec = _summ._precision(dtype)
-        x = self.rows(states[:n], actions[:n], dtype)
+        if lengths is not None:
+            lengths = _summ.check_lengths(lengths, int(states.shape[0]), int(states.shape[1]), self.diff)[:n]
+        x = self.rows(states[:n], actions[:n], dtype, lengths=lengths)
         dev = x.device
         with _lib.on_device(dev):
             mean = torch.empty(self.row_dim, dtype=torch.float64, device=dev)
@@ -166,10 +202,13 @@ class KernelMeanEmbedding(FrozenStatistic):
             self._coeff[prec.itemsize] = buf
         return self._coeff[prec.itemsize][:, :self.row_dim]
 
-    def forward(self, states, actions, out=None, check_finite=True, dtype=None):
+    def forward(self, states, actions, out=None, check_finite=True, dtype=None, lengths=None):
         """The embedding rows ``[N, n_feat]``.  ``out=``, ``check_finite`` and ``dtype=torch.float64`` are
         ``cross_correlation``'s.  RuntimeError before the scale exists; NotImplementedError when a block of
-        rows does not fit a workgroup's LDS."""
+        rows does not fit a workgroup's LDS.  ``lengths`` (``summarizers.check_lengths``,
+        include/bsig_ragged.h): the valid states of every trajectory -- row n is, bit for bit, the row of the
+        one trajectory sliced to them; lengths on the device are never read back here (one outside the range
+        makes its row NaN and fails the finite check); ``None``: the call it always was."""
         prec = _summ._precision(dtype)
         self.require_ready()
         assert len(states.shape) == 3, 'Need states: ntraj x n_steps x state_dim'
@@ -178,6 +217,8 @@ class KernelMeanEmbedding(FrozenStatistic):
             'trajectories of other dimensions'
         steps = states.shape[1] - (1 if self.diff else 0)
         assert steps >= 1, 'Need %d states or more' % (2 if self.diff else 1)
+        if lengths is not None:
+            lengths = _summ.check_lengths(lengths, int(states.shape[0]), int(states.shape[1]), self.diff)
         dev = self._on_gpu()
         home = states.device
         with _lib.on_device(dev):
@@ -186,8 +227,14 @@ class KernelMeanEmbedding(FrozenStatistic):
             coeff = self.coefficients(dtype)
             buf, ld = _summ._alloc(n, self.n_feat, dev, out, prec)
             flag, read_back = _summ._finite_flag(check_finite, dev)
-            prec.kme(_lib.ptr(s), _lib.ptr(a), _lib.ptr(coeff), coeff.stride(0), _lib.ptr(buf), n, ts, a.shape[1],
-                     sd, a.shape[2], self.n_feat // 2, int(self.diff), int(self.time), ld, _lib.ptr(flag),
-                     _lib.stream())
+            if lengths is None:
+                prec.kme(_lib.ptr(s), _lib.ptr(a), _lib.ptr(coeff), coeff.stride(0), _lib.ptr(buf), n, ts,
+                         a.shape[1], sd, a.shape[2], self.n_feat // 2, int(self.diff), int(self.time), ld,
+                         _lib.ptr(flag), _lib.stream())
+            else:
+                lens = _summ._lengths_on(lengths, dev)
+                prec.kme_ragged(_lib.ptr(s), _lib.ptr(a), _lib.ptr(lens), _lib.ptr(coeff), coeff.stride(0),
+                                _lib.ptr(buf), n, ts, a.shape[1], sd, a.shape[2], self.n_feat // 2, int(self.diff),
+                                int(self.time), ld, _lib.ptr(flag), _lib.stream())
             _summ._assert_finite(flag, read_back)
         return _summ._finish(buf, n, self.n_feat, home, out)

@@ -83,3 +83,18 @@ def pendulum_pairs(n, traj_len, policy='random', lows=(0.01, 0.01), highs=(2.0, 
     actions[:, traj_len] = actions[:, traj_len - 1]             # pad (summarizers.py:52-58)
     to = lambda a: torch.from_numpy(a).float().to(device)      # noqa: E731
     return to(theta), to(states), to(actions)
+
+
+def end_episodes(states, actions, lengths):
+    """Copies of ``states`` [N, T, sd] and ``actions`` [N, Ta, ad] as a recorder leaves episodes that ended
+    early: trajectory n's states from ``lengths[n]`` on repeat state ``lengths[n] - 1`` and its actions from step
+    ``lengths[n] - 1`` on repeat the last valid action, ``lengths[n] - 2`` (``pad_states_actions``' rule at the
+    episode's own end).  ``lengths``: N integers in 2..T, the valid STATES -- what ``summary_xcorr`` and
+    ``summary_kme`` take as ``lengths=``."""
+    lens = lengths if torch.is_tensor(lengths) else torch.as_tensor(np.asarray(lengths))
+    lens = lens.to(device=states.device, dtype=torch.int64)
+    assert lens.shape == (states.shape[0],) and int(lens.min()) >= 2 and int(lens.max()) <= states.shape[1]
+    t_s = torch.arange(states.shape[1], device=states.device)[None, :].minimum(lens[:, None] - 1)
+    t_a = torch.arange(actions.shape[1], device=states.device)[None, :].minimum(lens[:, None] - 2)
+    rows = torch.arange(states.shape[0], device=states.device)[:, None]
+    return states[rows, t_s].clone(), actions[rows, t_a].clone()

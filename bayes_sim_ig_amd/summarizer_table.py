@@ -11,6 +11,7 @@ An entry (``Summarizer``) holds:
 - ``lazy``: it takes ``lazy=True`` (summarizers.CrossCorrFactors).
 - ``embedding``: None, or ``(model_cfg, obs_dim, act_dim, device) ->`` the module it is called with as its third
   positional argument (``model_cfg`` has been through ``configure``).
+- ``ragged``: it takes ``lengths=``, the valid states of every trajectory (include/bsig_ragged.h).
 """
 from collections import namedtuple
 
@@ -20,8 +21,8 @@ from . import _lib
 from . import summarizers as _summ
 from .kme import KernelMeanEmbedding
 
-Summarizer = namedtuple('Summarizer', 'fxn keys configure check_finite lazy embedding',
-                        defaults=(False, False, None))
+Summarizer = namedtuple('Summarizer', 'fxn keys configure check_finite lazy embedding ragged',
+                        defaults=(False, False, None, False))
 
 
 def given(model_cfg, key):
@@ -134,6 +135,7 @@ SUMMARIZERS = {
                                    lazy=True),
     'summary_signatory': Summarizer(_summ.summary_signatory, _SIG_KEYS, _signatory),
     'summary_logsignature': Summarizer(_summ.summary_logsignature, _SIG_KEYS, _logsignature),
-    'summary_xcorr': Summarizer(_summ.summary_xcorr, _XCORR_KEYS, _xcorr, check_finite=True),
-    'summary_kme': Summarizer(_summ.summary_kme, _KME_KEYS, _kme, check_finite=True, embedding=_kme_embedding),
+    'summary_xcorr': Summarizer(_summ.summary_xcorr, _XCORR_KEYS, _xcorr, check_finite=True, ragged=True),
+    'summary_kme': Summarizer(_summ.summary_kme, _KME_KEYS, _kme, check_finite=True, embedding=_kme_embedding,
+                              ragged=True),
 }

@@ -17,6 +17,7 @@ precision seam (``_lib.F32`` / ``_lib.F64``).
 import ctypes as C
 import operator
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -63,6 +64,47 @@ def _finish(buf, n, width, home, out):
     if out is None and home != buf.device:
         res = res.to(home)
     return res
+
+
+def check_lengths(lengths, n, ts, diff, name='lengths'):
+    """``lengths`` of ``summary_xcorr`` / ``summary_kme`` (include/bsig_ragged.h) before any GPU call: an int32 /
+    int64 tensor, a numpy integer array or a list of ``n`` values, the valid STATES of every trajectory.
+    ValueError for another shape or a dtype that is not an integer's.  Lengths on the host are range-checked
+    here -- ``Lmin..ts``, Lmin = 2 where differences are formed (``diff``), else 1 -- and the ValueError names the
+    first index outside; they come back as a CPU int32 tensor.  Lengths on the device come back as they are and
+    are never read back: a length outside the range makes its row NaN and raises the finite flag."""
+    if torch.is_tensor(lengths):
+        if lengths.dtype not in (torch.int32, torch.int64):
+            raise ValueError('%s must hold integers (int32 or int64), got dtype %s' % (name, lengths.dtype))
+        if tuple(lengths.shape) != (n,):
+            raise ValueError('%s must hold one value per trajectory, shape (%d,), got %r'
+                             % (name, n, tuple(lengths.shape)))
+        if lengths.is_cuda:
+            return lengths
+        host = lengths.detach().numpy()
+    else:
+        host = np.asarray(lengths)
+        if host.size == 0 and host.ndim == 1:      # (an empty list has no dtype of its own)
+            host = host.astype(np.int64)
+        if host.dtype.kind not in 'iu':
+            raise ValueError('%s must hold integers, got dtype %s' % (name, host.dtype))
+        if host.shape != (n,):
+            raise ValueError('%s must hold one value per trajectory, shape (%d,), got %r'
+                             % (name, n, tuple(host.shape)))
+    lmin = 2 if diff else 1
+    outside = np.flatnonzero((host < lmin) | (host > ts))
+    if outside.size:
+        i = int(outside[0])
+        raise ValueError('%s[%d] = %d is outside %d..%d (the valid states of a trajectory of %d)'
+                         % (name, i, int(host[i]), lmin, ts, ts))
+    return torch.from_numpy(host.astype(np.int32))
+
+
+def _lengths_on(lengths, device):
+    """What ``check_lengths`` returned as the contiguous int32 device vector the kernels read."""
+    if lengths.dtype == torch.int64:      # (a device value beyond int32 stays outside every range)
+        lengths = lengths.clamp(min=-1, max=2 ** 31 - 1)
+    return lengths.to(device=device, dtype=torch.int32).contiguous()
 
 
 def summary_dim(name, traj_len, obs_dim, act_dim, depth=0):
@@ -287,7 +329,8 @@ def _xcorr_lag(max_lag):
     return max(min(lag, 2 ** 31 - 1), -1)
 
 
-def summary_xcorr(states, actions, max_lag=0, state_diff=True, out=None, check_finite=True, dtype=None):
+def summary_xcorr(states, actions, max_lag=0, state_diff=True, out=None, check_finite=True, dtype=None,
+                  lengths=None):
     """The time-lagged cross-correlation summary of the BayesSim paper (RSS 2019, section IV.F; not in the
     reference, whose ``cross_correlation`` is another statistic): with ``f_t = s_(t+1) - s_t``, the difference
     in TIME (``state_diff=False``: ``f_t = s_t``), M such steps, and the actions padded as
@@ -295,6 +338,13 @@ def summary_xcorr(states, actions, max_lag=0, state_diff=True, out=None, check_f
     ``c_tau[i, j] = 1/(M - tau) * sum_t f_(t+tau),i * a_t,j`` flattened with i major, then the mean and the
     population standard deviation of every ``f_.,i`` -- ``xcorr_dim(sd, ad, max_lag)`` numbers from the whole
     trajectory, whatever its length (include/bsig_xcorr.h, csrc/xcorr.h).
+
+    ``lengths`` (include/bsig_ragged.h; ``check_lengths``): the valid states ``L_n`` of every trajectory, for
+    recorded episodes that end early and whose tail the recorder filled.  Row n is then, bit for bit, the row of
+    ``states[n:n + 1, :L_n]`` and ``actions[n:n + 1]``; a lag with no term (``tau >= M_n``) is a block of zeros;
+    ``max_lag`` is still checked against the M of the whole tensor.  Lengths on the host are range-checked
+    here; lengths on the device are never read back: one outside ``2..ts`` (``1..ts`` without ``state_diff``)
+    makes its row NaN and fails the finite check.  ``None``: the call it always was.
 
     ``out=``, ``check_finite`` and ``dtype=torch.float64`` are ``cross_correlation``'s.  ValueError (before
     any GPU call) for a ``max_lag`` outside ``0..M-1``; NotImplementedError when a trajectory does not fit a
@@ -307,15 +357,23 @@ def summary_xcorr(states, actions, max_lag=0, state_diff=True, out=None, check_f
     assert m >= 1, 'Need %d states or more' % (2 if state_diff else 1)
     if not 0 <= lag <= m - 1:
         raise ValueError('max_lag %r is outside 0..%d: the feature series has %d steps' % (max_lag, m - 1, m))
+    if lengths is not None:
+        lengths = check_lengths(lengths, states.shape[0], states.shape[1], state_diff)
     s, a, home = _prep(states, actions, prec)
     n, t, sd = s.shape
     ad = a.shape[2]
     width = xcorr_dim(sd, ad, lag)
     buf, ld = _alloc(n, width, s.device, out, prec)
     flag, read_back = _finite_flag(check_finite, s.device)
-    prec.xcorr(
-        _lib.ptr(s), _lib.ptr(a), _lib.ptr(buf), n, t, a.shape[1], sd, ad, lag,
-        1 if state_diff else 0, ld, _lib.ptr(flag), _lib.stream())
+    if lengths is None:
+        prec.xcorr(
+            _lib.ptr(s), _lib.ptr(a), _lib.ptr(buf), n, t, a.shape[1], sd, ad, lag,
+            1 if state_diff else 0, ld, _lib.ptr(flag), _lib.stream())
+    else:
+        lens = _lengths_on(lengths, s.device)
+        prec.xcorr_ragged(
+            _lib.ptr(s), _lib.ptr(a), _lib.ptr(lens), _lib.ptr(buf), n, t, a.shape[1], sd, ad, lag,
+            1 if state_diff else 0, ld, _lib.ptr(flag), _lib.stream())
     _assert_finite(flag, read_back)
     return _finish(buf, n, width, home, out)
 
@@ -336,7 +394,7 @@ def kme_row_dim(obs_dim, act_dim, diff=True, time=False):
     return d
 
 
-def summary_kme(states, actions, embedding, out=None, check_finite=True, dtype=None):
+def summary_kme(states, actions, embedding, out=None, check_finite=True, dtype=None, lengths=None):
     """The random-feature kernel mean embedding of the trajectories' transitions (not in the reference): with
     the rows ``x_t = [tau_t? | s_t | a_t | s_(t+1) - s_t]``, M of them, the actions padded as
     ``pad_states_actions`` leaves them, and ``z_t = coeff x_t``, the row is
@@ -344,9 +402,14 @@ def summary_kme(states, actions, embedding, out=None, check_finite=True, dtype=N
     whatever its length and dimensions (include/bsig_kme.h, csrc/kme.h).  ``embedding`` is a
     ``kme.KernelMeanEmbedding``: the frequencies, the per-column scale and the row's layout.
 
+    ``lengths``: as ``summary_xcorr``'s (include/bsig_ragged.h): row n is, bit for bit, the row of the one
+    trajectory sliced to its ``L_n`` valid states; ``None``: the call it always was.
+
     ``out=``, ``check_finite`` and ``dtype=torch.float64`` are ``cross_correlation``'s.  RuntimeError while the
     embedding has no scale; NotImplementedError when a block of rows does not fit a workgroup's LDS."""
-    return embedding(states, actions, out=out, check_finite=check_finite, dtype=dtype)
+    if lengths is None:
+        return embedding(states, actions, out=out, check_finite=check_finite, dtype=dtype)
+    return embedding(states, actions, out=out, check_finite=check_finite, dtype=dtype, lengths=lengths)
 
 
 def signature_depth(ndim):
