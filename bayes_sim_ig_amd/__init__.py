@@ -16,4 +16,4 @@ from .summarizers import (pad_states_actions, summary_start, summary_waypts,  # 
                           summary_corr, summary_corrdiff, summary_signatory,
                           signature_depth, cross_correlation, summary_logsignature,
                           logsignature_dim, lyndon_words, summary_xcorr, xcorr_dim,
-                          summary_kme, kme_row_dim)
+                          summary_kme, kme_row_dim, summary_sysid, sysid_dim)

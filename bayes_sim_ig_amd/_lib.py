@@ -305,6 +305,14 @@ HEADERS['bsig_ragged.h'] = {
     'bsig_kme_rows_ragged': (C.c_int, [vp, vp, vp, vp, vp, i64] + [C.c_int] * 6 + [i64, vp]),
     'bsig_kme_rows_ragged_f64': (C.c_int, [vp, vp, vp, vp, vp, i64] + [C.c_int] * 6 + [i64, vp]),
 }
+# the least-squares dynamics summary
+HEADERS['bsig_sysid.h'] = {
+    'bsig_sysid_dim': (i64, [C.c_int] * 2),
+    'bsig_sysid_fits': (C.c_int, [C.c_int] * 5),
+    'bsig_sysid_group': (C.c_int, [C.c_int] * 5),
+    'bsig_sysid': (C.c_int, [vp, vp, vp, i64] + [C.c_int] * 4 + [f64, i64, vp, vp]),
+    'bsig_sysid_f64': (C.c_int, [vp, vp, vp, i64] + [C.c_int] * 4 + [f64, i64, vp, vp]),
+}
 COMM_ID_BYTES = 128
 EXCHANGE_SUM, EXCHANGE_BROADCAST = 0, 1
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int, vp, i64, C.c_int, vp)
@@ -449,6 +457,7 @@ class Precision:
         'xcorr_ragged': ('bsig_xcorr_ragged', 'bsig_xcorr_ragged_f64'),
         'kme_ragged': ('bsig_kme_ragged', 'bsig_kme_ragged_f64'),
         'kme_rows_ragged': ('bsig_kme_rows_ragged', 'bsig_kme_rows_ragged_f64'),
+        'sysid': ('bsig_sysid', 'bsig_sysid_f64'),
         # the input-side companions of normalize_rows / copy_rows (the statistics of rows, and the copy that
         # standardises)
         'input_norm_stats': ('bsig_input_norm_stats', 'bsig_input_norm_stats_f64'),

@@ -22,7 +22,7 @@ from .summarizers import check_lengths as _check_lengths
 from .summarizers import (pad_states_actions, summary_start, summary_waypts,  # noqa: F401
                           summary_corr, summary_corrdiff, summary_signatory,
                           signature_depth, cross_correlation, summary_logsignature,
-                          summary_xcorr, summary_kme)
+                          summary_xcorr, summary_kme, summary_sysid)
 
 _MODELS = {'MDNN': MDNN, 'MDRFF': MDRFF}
 
@@ -76,6 +76,14 @@ class BayesSim(object):
           - ``kmeSeed``: an int >= 0, default 0, the frequencies' own generator;
           - ``kmeDiff``: a bool, default True; False: no state differences in the rows;
           - ``kmeTime``: a bool, default False; True: the step's position leads the row.
+        - ``'summarizerFxn': 'summary_sysid'``: the ridge least-squares fit of ``s_(t+1) - s_t`` on
+          ``[1 | s_t | a_t]`` over the trajectory's own steps and the root mean square of what it leaves,
+          ``sysid_dim`` deterministic inputs from the whole trajectory; a shape that does not fit a
+          workgroup's LDS at ``trainTrajLen`` is a NotImplementedError here; include/bsig_sysid.h.  Its own
+          key:
+
+          - ``sysidRidge``: a positive float, default 1e-3, times the mean diagonal of the Gram matrix; the
+            solved system's condition number is at most 1 + (1 + obs_dim + act_dim) / sysidRidge.
         - ``dtype``: 'float32', the default, or 'float64': the estimator's fp64 mode, as ``bs.model.double()``.
         - ``summaryDtype``: 'float32', the default in both modes: the summaries are made in fp32 and a double
           model gets them widened.  'float64', only with ``'dtype': 'float64'``: the summarizers compute in

@@ -123,6 +123,17 @@ def _kme_embedding(model_cfg, obs_dim, act_dim, device):
     return KernelMeanEmbedding(obs_dim, act_dim, device=device, **_kme_arguments(model_cfg))
 
 
+def _sysid(model_cfg, obs_dim, act_dim, itemsize):
+    # include/bsig_sysid.h: the key, then the trajectory and the system it solves against the LDS
+    ridge = _summ.sysid_ridge(model_cfg.get('sysidRidge', 1e-3), "model_cfg['sysidRidge']")
+    length = model_cfg['trainTrajLen']
+    if length < 2:
+        raise ValueError("model_cfg['trainTrajLen'] = %d leaves no step to fit" % (length,))
+    width = _summ.sysid_dim(obs_dim, act_dim)
+    _lib.check(_lib.load().bsig_sysid_fits(length, length, obs_dim, act_dim, itemsize))
+    return width, {'ridge': ridge}
+
+
 _SIG_KEYS = {'sigChannels': 'summary_signatory'}
 _XCORR_KEYS = dict.fromkeys(('xcorrLags', 'xcorrStateDiff'), 'summary_xcorr')
 _KME_KEYS = dict.fromkeys(('kmeFeatures', 'kmeScale', 'kmeSeed', 'kmeDiff', 'kmeTime'), 'summary_kme')
@@ -138,4 +149,5 @@ SUMMARIZERS = {
     'summary_xcorr': Summarizer(_summ.summary_xcorr, _XCORR_KEYS, _xcorr, check_finite=True, ragged=True),
     'summary_kme': Summarizer(_summ.summary_kme, _KME_KEYS, _kme, check_finite=True, embedding=_kme_embedding,
                               ragged=True),
+    'summary_sysid': Summarizer(_summ.summary_sysid, {'sysidRidge': 'summary_sysid'}, _sysid, check_finite=True),
 }

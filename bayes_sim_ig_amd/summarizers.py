@@ -378,6 +378,64 @@ def summary_xcorr(states, actions, max_lag=0, state_diff=True, out=None, check_f
     return _finish(buf, n, width, home, out)
 
 
+def sysid_dim(obs_dim, act_dim):
+    """Width of a ``summary_sysid`` row, ``(1 + obs_dim + act_dim) * obs_dim + obs_dim``, without touching the
+    GPU (bsig_sysid_dim, include/bsig_sysid.h).  ValueError for a dimension below 1 or a width past 2^31 - 1."""
+    try:
+        sd, ad = operator.index(obs_dim), operator.index(act_dim)
+    except TypeError:
+        raise ValueError('obs_dim and act_dim must be ints >= 1, got %r, %r' % (obs_dim, act_dim)) from None
+    ok = 1 <= sd < 2 ** 31 and 1 <= ad < 2 ** 31
+    width = int(_lib.load().bsig_sysid_dim(sd, ad)) if ok else -1
+    if width < 0:
+        raise ValueError('no dynamics-fit row for obs_dim=%r, act_dim=%r (dimensions >= 1, width below 2^31)'
+                         % (obs_dim, act_dim))
+    return width
+
+
+def sysid_ridge(ridge, name='ridge'):
+    """``ridge`` of ``summary_sysid`` as a float; ValueError unless it is a positive finite float (an int or a
+    bool is not) that stays positive in fp32."""
+    if not isinstance(ridge, float) or not (np.isfinite(ridge) and np.float32(ridge) > 0.0):
+        raise ValueError('%s must be a positive float, got %r' % (name, ridge))
+    return ridge
+
+
+def summary_sysid(states, actions, ridge=1e-3, out=None, check_finite=True, dtype=None):
+    """The least-squares dynamics summary of every trajectory (not in the reference): the ridge fit of
+    ``y_t = s_(t+1) - s_t`` on ``phi_t = [1 | s_t | a_t]`` over the trajectory's own M = T - 1 steps, the
+    actions padded as ``pad_states_actions`` leaves them.  With ``G = 1/M sum phi_t phi_t^T``,
+    ``B = 1/M sum phi_t y_t^T`` and ``rho = ridge * trace(G) / p``, p = 1 + sd + ad, the row is
+    ``[W | r]``: ``W = (G + rho I)^-1 B`` row-major, then ``r_j = sqrt(1/M sum_t (y_tj - phi_t . W_:j)^2)`` --
+    ``sysid_dim(sd, ad)`` deterministic numbers, whatever the trajectory's length (include/bsig_sysid.h,
+    csrc/sysid.h).  The condition number of the solved system is at most ``1 + p / ridge``: where
+    ``p^2 * 6e-8 / ridge`` nears 1, compute in double.
+
+    ``out=``, ``check_finite`` and ``dtype=torch.float64`` are ``cross_correlation``'s; a trajectory with a
+    non-finite value, or whose factorisation meets a pivot that is not positive, has a row of NaN and fails
+    the finite check.  ValueError (before any GPU call) for a ``ridge`` that is not a positive float or
+    fewer than two states; NotImplementedError when a trajectory does not fit a workgroup's LDS."""
+    prec = _precision(dtype)
+    ridge = sysid_ridge(ridge)
+    assert len(states.shape) == 3, 'Need states: ntraj x n_steps x state_dim'
+    assert len(actions.shape) == 3, 'Need actions: ntraj x n_steps x state_dim'
+    if states.shape[1] < 2:
+        raise ValueError('summary_sysid needs 2 states or more, got %d' % (states.shape[1],))
+    if actions.shape[1] < 1:
+        raise ValueError('summary_sysid needs 1 action or more, got %d' % (actions.shape[1],))
+    width = sysid_dim(states.shape[2], actions.shape[2])
+    s, a, home = _prep(states, actions, prec)
+    n, t, sd = s.shape
+    ad = a.shape[2]
+    buf, ld = _alloc(n, width, s.device, out, prec)
+    flag, read_back = _finite_flag(check_finite, s.device)
+    with _lib.on_device(s.device):
+        prec.sysid(_lib.ptr(s), _lib.ptr(a), _lib.ptr(buf), n, t, a.shape[1], sd, ad, ridge, ld,
+                   _lib.ptr(flag), _lib.stream(s.device))
+    _assert_finite(flag, read_back)
+    return _finish(buf, n, width, home, out)
+
+
 def kme_row_dim(obs_dim, act_dim, diff=True, time=False):
     """Width d of a transition row ``[tau? | s | a | ds?]`` of ``summary_kme``: ``2 * obs_dim + act_dim`` with
     the differences, ``obs_dim + act_dim`` without, one more with the time column -- without touching the GPU

@@ -32,13 +32,13 @@ build_one() {  # name, source, extra flags
 }
 [ -n "$WIDE_TILES" ] || rm -f "$OUT"/obj/gemm_tile_128x288.* "$OUT"/obj/gemm_tile_288x128.*
 rm -f "$OUT"/obj/fit_persistent_v1.*      # (retired in round 6: an object of an older build must not be linked)
-for f in summarizers gemm_f32 gemm_tile_64 gemm_tile_128 gemm_tile_128x32 gemm_tile_128x64 gemm_tile_128x96 gemm_tile_96x128 gemm_lean_64 gemm_lean_128 gemm_lean_128x32 gemm_lean_128x64 gemm_lean_128x96 gemm_lean_96x128 gemm_wide gemm_split_bf16 $WIDE_TILES mdn_head flat_ops estimator fit_persistent fit_deferred_eval fit_persistent_mdnn fit_persistent_mdnn_stream signature_ex logsignature input_norm rff_bandwidth xcorr kme xcorr_ragged kme_ragged; do
+for f in summarizers gemm_f32 gemm_tile_64 gemm_tile_128 gemm_tile_128x32 gemm_tile_128x64 gemm_tile_128x96 gemm_tile_96x128 gemm_lean_64 gemm_lean_128 gemm_lean_128x32 gemm_lean_128x64 gemm_lean_128x96 gemm_lean_96x128 gemm_wide gemm_split_bf16 $WIDE_TILES mdn_head flat_ops estimator fit_persistent fit_deferred_eval fit_persistent_mdnn fit_persistent_mdnn_stream signature_ex logsignature input_norm rff_bandwidth xcorr kme xcorr_ragged kme_ragged sysid; do
   build_one "$f" "$SRC/$f.hip" ""
 done
 for f in api comm; do
   build_one "$f" "$SRC/$f.cpp" "-x hip"
 done
-for f in gemm_f64 mdn_head_f64 flat_ops_f64 estimator_f64 summarizers_f64 signature_ex_f64 logsignature_f64 input_norm_f64 xcorr_f64 kme_f64 xcorr_ragged_f64 kme_ragged_f64; do
+for f in gemm_f64 mdn_head_f64 flat_ops_f64 estimator_f64 summarizers_f64 signature_ex_f64 logsignature_f64 input_norm_f64 xcorr_f64 kme_f64 xcorr_ragged_f64 kme_ragged_f64 sysid_f64; do
   build_one "$f" "$SRC/f64/$f.hip" ""
 done
 rc=0
