@@ -10,6 +10,7 @@ The product path has NO fallback: if the library is missing or there is no
 GPU, every compute entry point raises.  torch is used only for device memory,
 streams and torch.distributed.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -571,6 +572,15 @@ def on_device(device):
     """Context: make ``device`` the current HIP device (kernels launch on the current
     device; a model built on cuda:1 must not launch on cuda:0's stream)."""
     return torch.cuda.device(device)
+
+
+@contextlib.contextmanager
+def device_stream(device):
+    """Context: ``on_device(device)``, yielding ``stream(device)`` -- the ONE rule for where a call of the
+    summarizers, the embedding and the RFF map launches: on the device its rows live on, on that device's
+    current torch stream, whichever device was current before (and is again afterwards)."""
+    with on_device(device):
+        yield stream(device)
 
 
 def as_rows(t, device=None, dtype=torch.float32):

@@ -109,8 +109,8 @@ class KernelMeanEmbedding(FrozenStatistic):
         if lengths is not None:
             return self._valid_rows(states, actions, prec, lengths)
         dev = self._on_gpu()
-        with _lib.on_device(dev):
-            s, a, _ = _summ._prep(states.to(dev), actions.to(dev), prec)
+        with _lib.device_stream(dev) as stream:
+            s, a, _ = _summ._prep(states, actions, prec, dev)
             n, ts, sd = s.shape
             assert (sd, a.shape[2]) == (self.obs_dim, self.act_dim), 'trajectories of other dimensions'
             steps = ts - (1 if self.diff else 0)
@@ -118,7 +118,7 @@ class KernelMeanEmbedding(FrozenStatistic):
             ld = _lib.round_up(self.row_dim, 16 // prec.itemsize)
             buf = torch.empty((n * steps, ld), dtype=prec.dtype, device=dev)
             prec.kme_rows(_lib.ptr(s), _lib.ptr(a), _lib.ptr(buf), n, ts, a.shape[1], sd, a.shape[2],
-                          int(self.diff), int(self.time), ld, _lib.stream())
+                          int(self.diff), int(self.time), ld, stream)
         return buf[:, :self.row_dim]
 
     def _valid_rows(self, states, actions, prec, lengths):
@@ -133,15 +133,15 @@ class KernelMeanEmbedding(FrozenStatistic):
         offsets = torch.cumsum(steps, 0) - steps
         total = int(steps.sum())
         dev = self._on_gpu()
-        with _lib.on_device(dev):
-            s, a, _ = _summ._prep(states.to(dev), actions.to(dev), prec)
+        with _lib.device_stream(dev) as stream:
+            s, a, _ = _summ._prep(states, actions, prec, dev)
             sd = s.shape[2]
             assert (sd, a.shape[2]) == (self.obs_dim, self.act_dim), 'trajectories of other dimensions'
             ld = _lib.round_up(self.row_dim, 16 // prec.itemsize)
             buf = torch.empty((total, ld), dtype=prec.dtype, device=dev)
             lens, offs = _summ._lengths_on(lengths, dev), offsets.to(dev)
             prec.kme_rows_ragged(_lib.ptr(s), _lib.ptr(a), _lib.ptr(lens), _lib.ptr(offs), _lib.ptr(buf), n, ts,
-                                 a.shape[1], sd, a.shape[2], int(self.diff), int(self.time), ld, _lib.stream())
+                                 a.shape[1], sd, a.shape[2], int(self.diff), int(self.time), ld, stream)
         return buf[:, :self.row_dim]
 
     def fit_scale(self, states, actions, dtype=None, lengths=None):
@@ -162,7 +162,7 @@ class KernelMeanEmbedding(FrozenStatistic):
             lengths = _summ.check_lengths(lengths, int(states.shape[0]), int(states.shape[1]), self.diff)[:n]
         x = self.rows(states[:n], actions[:n], dtype, lengths=lengths)
         dev = x.device
-        with _lib.on_device(dev):
+        with _lib.device_stream(dev):      # (column_statistics launches on the current device's stream)
             mean = torch.empty(self.row_dim, dtype=torch.float64, device=dev)
             column_statistics(prec, x, x.stride(0), x.shape[0], self.row_dim, mean, self.inv_std,
                               lambda numel: torch.empty(numel, dtype=torch.float64, device=dev))
@@ -196,9 +196,9 @@ class KernelMeanEmbedding(FrozenStatistic):
             m, d = self.n_feat // 2, self.row_dim
             ld = _lib.round_up(d, 16 // prec.itemsize)
             buf = torch.empty((m, ld), dtype=prec.dtype, device=dev)
-            with _lib.on_device(dev):
+            with _lib.device_stream(dev) as stream:
                 prec.kme_coeff(_lib.ptr(self.freqs), d, _lib.ptr(self.inv_std), self.kappa, _lib.ptr(buf), ld, m,
-                               d, _lib.stream())
+                               d, stream)
             self._coeff[prec.itemsize] = buf
         return self._coeff[prec.itemsize][:, :self.row_dim]
 
@@ -211,8 +211,7 @@ class KernelMeanEmbedding(FrozenStatistic):
         makes its row NaN and fails the finite check); ``None``: the call it always was."""
         prec = _summ._precision(dtype)
         self.require_ready()
-        assert len(states.shape) == 3, 'Need states: ntraj x n_steps x state_dim'
-        assert len(actions.shape) == 3, 'Need actions: ntraj x n_steps x state_dim'
+        _summ._need_trajectories(states, actions)
         assert (states.shape[2], actions.shape[2]) == (self.obs_dim, self.act_dim), \
             'trajectories of other dimensions'
         steps = states.shape[1] - (1 if self.diff else 0)
@@ -220,21 +219,14 @@ class KernelMeanEmbedding(FrozenStatistic):
         if lengths is not None:
             lengths = _summ.check_lengths(lengths, int(states.shape[0]), int(states.shape[1]), self.diff)
         dev = self._on_gpu()
-        home = states.device
-        with _lib.on_device(dev):
-            s, a, _ = _summ._prep(states.to(dev), actions.to(dev), prec)
-            n, ts, sd = s.shape
+
+        def launch(s, a, buf, ld, flag, stream):
             coeff = self.coefficients(dtype)
-            buf, ld = _summ._alloc(n, self.n_feat, dev, out, prec)
-            flag, read_back = _summ._finite_flag(check_finite, dev)
+            tail = (_lib.ptr(coeff), coeff.stride(0), _lib.ptr(buf), s.shape[0], s.shape[1], a.shape[1], s.shape[2],
+                    a.shape[2], self.n_feat // 2, int(self.diff), int(self.time), ld, _lib.ptr(flag), stream)
             if lengths is None:
-                prec.kme(_lib.ptr(s), _lib.ptr(a), _lib.ptr(coeff), coeff.stride(0), _lib.ptr(buf), n, ts,
-                         a.shape[1], sd, a.shape[2], self.n_feat // 2, int(self.diff), int(self.time), ld,
-                         _lib.ptr(flag), _lib.stream())
+                prec.kme(_lib.ptr(s), _lib.ptr(a), *tail)
             else:
                 lens = _summ._lengths_on(lengths, dev)
-                prec.kme_ragged(_lib.ptr(s), _lib.ptr(a), _lib.ptr(lens), _lib.ptr(coeff), coeff.stride(0),
-                                _lib.ptr(buf), n, ts, a.shape[1], sd, a.shape[2], self.n_feat // 2, int(self.diff),
-                                int(self.time), ld, _lib.ptr(flag), _lib.stream())
-            _summ._assert_finite(flag, read_back)
-        return _summ._finish(buf, n, self.n_feat, home, out)
+                prec.kme_ragged(_lib.ptr(s), _lib.ptr(a), _lib.ptr(lens), *tail)
+        return _summ._launch_summary(states, actions, prec, self.n_feat, out, check_finite, launch, device=dev)

@@ -137,8 +137,9 @@ class RFF:
             ld = _lib.round_up(self.d, 4)
             if self._coeff is None or self._coeff.device != dev:
                 self._coeff = torch.empty((self.m_feat, ld), dtype=torch.float32, device=dev)
-            _lib.check(lib.bsig_rff_coeff_dev(_lib.ptr(fr), _lib.ptr(bw.sigma.to(dev)), _lib.ptr(self._coeff),
-                                              self.m_feat, self.d, ld, _lib.stream()))
+            with _lib.device_stream(dev) as stream:
+                _lib.check(lib.bsig_rff_coeff_dev(_lib.ptr(fr), _lib.ptr(bw.sigma.to(dev)), _lib.ptr(self._coeff),
+                                                  self.m_feat, self.d, ld, stream))
             self._coeff_version = bw.version
         return self._coeff
 
@@ -154,8 +155,9 @@ class RFF:
             sg = (self.sigma if sigma is None else sigma).to(dev).float().contiguous()
             ld = _lib.round_up(self.d, 4)
             co = torch.empty((self.m_feat, ld), dtype=torch.float32, device=dev)
-            _lib.check(lib.bsig_rff_coeff(_lib.ptr(fr), _lib.ptr(sg), _lib.ptr(co),
-                                          self.m_feat, self.d, ld, _lib.stream()))
+            with _lib.device_stream(dev) as stream:
+                _lib.check(lib.bsig_rff_coeff(_lib.ptr(fr), _lib.ptr(sg), _lib.ptr(co),
+                                              self.m_feat, self.d, ld, stream))
             if sigma is not None:
                 return co
             self._coeff = co
@@ -176,14 +178,15 @@ class RFF:
             self._ws = torch.empty(max(need // 4 + 1, 1), dtype=torch.float32,
                                    device=co.device)
         off = self.offset.to(co.device).contiguous() if cos_only else None
-        args = (_lib.ptr(xs), ldx, None, _lib.ptr(co), co.stride(0), _lib.ptr(off),
-                _lib.ptr(feats), feats.stride(0), b, self.d, self.m_feat,
-                float(self.a), 1 if cos_only else 0, _lib.ptr(self._ws),
-                self._ws.numel() * 4, _lib.stream())
-        if self.matmul_precision == 'float32':
-            _lib.check(lib.bsig_rff_project(*args))
-        else:
-            _lib.check(lib.bsig_rff_project_ex(*args, _lib.matmul_precision(self.matmul_precision)))
+        with _lib.device_stream(co.device) as stream:
+            args = (_lib.ptr(xs), ldx, None, _lib.ptr(co), co.stride(0), _lib.ptr(off),
+                    _lib.ptr(feats), feats.stride(0), b, self.d, self.m_feat,
+                    float(self.a), 1 if cos_only else 0, _lib.ptr(self._ws),
+                    self._ws.numel() * 4, stream)
+            if self.matmul_precision == 'float32':
+                _lib.check(lib.bsig_rff_project(*args))
+            else:
+                _lib.check(lib.bsig_rff_project_ex(*args, _lib.matmul_precision(self.matmul_precision)))
         return feats if home == feats.device else feats.to(home)
 
     def _to_cos_only_features(self, x, sigma=None):

@@ -34,13 +34,21 @@ def _precision(dtype):
     raise ValueError('summarizers compute in torch.float32 or torch.float64, got dtype=%r' % (dtype,))
 
 
-def _prep(states, actions, prec=_lib.F32):
+def _need_trajectories(states, actions):
     assert len(states.shape) == 3, 'Need states: ntraj x n_steps x state_dim'
     assert len(actions.shape) == 3, 'Need actions: ntraj x n_steps x state_dim'
+
+
+def _prep(states, actions, prec=_lib.F32, device=None):
+    """The trajectories in ``prec`` on a GPU -- ``device`` (they move there as they are, then convert), else
+    their own, else the current one -- and the device they came from."""
+    _need_trajectories(states, actions)
     assert states.shape[0] == actions.shape[0]
     _lib.require_gpu()
     home = states.device
-    dev = home if states.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    if device is not None:
+        states, actions = states.to(device), actions.to(device)
+    dev = states.device if states.is_cuda else torch.device('cuda', torch.cuda.current_device())
     if prec.itemsize == 8:      # the smaller form crosses the bus: widened (exactly) on the device
         s = states.to(device=dev).to(prec.dtype).contiguous()
         a = actions.to(device=dev).to(prec.dtype).contiguous()
@@ -64,6 +72,39 @@ def _finish(buf, n, width, home, out):
     if out is None and home != buf.device:
         res = res.to(home)
     return res
+
+
+def _finite_flag(check_finite, device):
+    """The flag word a cross-correlation kernel raises on a non-finite feature, and whether this call reads it
+    back.  ``check_finite`` may be a 1-element int32 device tensor: the kernel raises its flag there and the
+    caller asserts later (BayesSim.fit: one read-back for all chunks); None / False: no flag."""
+    if torch.is_tensor(check_finite):
+        return check_finite, False
+    if not check_finite:
+        return None, False
+    return torch.zeros(1, dtype=torch.int32, device=device), True
+
+
+def _assert_finite(flag, read_back):
+    if read_back:
+        assert int(flag.item()) == 0  # summarizers.py:120
+
+
+def _launch_summary(states, actions, prec, width, out, check_finite, launch, device=None):
+    """The host side of every ``[N, F]`` summary: the trajectories on a GPU (``_prep``), THAT device current and
+    its stream the library's, the rows (``out=`` or new), the finite flag (none for ``check_finite=False``), the
+    one library call ``launch(s, a, buf, ld, flag, stream)``, the flag's read-back, the ``[:n, :width]`` view back
+    where the inputs live.  ``width``: F, or ``(s, a) -> F`` where it, or an assert on the shapes, has to follow
+    the move to the GPU."""
+    s, a, home = _prep(states, actions, prec, device)
+    if callable(width):
+        width = width(s, a)
+    with _lib.device_stream(s.device) as stream:
+        buf, ld = _alloc(s.shape[0], width, s.device, out, prec)
+        flag, read_back = _finite_flag(check_finite, s.device)
+        launch(s, a, buf, ld, flag, stream)
+        _assert_finite(flag, read_back)
+    return _finish(buf, s.shape[0], width, home, out)
 
 
 def check_lengths(lengths, n, ts, diff, name='lengths'):
@@ -119,8 +160,7 @@ def pad_states_actions(states, actions, tgt_actions_len=None):
     """Reference summarizers.py:20-62 (plain slicing / repeat; no arithmetic).
     Unlike the reference, padding works for any batch size: each trajectory
     repeats its own last step."""
-    assert len(states.shape) == 3, 'Need states: ntraj x n_steps x state_dim'
-    assert len(actions.shape) == 3, 'Need actions: ntraj x n_steps x state_dim'
+    _need_trajectories(states, actions)
     if tgt_actions_len is None:
         tgt_actions_len = states.shape[1]
 
@@ -137,14 +177,13 @@ def pad_states_actions(states, actions, tgt_actions_len=None):
 def summary_start(states, actions, max_t=10, out=None, dtype=None):
     """Reference summarizers.py:65-70."""
     prec = _precision(dtype)
-    s, a, home = _prep(states, actions, prec)
-    n, sd, ad = s.shape[0], s.shape[2], a.shape[2]
-    width = max_t * (sd + ad)
-    buf, ld = _alloc(n, width, s.device, out, prec)
-    prec.summary_start(
-        _lib.ptr(s), _lib.ptr(a), _lib.ptr(buf), n, s.shape[1], a.shape[1],
-        sd, ad, max_t, ld, _lib.stream())
-    return _finish(buf, n, width, home, out)
+
+    def launch(s, a, buf, ld, flag, stream):
+        prec.summary_start(
+            _lib.ptr(s), _lib.ptr(a), _lib.ptr(buf), s.shape[0], s.shape[1], a.shape[1],
+            s.shape[2], a.shape[2], max_t, ld, stream)
+    return _launch_summary(states, actions, prec, lambda s, a: max_t * (s.shape[2] + a.shape[2]), out, False,
+                           launch)
 
 
 def summary_waypts(states, actions, n_waypts=10, out=None, dtype=None):
@@ -211,11 +250,11 @@ class CrossCorrFactors:
         lib = _lib.require_gpu()
         n, width = self.shape
         fac = self.factors if self.factors.stride(1) == 1 else self.factors.contiguous()
-        with _lib.on_device(fac.device):
+        with _lib.device_stream(fac.device) as stream:
             buf, ld = _alloc(n, width, fac.device, out)
             _lib.check(lib.bsig_crosscorr_expand(
                 _lib.ptr(fac), fac.stride(0) if n > 1 else fac.shape[1], n, self.s_dim, self.a_dim,
-                _lib.ptr(buf), ld, _lib.stream(fac.device)))
+                _lib.ptr(buf), ld, stream))
         return buf[:n, :width]
 
     @classmethod
@@ -236,22 +275,6 @@ class CrossCorrFactors:
         return self.materialize().to(*args, **kwargs)
 
 
-def _finite_flag(check_finite, device):
-    """The flag word a cross-correlation kernel raises on a non-finite feature, and whether this call reads it
-    back.  ``check_finite`` may be a 1-element int32 device tensor: the kernel raises its flag there and the
-    caller asserts later (BayesSim.fit: one read-back for all chunks); None / False: no flag."""
-    if torch.is_tensor(check_finite):
-        return check_finite, False
-    if not check_finite:
-        return None, False
-    return torch.zeros(1, dtype=torch.int32, device=device), True
-
-
-def _assert_finite(flag, read_back):
-    if read_back:
-        assert int(flag.item()) == 0  # summarizers.py:120
-
-
 def cross_correlation(states, actions, use_state_diff=False, out=None,
                       check_finite=True, lazy=False, dtype=None):
     """Reference summarizers.py:90-122.  ``lazy=True`` returns a CrossCorrFactors handle
@@ -263,19 +286,18 @@ def cross_correlation(states, actions, use_state_diff=False, out=None,
                 'lazy=True with dtype=torch.float64: there are no factor rows in double -- the fp64 fit '
                 'refuses them (bsig_fit64_bind: BSIG_X_CROSSCORR_FACTORS is BSIG_EUNSUPPORTED)')
         return _cross_correlation_factors(states, actions, use_state_diff, check_finite)
-    s, a, home = _prep(states, actions, prec)
-    n, t, sd = s.shape
-    ad = a.shape[2]
-    assert t > 1                      # summarizers.py:94
-    width = summary_dim('summary_corrdiff' if use_state_diff else 'summary_corr',
-                        t, sd, ad)
-    buf, ld = _alloc(n, width, s.device, out, prec)
-    flag, read_back = _finite_flag(check_finite, s.device)
-    prec.crosscorr(
-        _lib.ptr(s), _lib.ptr(a), _lib.ptr(buf), n, t, a.shape[1], sd, ad,
-        1 if use_state_diff else 0, ld, _lib.ptr(flag), _lib.stream())
-    _assert_finite(flag, read_back)
-    return _finish(buf, n, width, home, out)
+
+    def width(s, a):
+        assert s.shape[1] > 1         # summarizers.py:94
+        return summary_dim('summary_corrdiff' if use_state_diff else 'summary_corr',
+                           s.shape[1], s.shape[2], a.shape[2])
+
+    def launch(s, a, buf, ld, flag, stream):
+        n, t, sd = s.shape
+        prec.crosscorr(
+            _lib.ptr(s), _lib.ptr(a), _lib.ptr(buf), n, t, a.shape[1], sd, a.shape[2],
+            1 if use_state_diff else 0, ld, _lib.ptr(flag), stream)
+    return _launch_summary(states, actions, prec, width, out, check_finite, launch)
 
 
 def _cross_correlation_factors(states, actions, use_state_diff, check_finite):
@@ -289,10 +311,10 @@ def _cross_correlation_factors(states, actions, use_state_diff, check_finite):
     ld = _lib.round_up(s_dim.value + a_dim.value + 3, 4)
     fac = torch.empty((n, ld), dtype=torch.float32, device=s.device)
     flag, read_back = _finite_flag(check_finite, s.device)
-    with _lib.on_device(s.device):
+    with _lib.device_stream(s.device) as stream:
         _lib.check(lib.bsig_crosscorr_factors(
             _lib.ptr(s), _lib.ptr(a), _lib.ptr(fac), n, t, a.shape[1], sd, ad,
-            1 if use_state_diff else 0, ld, _lib.ptr(flag), _lib.stream(s.device)))
+            1 if use_state_diff else 0, ld, _lib.ptr(flag), stream))
     _assert_finite(flag, read_back)
     return CrossCorrFactors(fac, s_dim.value, a_dim.value)
 
@@ -351,46 +373,45 @@ def summary_xcorr(states, actions, max_lag=0, state_diff=True, out=None, check_f
     workgroup's LDS."""
     prec = _precision(dtype)
     lag = _xcorr_lag(max_lag)
-    assert len(states.shape) == 3, 'Need states: ntraj x n_steps x state_dim'
-    assert len(actions.shape) == 3, 'Need actions: ntraj x n_steps x state_dim'
+    _need_trajectories(states, actions)
     m = states.shape[1] - (1 if state_diff else 0)
     assert m >= 1, 'Need %d states or more' % (2 if state_diff else 1)
     if not 0 <= lag <= m - 1:
         raise ValueError('max_lag %r is outside 0..%d: the feature series has %d steps' % (max_lag, m - 1, m))
     if lengths is not None:
         lengths = check_lengths(lengths, states.shape[0], states.shape[1], state_diff)
-    s, a, home = _prep(states, actions, prec)
-    n, t, sd = s.shape
-    ad = a.shape[2]
-    width = xcorr_dim(sd, ad, lag)
-    buf, ld = _alloc(n, width, s.device, out, prec)
-    flag, read_back = _finite_flag(check_finite, s.device)
-    if lengths is None:
-        prec.xcorr(
-            _lib.ptr(s), _lib.ptr(a), _lib.ptr(buf), n, t, a.shape[1], sd, ad, lag,
-            1 if state_diff else 0, ld, _lib.ptr(flag), _lib.stream())
-    else:
-        lens = _lengths_on(lengths, s.device)
-        prec.xcorr_ragged(
-            _lib.ptr(s), _lib.ptr(a), _lib.ptr(lens), _lib.ptr(buf), n, t, a.shape[1], sd, ad, lag,
-            1 if state_diff else 0, ld, _lib.ptr(flag), _lib.stream())
-    _assert_finite(flag, read_back)
-    return _finish(buf, n, width, home, out)
+
+    def launch(s, a, buf, ld, flag, stream):
+        n, t, sd = s.shape
+        tail = (n, t, a.shape[1], sd, a.shape[2], lag, 1 if state_diff else 0, ld, _lib.ptr(flag), stream)
+        if lengths is None:
+            prec.xcorr(_lib.ptr(s), _lib.ptr(a), _lib.ptr(buf), *tail)
+        else:
+            lens = _lengths_on(lengths, s.device)
+            prec.xcorr_ragged(_lib.ptr(s), _lib.ptr(a), _lib.ptr(lens), _lib.ptr(buf), *tail)
+    return _launch_summary(states, actions, prec, lambda s, a: xcorr_dim(s.shape[2], a.shape[2], lag), out,
+                           check_finite, launch)
 
 
-def sysid_dim(obs_dim, act_dim):
-    """Width of a ``summary_sysid`` row, ``(1 + obs_dim + act_dim) * obs_dim + obs_dim``, without touching the
-    GPU (bsig_sysid_dim, include/bsig_sysid.h).  ValueError for a dimension below 1 or a width past 2^31 - 1."""
+def _obs_act_width(what, dim_fn, obs_dim, act_dim, *flags):
+    """``sysid_dim`` and ``kme_row_dim``: what the library's ``dim_fn`` answers for ints in 1..2^31 - 1, asked
+    for nothing else; ValueError for anything else or a negative answer (no ``what`` row)."""
     try:
         sd, ad = operator.index(obs_dim), operator.index(act_dim)
     except TypeError:
         raise ValueError('obs_dim and act_dim must be ints >= 1, got %r, %r' % (obs_dim, act_dim)) from None
     ok = 1 <= sd < 2 ** 31 and 1 <= ad < 2 ** 31
-    width = int(_lib.load().bsig_sysid_dim(sd, ad)) if ok else -1
+    width = int(getattr(_lib.load(), dim_fn)(sd, ad, *flags)) if ok else -1
     if width < 0:
-        raise ValueError('no dynamics-fit row for obs_dim=%r, act_dim=%r (dimensions >= 1, width below 2^31)'
-                         % (obs_dim, act_dim))
+        raise ValueError('no %s row for obs_dim=%r, act_dim=%r (dimensions >= 1, width below 2^31)'
+                         % (what, obs_dim, act_dim))
     return width
+
+
+def sysid_dim(obs_dim, act_dim):
+    """Width of a ``summary_sysid`` row, ``(1 + obs_dim + act_dim) * obs_dim + obs_dim``, without touching the
+    GPU (bsig_sysid_dim, include/bsig_sysid.h).  ValueError for a dimension below 1 or a width past 2^31 - 1."""
+    return _obs_act_width('dynamics-fit', 'bsig_sysid_dim', obs_dim, act_dim)
 
 
 def sysid_ridge(ridge, name='ridge'):
@@ -417,39 +438,25 @@ def summary_sysid(states, actions, ridge=1e-3, out=None, check_finite=True, dtyp
     fewer than two states; NotImplementedError when a trajectory does not fit a workgroup's LDS."""
     prec = _precision(dtype)
     ridge = sysid_ridge(ridge)
-    assert len(states.shape) == 3, 'Need states: ntraj x n_steps x state_dim'
-    assert len(actions.shape) == 3, 'Need actions: ntraj x n_steps x state_dim'
+    _need_trajectories(states, actions)
     if states.shape[1] < 2:
         raise ValueError('summary_sysid needs 2 states or more, got %d' % (states.shape[1],))
     if actions.shape[1] < 1:
         raise ValueError('summary_sysid needs 1 action or more, got %d' % (actions.shape[1],))
     width = sysid_dim(states.shape[2], actions.shape[2])
-    s, a, home = _prep(states, actions, prec)
-    n, t, sd = s.shape
-    ad = a.shape[2]
-    buf, ld = _alloc(n, width, s.device, out, prec)
-    flag, read_back = _finite_flag(check_finite, s.device)
-    with _lib.on_device(s.device):
-        prec.sysid(_lib.ptr(s), _lib.ptr(a), _lib.ptr(buf), n, t, a.shape[1], sd, ad, ridge, ld,
-                   _lib.ptr(flag), _lib.stream(s.device))
-    _assert_finite(flag, read_back)
-    return _finish(buf, n, width, home, out)
+
+    def launch(s, a, buf, ld, flag, stream):
+        n, t, sd = s.shape
+        prec.sysid(_lib.ptr(s), _lib.ptr(a), _lib.ptr(buf), n, t, a.shape[1], sd, a.shape[2], ridge, ld,
+                   _lib.ptr(flag), stream)
+    return _launch_summary(states, actions, prec, width, out, check_finite, launch)
 
 
 def kme_row_dim(obs_dim, act_dim, diff=True, time=False):
     """Width d of a transition row ``[tau? | s | a | ds?]`` of ``summary_kme``: ``2 * obs_dim + act_dim`` with
     the differences, ``obs_dim + act_dim`` without, one more with the time column -- without touching the GPU
     (bsig_kme_row_dim, include/bsig_kme.h).  ValueError for a dimension below 1 or a width past 2^31 - 1."""
-    try:
-        sd, ad = operator.index(obs_dim), operator.index(act_dim)
-    except TypeError:
-        raise ValueError('obs_dim and act_dim must be ints >= 1, got %r, %r' % (obs_dim, act_dim)) from None
-    ok = 1 <= sd < 2 ** 31 and 1 <= ad < 2 ** 31
-    d = int(_lib.load().bsig_kme_row_dim(sd, ad, 1 if diff else 0, 1 if time else 0)) if ok else -1
-    if d < 0:
-        raise ValueError('no transition row for obs_dim=%r, act_dim=%r (dimensions >= 1, width below 2^31)'
-                         % (obs_dim, act_dim))
-    return d
+    return _obs_act_width('transition', 'bsig_kme_row_dim', obs_dim, act_dim, 1 if diff else 0, 1 if time else 0)
 
 
 def summary_kme(states, actions, embedding, out=None, check_finite=True, dtype=None, lengths=None):
@@ -520,22 +527,17 @@ def _channel_vector(picked, device):
 
 def _signature_args(states, actions, depth, dtype, channels):
     """What summary_signatory and summary_logsignature do with their arguments: the host checks (asserts, then
-    ValueErrors, all before any GPU call), the trajectories on the device, the path and its default depth.
-    Returns (prec, s, a, home, n, length, sd, ad, picked, path_dim, depth)."""
+    ValueErrors, all before any GPU call), the path and its default depth: (prec, picked, path_dim, depth)."""
     prec = _precision(dtype)
     assert len(states.shape) == 3, 'states should be batch x time x state_dim'
     assert len(actions.shape) == 3, 'Need actions: ntraj x n_steps x state_dim'
     picked = None if channels is None else signature_channels(channels, states.shape[2], actions.shape[2])
     if depth is not None and depth > _lib.SIGNATURE_MAX_DEPTH:
         raise ValueError('depth %r is above %d' % (depth, _lib.SIGNATURE_MAX_DEPTH))
-    s, a, home = _prep(states, actions, prec)
-    n, length, sd = s.shape
-    ad = a.shape[2]
-    assert a.shape[1] == length
-    path_dim = 1 + (sd + ad if picked is None else len(picked))
+    path_dim = 1 + (states.shape[2] + actions.shape[2] if picked is None else len(picked))
     if depth is None:
         depth = signature_depth(path_dim)
-    return prec, s, a, home, n, length, sd, ad, picked, path_dim, depth
+    return prec, picked, path_dim, depth
 
 
 def summary_signatory(states, actions, depth=None, out=None, dtype=None, channels=None):
@@ -551,22 +553,23 @@ def summary_signatory(states, actions, depth=None, out=None, dtype=None, channel
     call it always was (signature3_kernel / signature12_kernel); anything else, the identity list
     included, runs the general kernel of csrc/signature_ex.h.  ValueError (before any GPU call) for a
     bad channel list or a depth above 6; NotImplementedError when the levels do not fit a workgroup's LDS."""
-    prec, s, a, home, n, length, sd, ad, picked, path_dim, depth = _signature_args(
-        states, actions, depth, dtype, channels)
-    if picked is None and depth <= 3:
-        width = summary_dim('summary_signatory', length, sd, ad, depth)
-        buf, ld = _alloc(n, width, s.device, out, prec)
-        prec.signature(
-            _lib.ptr(s), _lib.ptr(a), _lib.ptr(buf), n, length, sd, ad, depth, ld,
-            _lib.stream())
-        return _finish(buf, n, width, home, out)
-    width = signature_dim(path_dim, depth)
-    buf, ld = _alloc(n, width, s.device, out, prec)
-    vec = None if picked is None else _channel_vector(picked, s.device)
-    prec.signature_ex(
-        _lib.ptr(s), _lib.ptr(a), _lib.ptr(vec), len(picked or ()), _lib.ptr(buf), n, length, sd, ad,
-        depth, ld, _lib.stream())
-    return _finish(buf, n, width, home, out)
+    prec, picked, path_dim, depth = _signature_args(states, actions, depth, dtype, channels)
+    general = not (picked is None and depth <= 3)      # the kernel of csrc/signature_ex.h
+
+    def width(s, a):
+        assert a.shape[1] == s.shape[1]
+        if general:
+            return signature_dim(path_dim, depth)
+        return summary_dim('summary_signatory', s.shape[1], s.shape[2], a.shape[2], depth)
+
+    def launch(s, a, buf, ld, flag, stream):
+        tail = (_lib.ptr(buf), s.shape[0], s.shape[1], s.shape[2], a.shape[2], depth, ld, stream)
+        if general:
+            vec = None if picked is None else _channel_vector(picked, s.device)
+            prec.signature_ex(_lib.ptr(s), _lib.ptr(a), _lib.ptr(vec), len(picked or ()), *tail)
+        else:
+            prec.signature(_lib.ptr(s), _lib.ptr(a), *tail)
+    return _launch_summary(states, actions, prec, width, out, False, launch)
 
 
 def logsignature_dim(path_dim, depth):
@@ -633,13 +636,17 @@ def summary_logsignature(states, actions, depth=None, out=None, dtype=None, chan
     are those of ``summary_signatory``.  Depth 1 is the signature's level 1; every other call, whatever
     ``channels``, runs the log-signature kernel.  In fp32 the log cancels: see the README for the error
     relative to the value at depth 6; ``dtype=torch.float64`` is the remedy."""
-    prec, s, a, home, n, length, sd, ad, picked, path_dim, depth = _signature_args(
-        states, actions, depth, dtype, channels)
-    width = logsignature_dim(path_dim, depth)
-    buf, ld = _alloc(n, width, s.device, out, prec)
-    vec = None if picked is None else _channel_vector(picked, s.device)
-    words = None if depth == 1 else _word_vector(path_dim, depth, s.device)
-    prec.logsignature(
-        _lib.ptr(s), _lib.ptr(a), _lib.ptr(vec), len(picked or ()), _lib.ptr(words), _lib.ptr(buf), n, length,
-        sd, ad, depth, ld, _lib.stream())
-    return _finish(buf, n, width, home, out)
+    prec, picked, path_dim, depth = _signature_args(states, actions, depth, dtype, channels)
+
+    def width(s, a):
+        assert a.shape[1] == s.shape[1]
+        return logsignature_dim(path_dim, depth)
+
+    def launch(s, a, buf, ld, flag, stream):
+        n, length, sd = s.shape
+        vec = None if picked is None else _channel_vector(picked, s.device)
+        words = None if depth == 1 else _word_vector(path_dim, depth, s.device)
+        prec.logsignature(
+            _lib.ptr(s), _lib.ptr(a), _lib.ptr(vec), len(picked or ()), _lib.ptr(words), _lib.ptr(buf), n, length,
+            sd, a.shape[2], depth, ld, stream)
+    return _launch_summary(states, actions, prec, width, out, False, launch)
