@@ -196,8 +196,23 @@ __global__ __launch_bounds__(256) void gemm_f64acc_kernel(GemmParams p) {
 
 enum { TILE_64 = 0, TILE_128 = 1, TILE_128x32 = 2, TILE_128x64 = 3, TILE_128x96 = 4,
        TILE_96x128 = 5, TILE_128x288 = 6, TILE_288x128 = 7, N_TILES = 8 };
-static const int kTileM[N_TILES] = {64, 128, 128, 128, 128, 96, 128, 288};
-static const int kTileN[N_TILES] = {64, 128, 32, 64, 96, 128, 288, 128};
+// One entry per tile shape, indexed by the enum (= BSIG_GEMM_TILE): its launcher of gemm_mfma_kernel (null: not
+// in this build) and of gemm_lean_kernel (null: the lean loop is not instantiated for the shape).
+struct GemmTile {
+  int m, n;
+  int (*mfma)(const GemmParams&, bool akm, bool bkm, int avec, int bvec, hipStream_t);
+  int (*lean)(const GemmParams&, bool akm, bool bkm, hipStream_t);
+};
+static const GemmTile kTiles[N_TILES] = {
+    {64, 64, launch_tile_64, launch_lean_64},         {128, 128, launch_tile_128, launch_lean_128},
+    {128, 32, launch_tile_128x32, launch_lean_128x32}, {128, 64, launch_tile_128x64, launch_lean_128x64},
+    {128, 96, launch_tile_128x96, launch_lean_128x96}, {96, 128, launch_tile_96x128, launch_lean_96x128},
+#ifdef BSIG_WITH_WIDE_TILES
+    {128, 288, launch_tile_128x288, nullptr},          {288, 128, launch_tile_288x128, nullptr},
+#else
+    {128, 288, nullptr, nullptr},                      {288, 128, nullptr, nullptr},
+#endif
+};
 struct GemmPlan { int tile; int splits; int k_chunk; };
 
 static int env_int(const char* name, int dflt) {
@@ -236,8 +251,8 @@ static bool plan_gemm_large(int64_t m, int64_t n, int64_t k, size_t ws_bytes, Ge
   for (int i = 0; i < 7; ++i) {
     const int t = cand[i];
     if (!wide_ok && (t == TILE_128x288 || t == TILE_288x128)) continue;
-    const int64_t tm = ceil_div<int64_t>(m, kTileM[t]), tn = ceil_div<int64_t>(n, kTileN[t]);
-    const double padded = (double)(tm * kTileM[t]) * (double)(tn * kTileN[t]) * cost[i];
+    const int64_t tm = ceil_div<int64_t>(m, kTiles[t].m), tn = ceil_div<int64_t>(n, kTiles[t].n);
+    const double padded = (double)(tm * kTiles[t].m) * (double)(tn * kTiles[t].n) * cost[i];
     if (best_t < 0 || padded < best) { best = padded; best_t = t; best_tiles = tm * tn; }
   }
   int64_t splits = 1;
@@ -288,9 +303,9 @@ static GemmPlan plan_gemm(int64_t m, int64_t n, int64_t k, size_t ws_bytes, bool
   }
   const int forced_tile = env_int("BSIG_GEMM_TILE", -1);
   if (forced_tile >= 0) {
-    pl.tile = forced_tile;
-    const int bm = kTileM[forced_tile % N_TILES], bn = kTileN[forced_tile % N_TILES];
-    tiles = ceil_div<int64_t>(m, bm) * ceil_div<int64_t>(n, bn);
+    pl.tile = forced_tile;   // (as given: route_generic refuses one that names no built tile)
+    const GemmTile& t = kTiles[forced_tile % N_TILES];
+    tiles = ceil_div<int64_t>(m, t.m) * ceil_div<int64_t>(n, t.n);
   }
   int64_t splits = 1;
   if (tiles < target && tiles < 256) {   // fewer workgroups than CUs: split K
@@ -305,26 +320,84 @@ static GemmPlan plan_gemm(int64_t m, int64_t n, int64_t k, size_t ws_bytes, bool
   const int64_t max_by_ws = (int64_t)(ws_bytes / (sizeof(float) * (size_t)(m * n)));
   if (splits > max_by_ws) splits = max_by_ws;
   if (splits < 1) splits = 1;
-  int64_t chunk = round_up<int64_t>(ceil_div<int64_t>(k, splits), BK);
-  splits = ceil_div<int64_t>(k, chunk);
+  // (k = 0, which only bsig_gemm_workspace_bytes brings here: one empty slice, not a division by zero)
+  int64_t chunk = std::max<int64_t>(round_up<int64_t>(ceil_div<int64_t>(k, splits), BK), BK);
+  splits = std::max<int64_t>(ceil_div<int64_t>(k, chunk), 1);
   pl.splits = (int)splits;
   pl.k_chunk = (int)chunk;
   return pl;
 }
 
-static int pick_vec(const float* ptr, int64_t ld) {
-  return (ld % 4 == 0 && aligned(ptr, 16)) ? 4 : 1;
-}
-// k-contiguous operand with unaligned rows (ld % 4 != 0: the cross-correlation widths S*A + 2):
-// quads at any 4-byte address, the row's last one shifted into place
-static bool unaligned_quads(const float* ptr, int64_t ld, int kmajor, int k) {
-  return !kmajor && pick_vec(ptr, ld) == 1 && ld >= 4 && k >= 4 && getenv("BSIG_GEMM_NO_UNALIGNED") == nullptr;
+// ---- routing: facts -> route -> launch.  What a route depends on, without pointers: gemm_run fills it from
+// its operands (gemm_facts), the report bsig_debug_gemm_path from its arguments (gemm_facts_dense).  Wherever
+// the two answer differently for one shape, it is those two builders that differ.
+struct GemmFacts {
+  int64_t m = 0, n = 0, k = 0;
+  bool a_kmajor = false, b_kmajor = false;
+  int epilogue = BSIG_EPI_NONE, math = 0;
+  size_t ws_bytes = 0;        // 0: no workspace
+  struct Operand {
+    bool vec4 = false;        // moves as aligned 16-byte items (pitch % 4 == 0, storage 16-byte aligned)
+    // k-contiguous rows that are not (the cross-correlation widths S*A + 2) and can still move in quads, at any
+    // 4-byte address, the row's last one shifted into place
+    bool unal = false;
+    bool gathered = false, offset = false;   // through an index vector; at a device-resolved row offset
+  } a, b;
+  bool lda_ceil16 = false;    // lda == ceil16(m): the pitch the whole-width gradient takes dO at
+  bool partial_bias = false, expsum = false;   // bias_g_n > 1; the exp side output is asked for
+  // the whole-width forward may combine its K slices in the launch: a ticket for every 64-row tile (those beyond
+  // the caller's buffer are somebody else's memory -- a head whose width is a multiple of 16 keeps ldc == wide at
+  // ANY row count) and c 16-byte aligned at a pitch that holds the padded width
+  bool combine_ok = false;
+};
+
+struct GemmRoute {
+  int path = GEMM_PATH_MFMA;
+  int tile = -1, tile_m = 0, tile_n = 0;   // tile: index of kTiles (the generic kernels only)
+  int splits = 1, k_chunk = 0;
+  int64_t workgroups = 0;
+  int64_t slab = 0;                        // the whole-width kernels: floats per K slice of slabs
+  bool reduce = false;                     // raw slabs: launch_reduce sums them and applies the epilogue ...
+  bool combine = false;                    // ... or the whole-width forward does, inside its launch
+  bool a_unal = false, b_unal = false;     // gemm_mfma_kernel fetches the operand in unaligned quads
+  int declined = 0;                        // split-bf16 asked for: 1 the kernel does not cover the call, 2 left to fp32 by rule
+};
+
+static GemmFacts::Operand operand_facts(const float* ptr, int64_t ld, bool kmajor, int64_t k, bool gathered, bool offset) {
+  GemmFacts::Operand o;
+  o.vec4 = ld % 4 == 0 && aligned(ptr, 16);
+  o.unal = !kmajor && !o.vec4 && ld >= 4 && k >= 4;
+  o.gathered = gathered; o.offset = offset;   // (offsets are whole rows: they change the alignment of nothing)
+  return o;
 }
 
-bool gemm_wide_gradient_applies(int64_t m, int64_t n, int64_t k, int64_t lda, int64_t ldb, const float* a,
-                                const float* b, bool gathered) {
-  return env_int("BSIG_GEMM_WIDE", 1) && gathered && k >= 2048 && k % BK == 0 && gemm_wide_covers((int)m) &&
-         lda == ceil_div<int64_t>(m, 16) * 16 && n % 64 == 0 && pick_vec(a, lda) == 4 && pick_vec(b, ldb) == 4;
+static GemmFacts gemm_facts(const GemmParams& p, const void* workspace, size_t workspace_bytes) {
+  GemmFacts f;
+  f.m = p.m; f.n = p.n; f.k = p.k; f.a_kmajor = p.a_kmajor != 0; f.b_kmajor = p.b_kmajor != 0;
+  f.epilogue = p.epilogue; f.math = p.math;
+  f.ws_bytes = workspace ? workspace_bytes : 0;
+  f.a = operand_facts(p.a, p.lda, f.a_kmajor, p.k, p.a_rows != nullptr, p.a_dyn_stride || p.a_dyn_base);
+  f.b = operand_facts(p.b, p.ldb, f.b_kmajor, p.k, p.b_rows != nullptr, p.b_dyn_stride || p.b_dyn_base);
+  f.lda_ceil16 = p.lda == round_up<int64_t>(p.m, 16);
+  f.partial_bias = p.bias_g_n > 1; f.expsum = p.expsum != nullptr;
+  f.combine_ok = p.combine_tickets && ceil_div(p.m, 64) <= p.combine_capacity && p.ldc >= round_up(p.n, 16) &&
+                 (p.ldc & 3) == 0 && aligned(p.c, 16);
+  return f;
+}
+
+// The report's operands: dense and 16-byte aligned, A [m, k] or k-major [k, ceil16(m)], B [n, k] or k-major [k, n];
+// no unaligned quads, offsets, side output, partial bias sums or tickets.  Its one `gathered` bit speaks for X[ids]
+// of the whole-width gradient only (B where both operands are k-major): the forward, which needs B direct, never sees it.
+static GemmFacts gemm_facts_dense(int64_t m, int64_t n, int64_t k, bool akm, bool bkm, bool gathered, int epilogue,
+                                  size_t ws_bytes, int math) {
+  GemmFacts f;
+  f.m = m; f.n = n; f.k = k; f.a_kmajor = akm; f.b_kmajor = bkm;
+  f.epilogue = epilogue; f.math = math; f.ws_bytes = ws_bytes;
+  f.a.vec4 = (akm ? round_up<int64_t>(m, 16) : k) % 4 == 0;
+  f.b.vec4 = (bkm ? n : k) % 4 == 0;
+  f.b.gathered = gathered && akm && bkm;
+  f.lda_ceil16 = true;
+  return f;
 }
 
 // The one class of shapes the split-bf16 mode leaves on the fp32 kernels (profiles/split_bf16_NOTES.md): the
@@ -333,11 +406,176 @@ bool gemm_wide_gradient_applies(int64_t m, int64_t n, int64_t k, int64_t lda, in
 // vector-ALU time on splitting the operands than the whole-width fp32 kernels spend on their MFMAs
 // (forward 255 us against 168, gradient 344 against 162).  bsig_debug_gemm_path reports the rule (out[6] = 2).
 // (BSIG_SPLIT_BF16_EVERYWHERE=1 switches the rule off: tools/split_bf16_timing.py measures what it rests on)
-static bool split_bf16_leaves_to_fp32(int64_t m, int64_t n, int64_t k, bool akm, bool bkm) {
+static bool split_bf16_leaves_to_fp32(const GemmFacts& f) {
   if (env_int("BSIG_SPLIT_BF16_EVERYWHERE", 0)) return false;
-  if (!akm && !bkm) return m >= 4096 && k >= 1024 && gemm_wide_covers((int)n);
-  if (akm && bkm) return k >= 4096 && n >= 1024 && gemm_wide_covers((int)m);
+  if (!f.a_kmajor && !f.b_kmajor) return f.m >= 4096 && f.k >= 1024 && gemm_wide_covers((int)f.n);
+  if (f.a_kmajor && f.b_kmajor) return f.k >= 4096 && f.n >= 1024 && gemm_wide_covers((int)f.m);
   return false;
+}
+
+// dW = dO^T X[ids] on the whole-width gradient kernel (the workspace aside: a caller asks before it issues the product)
+static bool wide_gradient_rule(const GemmFacts& f) {
+  return f.a_kmajor && f.b_kmajor && !f.a.gathered && !f.a.offset && f.b.gathered && f.k >= 2048 && f.k % BK == 0 &&
+         gemm_wide_covers((int)f.m) && f.lda_ceil16 && f.n % 64 == 0 && f.a.vec4 && f.b.vec4 && env_int("BSIG_GEMM_WIDE", 1);
+}
+
+bool gemm_wide_gradient_applies(int64_t m, int64_t n, int64_t k, int64_t lda, int64_t ldb, const float* a,
+                                const float* b, bool gathered) {
+  GemmFacts f;
+  f.m = m; f.n = n; f.k = k; f.a_kmajor = f.b_kmajor = true;
+  f.a = operand_facts(a, lda, true, k, false, false);
+  f.b = operand_facts(b, ldb, true, k, gathered, false);
+  f.lda_ceil16 = lda == round_up<int64_t>(m, 16);
+  return wide_gradient_rule(f);
+}
+
+// K slices of a whole-width product of `tiles` narrow tiles into slabs of r->slab floats.  One workgroup per CU at a
+// time (123 KB of LDS): the launch takes ceil(tiles * s / 256) rounds of 1 / s of a tile's K loop each, plus a
+// slab's worth of traffic per slice -- e.g. 313 row tiles (a 20000-row evaluation): unsplit 2 rounds of the whole
+// K loop, in 4 slices 5 rounds of a quarter.  False: the workspace does not hold one slab.
+static bool wide_slices(const GemmFacts& f, int64_t tiles, GemmRoute* r) {
+  const int64_t smax = std::min<int64_t>(std::min<int64_t>(8, std::max<int64_t>(f.k / (8 * BK), 1)),
+                                         (int64_t)(f.ws_bytes / (sizeof(float) * (size_t)r->slab)));
+  if (smax < 1) return false;
+  int64_t s = 1;
+  double best = 1e30;
+  for (int64_t c = 1; c <= smax; ++c) {
+    const double cost = (double)ceil_div<int64_t>(tiles * c, 256) / (double)c + 0.02 * (double)c;
+    if (cost < best - 1e-9) { best = cost; s = c; }
+  }
+  r->k_chunk = (int)round_up<int64_t>(ceil_div<int64_t>(f.k, s), BK);
+  r->splits = (int)ceil_div<int64_t>(f.k, r->k_chunk);
+  r->workgroups = tiles * r->splits;
+  return true;
+}
+
+// The generic kernels: the lean main loop (gemm_lean.h: bit-identical, no vector-ALU work in the K loop) wherever
+// both operands move as aligned 16-byte items and the tile has one, gemm_mfma_kernel elsewhere.
+static int route_generic(const GemmFacts& f, GemmRoute* r) {
+  const int declined = r->declined;
+  *r = GemmRoute();   // (whatever a whole-width route that did not come about left in it)
+  r->declined = declined;
+  BSIG_REQUIRE(f.k >= 1, "gemm: an empty contraction (k = 0) on the fp32 MFMA kernels");
+  const bool lean_ok = f.a.vec4 && f.b.vec4;
+  // (the plan does not depend on BSIG_GEMM_LEAN: the two kernels are compared on the SAME plan)
+  const GemmPlan pl = plan_gemm(f.m, f.n, f.k, f.ws_bytes, lean_ok);
+  int built = 0;
+  while (built < N_TILES && kTiles[built].mfma) ++built;
+  BSIG_REQUIRE(pl.tile >= 0 && pl.tile < built, "gemm: BSIG_GEMM_TILE=%d names no tile of this build (0..%d)",
+               pl.tile, built - 1);
+  const GemmTile& t = kTiles[pl.tile];
+  const bool unal = (f.a.unal || f.b.unal) && getenv("BSIG_GEMM_NO_UNALIGNED") == nullptr;
+  r->a_unal = unal && f.a.unal; r->b_unal = unal && f.b.unal;
+  const int lean = env_int("BSIG_GEMM_LEAN", 1);   // (read per call: tests compare the two kernels)
+  r->path = lean && lean_ok && t.lean ? GEMM_PATH_LEAN : GEMM_PATH_MFMA;
+  r->tile = pl.tile; r->tile_m = t.m; r->tile_n = t.n;
+  r->splits = pl.splits; r->k_chunk = pl.k_chunk; r->reduce = pl.splits > 1;
+  r->workgroups = ceil_div<int64_t>(f.m, t.m) * ceil_div<int64_t>(f.n, t.n) * pl.splits;
+  return BSIG_OK;
+}
+
+// Which kernel runs a product: host arithmetic on the facts and the environment switches (read per call: tests
+// flip them between calls).  gemm_run launches what it says, bsig_debug_gemm_path reports it.
+static int gemm_route(const GemmFacts& f, GemmRoute* r) {
+  *r = GemmRoute();
+  // debug (BSIG_DEBUG_F64_ACC_MIN_K=<k>): a contraction at least <k> long is summed in fp64, gemm_f64acc_kernel
+  const int f64_min_k = env_int("BSIG_DEBUG_F64_ACC_MIN_K", 0);
+  if (f64_min_k > 0 && f.k >= f64_min_k) {
+    r->path = GEMM_PATH_F64ACC; r->k_chunk = (int)f.k;
+    r->workgroups = std::min<int64_t>(ceil_div<int64_t>(f.m * f.n, 256), 2048);
+    return BSIG_OK;
+  }
+  // The opt-in matmul precision (include/bsig_matmul.h): the split-bf16 kernel wherever it covers the
+  // call -- every operand form; a fused Adam step needs room for its slabs.  No size threshold; one
+  // measured class of shapes stays on the fp32 kernels (split_bf16_leaves_to_fp32).
+  if (f.math == BSIG_MATMUL_SPLIT_BF16) {
+    SplitBf16Plan sp;
+    // (an unsplit launch writes one exp partial per workgroup; the reduce at most 2048: a product of more
+    // tiles than that with the side output and no K slices -- a head on a narrow trunk over tens of
+    // thousands of rows -- keeps the fp32 kernels, whose planner the callers' partial arrays are sized for)
+    if (split_bf16_leaves_to_fp32(f)) {
+      r->declined = 2;
+    } else if (split_bf16_plan(f.m, f.n, f.k, f.epilogue, f.partial_bias, f.ws_bytes, &sp) &&
+               !(f.expsum && !sp.slabs && sp.workgroups > 2048)) {
+      r->path = GEMM_PATH_SPLIT_BF16; r->tile_m = r->tile_n = sp.tile;
+      r->splits = sp.splits; r->k_chunk = sp.k_chunk; r->workgroups = sp.workgroups; r->reduce = sp.slabs != 0;
+      return BSIG_OK;
+    } else {
+      r->declined = 1;
+    }
+  }
+  // Large-minibatch products of a few-hundred-wide head (the scaled-batch update): whole-width tiles
+  // of 16x16x4 MFMAs (gemm_wide.h) -- forward O = X[ids] W^T and the gradient dW = dO^T X[ids] with
+  // dO at a pitch of ceil16(Nh) floats -- in K slices of slabs, one round of ~256 workgroups.
+  if (env_int("BSIG_GEMM_WIDE", 1) && f.ws_bytes > 0 && f.k >= 1024 && f.k % BK == 0) {
+    r->reduce = true;
+    if (!f.a_kmajor && !f.b_kmajor && !f.b.gathered && !f.b.offset && f.m >= 2048 && gemm_wide_covers((int)f.n) &&
+        f.a.vec4 && f.b.vec4 && (f.epilogue == BSIG_EPI_NONE || f.epilogue == BSIG_EPI_BIAS)) {
+      r->path = GEMM_PATH_WIDE_FORWARD; r->tile_m = 64; r->tile_n = (int)round_up<int64_t>(f.n, 16);
+      r->slab = f.m * r->tile_n;
+      if (wide_slices(f, ceil_div<int64_t>(f.m, 64), r)) {
+        r->combine = f.combine_ok && f.epilogue == BSIG_EPI_BIAS && r->slab < ((int64_t)1 << 31) &&
+                     env_int("BSIG_GEMM_NO_COMBINE", 0) == 0;
+        r->reduce = !r->combine;
+        return BSIG_OK;
+      }
+    } else if (wide_gradient_rule(f)) {
+      r->path = GEMM_PATH_WIDE_GRADIENT; r->tile_m = (int)round_up<int64_t>(f.m, 16); r->tile_n = 64;
+      r->slab = f.m * f.n;
+      if (wide_slices(f, f.n / 64, r)) return BSIG_OK;
+    }
+  }
+  return route_generic(f, r);
+}
+
+// One launch per path id.  BSIG_EUNSUPPORTED: the launcher hands the call back, nothing was launched (gemm_run).
+static int launch_route(GemmParams& p, const GemmFacts& f, const GemmRoute& r, hipStream_t st) {
+  static const int xcd = [] { const char* e = getenv("BSIG_GEMM_XCD"); return e ? atoi(e) : 1; }();
+  p.xcd_swz = xcd;
+  p.splits = r.splits; p.k_chunk = r.k_chunk;
+  p.partial_ld = p.partial_slab = 0;
+  WideParams wp;
+  wp.dyn = p.dyn; wp.dyn_delta = p.dyn_delta; wp.k = p.k; wp.k_chunk = r.k_chunk; wp.splits = r.splits;
+  wp.out = p.partial; wp.slab = r.slab;
+  switch (r.path) {
+    case GEMM_PATH_F64ACC:
+      hipLaunchKernelGGL(gemm_f64acc_kernel, dim3((int)r.workgroups), dim3(256), 0, st, p);
+      BSIG_CHECK_LAUNCH("gemm_f64acc");
+      return BSIG_OK;
+    case GEMM_PATH_SPLIT_BF16: {
+      SplitBf16Plan sp;
+      sp.tile = r.tile_m; sp.splits = r.splits; sp.k_chunk = r.k_chunk; sp.slabs = r.reduce; sp.workgroups = r.workgroups;
+      return launch_split_bf16(p, sp, st);
+    }
+    case GEMM_PATH_WIDE_FORWARD:
+      wp.wide = p.b; wp.ld_wide = p.ldb; wp.n_wide = p.n;
+      wp.x = p.a; wp.ldx = p.lda; wp.ids = p.a_rows; wp.n_narrow = p.m;
+      wp.dyn_stride = p.a_dyn_stride; wp.dyn_base = p.a_dyn_base;
+      wp.ld_out = r.tile_n;
+      if (r.combine) {
+        wp.tickets = p.combine_tickets; wp.bias = p.bias; wp.final_out = p.c; wp.ld_final = p.ldc;
+        wp.expsum = p.expsum; wp.expsum_col0 = p.expsum_col0; wp.expsum_ncols = p.expsum_ncols;
+      } else {   // launch_reduce reads slabs at the padded width
+        p.partial_ld = r.tile_n; p.partial_slab = r.slab;
+      }
+      return gemm_wide_forward(wp, st);
+    case GEMM_PATH_WIDE_GRADIENT:
+      wp.wide = p.a; wp.ld_wide = p.lda; wp.n_wide = p.m;
+      wp.x = p.b; wp.ldx = p.ldb; wp.ids = p.b_rows; wp.n_narrow = p.n;
+      wp.dyn_stride = p.b_dyn_stride; wp.dyn_base = p.b_dyn_base;
+      wp.ld_out = p.n;
+      return gemm_wide_gradient(wp, st);
+    default: {
+      BSIG_REQUIRE(!f.partial_bias, "gemm: partial bias sums outside the whole-width gradient path");
+      p.a_unal = r.a_unal; p.b_unal = r.b_unal;
+      const int rc = r.path == GEMM_PATH_LEAN
+                         ? kTiles[r.tile].lean(p, f.a_kmajor, f.b_kmajor, st)
+                         : kTiles[r.tile].mfma(p, f.a_kmajor, f.b_kmajor, (f.a.vec4 || r.a_unal) ? 4 : 1,
+                                               (f.b.vec4 || r.b_unal) ? 4 : 1, st);
+      if (rc == BSIG_OK) BSIG_CHECK_LAUNCH("gemm_mfma");
+      return rc;
+    }
+  }
 }
 
 int gemm_run(GemmParams p, void* workspace, size_t workspace_bytes, hipStream_t st,
@@ -357,166 +595,27 @@ int gemm_run(GemmParams p, void* workspace, size_t workspace_bytes, hipStream_t 
   if (n_expsum) *n_expsum = 0;
   BSIG_REQUIRE(!(p.expsum && e != BSIG_EPI_BIAS), "gemm: expsum needs the bias epilogue");
   if (p.m == 0 || p.n == 0) return BSIG_OK;
-  {
-    const char* f64_env = getenv("BSIG_DEBUG_F64_ACC_MIN_K");     // (read per call: tests switch it)
-    const int f64_min_k = f64_env ? atoi(f64_env) : 0;
-    if (f64_min_k > 0 && p.k >= f64_min_k) {
-      const int blocks = (int)std::min<int64_t>(ceil_div<int64_t>((int64_t)p.m * p.n, 256), 2048);
-      hipLaunchKernelGGL(gemm_f64acc_kernel, dim3(blocks), dim3(256), 0, st, p);
-      BSIG_CHECK_LAUNCH("gemm_f64acc");
-      if (n_expsum && p.expsum) *n_expsum = blocks;
-      return BSIG_OK;
-    }
-  }
-  // The opt-in matmul precision (include/bsig_matmul.h): the split-bf16 kernel wherever it covers the
-  // call -- every operand form; a fused Adam step needs room for its slabs.  No size threshold; one
-  // measured class of shapes stays on the fp32 kernels (split_bf16_leaves_to_fp32).
-  if (p.math == BSIG_MATMUL_SPLIT_BF16 && !split_bf16_leaves_to_fp32(p.m, p.n, p.k, p.a_kmajor != 0, p.b_kmajor != 0)) {
-    SplitBf16Plan sp;
-    // (an unsplit launch writes one exp partial per workgroup; the reduce at most 2048: a product of more
-    // tiles than that with the side output and no K slices -- a head on a narrow trunk over tens of
-    // thousands of rows -- keeps the fp32 kernels, whose planner the callers' partial arrays are sized for)
-    if (split_bf16_plan(p.m, p.n, p.k, p.epilogue, p.bias_g_n > 1, workspace ? workspace_bytes : 0, &sp) &&
-        !(p.expsum && !sp.slabs && sp.workgroups > 2048)) {
-      static const int xcd = [] { const char* e = getenv("BSIG_GEMM_XCD"); return e ? atoi(e) : 1; }();
-      p.xcd_swz = xcd;
-      p.splits = sp.splits; p.k_chunk = sp.k_chunk;
-      p.partial = reinterpret_cast<float*>(workspace);
-      BSIG_TRY(launch_split_bf16(p, sp, st));
-      if (sp.slabs) return launch_reduce(p, st, n_expsum);
-      if (n_expsum && p.expsum) *n_expsum = ceil_div(p.m, sp.tile) * ceil_div(p.n, sp.tile);
-      return BSIG_OK;
-    }
-  }
-  // Large-minibatch products of a few-hundred-wide head (the scaled-batch update): whole-width tiles
-  // of 16x16x4 MFMAs (gemm_wide.h) -- forward O = X[ids] W^T and the gradient dW = dO^T X[ids] with
-  // dO at a pitch of ceil16(Nh) floats.  Split K so that the launch is one round of ~256 workgroups;
-  // the slabs are reduced (and the epilogue applied) by gemm_reduce_kernel as for every split product.
-  if (env_int("BSIG_GEMM_WIDE", 1) && workspace && p.k >= 1024 && p.k % BK == 0 && !p.a_unal && !p.b_unal) {
-    WideParams wp;
-    wp.dyn = p.dyn; wp.dyn_delta = p.dyn_delta; wp.k = p.k;
-    int rc = BSIG_EUNSUPPORTED;
-    auto split = [&](int64_t tiles, int64_t slab_floats) {
-      // one workgroup per CU at a time (123 KB of LDS): the launch takes ceil(tiles * s / 256) rounds
-      // of 1 / s of a tile's K loop each, plus a slab's worth of traffic per slice -- e.g. 313 row
-      // tiles (a 20000-row evaluation): unsplit 2 rounds of the whole K loop, in 4 slices 5 rounds of
-      // a quarter
-      const int64_t smax = std::min<int64_t>(std::min<int64_t>(8, std::max<int64_t>(p.k / (8 * BK), 1)),
-                                             (int64_t)(workspace_bytes / (sizeof(float) * (size_t)slab_floats)));
-      if (smax < 1) return false;
-      int64_t s = 1;
-      double best = 1e30;
-      for (int64_t c = 1; c <= smax; ++c) {
-        const double cost = (double)ceil_div<int64_t>(tiles * c, 256) / (double)c + 0.02 * (double)c;
-        if (cost < best - 1e-9) { best = cost; s = c; }
-      }
-      const int64_t chunk = round_up<int64_t>(ceil_div<int64_t>(p.k, s), BK);
-      wp.k_chunk = (int)chunk; wp.splits = (int)ceil_div<int64_t>(p.k, chunk);
-      wp.slab = slab_floats;
-      return true;
-    };
-    if (!p.a_kmajor && !p.b_kmajor && !p.b_rows && p.m >= 2048 && gemm_wide_covers(p.n) &&
-        pick_vec(p.a, p.lda) == 4 && pick_vec(p.b, p.ldb) == 4 && !p.b_dyn_stride && !p.b_dyn_base &&
-        (p.epilogue == BSIG_EPI_NONE || p.epilogue == BSIG_EPI_BIAS)) {
-      const int wide = ceil_div(p.n, 16) * 16;
-      if (split(ceil_div<int64_t>(p.m, 64), (int64_t)p.m * wide)) {
-        wp.wide = p.b; wp.ld_wide = p.ldb; wp.n_wide = p.n;
-        wp.x = p.a; wp.ldx = p.lda; wp.ids = p.a_rows; wp.n_narrow = p.m;
-        wp.dyn_stride = p.a_dyn_stride; wp.dyn_base = p.a_dyn_base;
-        wp.out = reinterpret_cast<float*>(workspace); wp.ld_out = wide;
-        // (one ticket per 64-row tile: a product of more row tiles than the caller's ticket words -- a head
-        // whose width is already a multiple of 16 keeps ldc == wide at ANY row count -- must not combine
-        // in the launch: the tickets beyond the buffer are somebody else's memory)
-        const bool combine = p.combine_tickets && ceil_div(p.m, 64) <= p.combine_capacity &&
-                             p.epilogue == BSIG_EPI_BIAS && p.ldc >= wide &&
-                             (p.ldc & 3) == 0 && aligned(p.c, 16) && wp.slab < ((int64_t)1 << 31) &&
-                             env_int("BSIG_GEMM_NO_COMBINE", 0) == 0;
-        if (combine) {
-          wp.tickets = p.combine_tickets; wp.bias = p.bias; wp.final_out = p.c; wp.ld_final = p.ldc;
-          wp.expsum = p.expsum; wp.expsum_col0 = p.expsum_col0; wp.expsum_ncols = p.expsum_ncols;
-        }
-        rc = gemm_wide_forward(wp, st);
-        if (rc == BSIG_OK && combine) {
-          if (n_expsum && p.expsum) *n_expsum = ceil_div(p.m, 64);
-          return BSIG_OK;
-        }
-        if (rc == BSIG_OK) { p.partial_ld = wide; p.partial_slab = wp.slab; }
-      }
-    } else if (p.a_kmajor && p.b_kmajor && !p.a_rows && !p.a_dyn_stride && !p.a_dyn_base &&
-               gemm_wide_gradient_applies(p.m, p.n, p.k, p.lda, p.ldb, p.a, p.b, p.b_rows != nullptr)) {
-      if (split(p.n / 64, (int64_t)p.m * p.n)) {
-        wp.wide = p.a; wp.ld_wide = p.lda; wp.n_wide = p.m;
-        wp.x = p.b; wp.ldx = p.ldb; wp.ids = p.b_rows; wp.n_narrow = p.n;
-        wp.dyn_stride = p.b_dyn_stride; wp.dyn_base = p.b_dyn_base;
-        wp.out = reinterpret_cast<float*>(workspace); wp.ld_out = p.n;
-        rc = gemm_wide_gradient(wp, st);
-      }
-    }
-    if (rc == BSIG_OK) {
-      p.splits = wp.splits; p.k_chunk = wp.k_chunk;
-      p.partial = reinterpret_cast<float*>(workspace);
-      return launch_reduce(p, st, n_expsum);
-    }
-    if (rc != BSIG_EUNSUPPORTED) return rc;
-  }
-  BSIG_REQUIRE(p.bias_g_n <= 1, "gemm: partial bias sums outside the whole-width gradient path");
-  // a device-resolved row offset changes the alignment of nothing: offsets are whole rows
-  {
-    static const int xcd = [] { const char* e = getenv("BSIG_GEMM_XCD"); return e ? atoi(e) : 1; }();
-    p.xcd_swz = xcd;
-  }
-  p.a_unal = unaligned_quads(p.a, p.lda, p.a_kmajor, p.k);
-  p.b_unal = unaligned_quads(p.b, p.ldb, p.b_kmajor, p.k);
-  const int avec = p.a_unal ? 4 : pick_vec(p.a, p.lda), bvec = p.b_unal ? 4 : pick_vec(p.b, p.ldb);
-  // the lean main loop (gemm_lean.h: bit-identical, no vector-ALU work in the K loop) wherever
-  // both operands move as aligned 16-byte items
-  const int lean = env_int("BSIG_GEMM_LEAN", 1);   // (read per call: tests compare the two kernels)
-  const bool lean_ok = avec == 4 && bvec == 4 && !p.a_unal && !p.b_unal;
-  // (the plan does not depend on BSIG_GEMM_LEAN: the two kernels are compared on the SAME plan)
-  const GemmPlan pl = plan_gemm(p.m, p.n, p.k, workspace ? workspace_bytes : 0, lean_ok);
-  p.splits = pl.splits; p.k_chunk = pl.k_chunk;
+  const GemmFacts f = gemm_facts(p, workspace, workspace_bytes);
+  GemmRoute r;
+  BSIG_TRY(gemm_route(f, &r));
   p.partial = reinterpret_cast<float*>(workspace);
-  int rc = BSIG_EUNSUPPORTED;
-  if (lean && lean_ok) {
-    const bool akm = p.a_kmajor != 0, bkm = p.b_kmajor != 0;
-    switch (pl.tile) {
-      case TILE_64: rc = launch_lean_64(p, akm, bkm, st); break;
-      case TILE_128: rc = launch_lean_128(p, akm, bkm, st); break;
-      case TILE_128x32: rc = launch_lean_128x32(p, akm, bkm, st); break;
-      case TILE_128x64: rc = launch_lean_128x64(p, akm, bkm, st); break;
-      case TILE_128x96: rc = launch_lean_128x96(p, akm, bkm, st); break;
-      case TILE_96x128: rc = launch_lean_96x128(p, akm, bkm, st); break;
-      default: break;
-    }
+  int rc = launch_route(p, f, r, st);
+  // The one fallback.  A launcher may hand its call back: the whole-width launchers on guards of their own that
+  // the facts do not carry (a workspace that is not 16-byte aligned), launch_lean for a gathered k-major operand
+  // on a tile where LeanLoader::kSame is false (96 rows).  The call then runs one step down: a whole-width product
+  // on the generic kernels' own plan, a lean one as gemm_mfma_kernel on the same plan, bit-identical by construction.
+  if (rc == BSIG_EUNSUPPORTED && (r.path == GEMM_PATH_WIDE_FORWARD || r.path == GEMM_PATH_WIDE_GRADIENT)) {
+    BSIG_TRY(route_generic(f, &r));
+    rc = launch_route(p, f, r, st);
   }
-  if (rc != BSIG_EUNSUPPORTED) {
-  } else
-  if (pl.tile == TILE_128)
-    rc = launch_tile_128(p, p.a_kmajor != 0, p.b_kmajor != 0, avec, bvec, st);
-  else if (pl.tile == TILE_128x32)
-    rc = launch_tile_128x32(p, p.a_kmajor != 0, p.b_kmajor != 0, avec, bvec, st);
-  else if (pl.tile == TILE_128x64)
-    rc = launch_tile_128x64(p, p.a_kmajor != 0, p.b_kmajor != 0, avec, bvec, st);
-  else if (pl.tile == TILE_128x96)
-    rc = launch_tile_128x96(p, p.a_kmajor != 0, p.b_kmajor != 0, avec, bvec, st);
-  else if (pl.tile == TILE_96x128)
-    rc = launch_tile_96x128(p, p.a_kmajor != 0, p.b_kmajor != 0, avec, bvec, st);
-#ifdef BSIG_WITH_WIDE_TILES
-  else if (pl.tile == TILE_128x288)
-    rc = launch_tile_128x288(p, p.a_kmajor != 0, p.b_kmajor != 0, avec, bvec, st);
-  else if (pl.tile == TILE_288x128)
-    rc = launch_tile_288x128(p, p.a_kmajor != 0, p.b_kmajor != 0, avec, bvec, st);
-#endif
-  else
-    rc = launch_tile_64(p, p.a_kmajor != 0, p.b_kmajor != 0, avec, bvec, st);
+  if (rc == BSIG_EUNSUPPORTED && r.path == GEMM_PATH_LEAN) {
+    r.path = GEMM_PATH_MFMA;
+    rc = launch_route(p, f, r, st);
+  }
   if (rc != BSIG_OK) return rc;
-  BSIG_CHECK_LAUNCH("gemm_mfma");
-  if (p.splits > 1) {
-    BSIG_TRY(launch_reduce(p, st, n_expsum));
-  } else if (n_expsum && p.expsum) {
-    const int bm = kTileM[pl.tile], bn = kTileN[pl.tile];
-    *n_expsum = ceil_div(p.m, bm) * ceil_div(p.n, bn);
-  }
+  if (r.reduce) return launch_reduce(p, st, n_expsum);
+  // (one exp partial per workgroup of an unsplit launch, per 64-row tile of a combining one)
+  if (n_expsum && p.expsum) *n_expsum = (int)(r.workgroups / r.splits);
   return BSIG_OK;
 }
 
@@ -630,8 +729,7 @@ extern "C" int bsig_rff_project_ex(const float* x, int64_t ldx, const int32_t* x
                   nullptr, 0, a, workspace, workspace_bytes, as_stream(stream), matmul);
 }
 
-// gemm_run's routing as host arithmetic (no pointers: operands taken as dense and 16-byte aligned,
-// A [m, k] or k-major [k, ceil16(m)], B [n, k] or k-major [k, n]; the environment switches as gemm_run reads them)
+// gemm_run's route for a product of dense, 16-byte aligned operands (gemm_facts_dense), as host arithmetic
 extern "C" int bsig_debug_gemm_path(int64_t m, int64_t n, int64_t k, int a_kmajor, int b_kmajor,
                                     int gathered, int epilogue, size_t workspace_bytes, int matmul,
                                     int32_t* out) {
@@ -642,55 +740,11 @@ extern "C" int bsig_debug_gemm_path(int64_t m, int64_t n, int64_t k, int a_kmajo
                "gemm path: bad epilogue %d", epilogue);
   BSIG_REQUIRE(matmul == BSIG_MATMUL_FP32 || matmul == BSIG_MATMUL_SPLIT_BF16,
                "gemm path: unknown matmul precision %d", matmul);
-  auto put = [&](int kernel, int tm, int tn, int splits, int k_chunk, int64_t wgs) {
-    out[0] = kernel; out[1] = tm; out[2] = tn; out[3] = splits; out[4] = k_chunk;
-    out[5] = (int32_t)std::min<int64_t>(wgs, INT32_MAX);
-    return BSIG_OK;
-  };
-  const int f64_min_k = env_int("BSIG_DEBUG_F64_ACC_MIN_K", 0);
-  if (f64_min_k > 0 && k >= f64_min_k)
-    return put(GEMM_PATH_F64ACC, 0, 0, 1, (int)k, std::min<int64_t>(ceil_div<int64_t>(m * n, 256), 2048));
-  if (matmul == BSIG_MATMUL_SPLIT_BF16 && split_bf16_leaves_to_fp32(m, n, k, a_kmajor != 0, b_kmajor != 0)) {
-    out[6] = 2;   // the large-minibatch head products stay on the fp32 kernels (measured slower)
-  } else if (matmul == BSIG_MATMUL_SPLIT_BF16) {
-    SplitBf16Plan sp;
-    if (split_bf16_plan(m, n, k, epilogue, false, workspace_bytes, &sp))
-      return put(GEMM_PATH_SPLIT_BF16, sp.tile, sp.tile, sp.splits, sp.k_chunk, sp.workgroups);
-    out[6] = 1;   // the mode was asked for and the kernel does not cover the call
-  }
-  if (env_int("BSIG_GEMM_WIDE", 1) && workspace_bytes > 0 && k >= 1024 && k % BK == 0) {
-    auto slices = [&](int64_t tiles, int64_t slab_floats) {   // (gemm_run's `split`)
-      const int64_t smax = std::min<int64_t>(std::min<int64_t>(8, std::max<int64_t>(k / (8 * BK), 1)),
-                                             (int64_t)(workspace_bytes / (sizeof(float) * (size_t)slab_floats)));
-      int64_t s = 0;
-      double best = 1e30;
-      for (int64_t c = 1; c <= smax; ++c) {
-        const double cost = (double)ceil_div<int64_t>(tiles * c, 256) / (double)c + 0.02 * (double)c;
-        if (cost < best - 1e-9) { best = cost; s = c; }
-      }
-      return s;
-    };
-    if (!a_kmajor && !b_kmajor && m >= 2048 && gemm_wide_covers((int)n) && k % 4 == 0 &&
-        (epilogue == BSIG_EPI_NONE || epilogue == BSIG_EPI_BIAS)) {
-      const int64_t s = slices(ceil_div<int64_t>(m, 64), m * round_up<int64_t>(n, 16));
-      if (s >= 1) {
-        const int64_t chunk = round_up<int64_t>(ceil_div<int64_t>(k, s), BK);
-        return put(GEMM_PATH_WIDE_FORWARD, 64, (int)round_up<int64_t>(n, 16), (int)ceil_div<int64_t>(k, chunk),
-                   (int)chunk, ceil_div<int64_t>(m, 64) * ceil_div<int64_t>(k, chunk));
-      }
-    } else if (a_kmajor && b_kmajor && gathered && k >= 2048 && gemm_wide_covers((int)m) && n % 64 == 0) {
-      const int64_t s = slices(n / 64, m * n);
-      if (s >= 1) {
-        const int64_t chunk = round_up<int64_t>(ceil_div<int64_t>(k, s), BK);
-        return put(GEMM_PATH_WIDE_GRADIENT, (int)round_up<int64_t>(m, 16), 64, (int)ceil_div<int64_t>(k, chunk),
-                   (int)chunk, (n / 64) * ceil_div<int64_t>(k, chunk));
-      }
-    }
-  }
-  const bool lean_ok = (a_kmajor ? round_up<int64_t>(m, 16) : k) % 4 == 0 && (b_kmajor ? n : k) % 4 == 0;
-  const GemmPlan pl = plan_gemm(m, n, k, workspace_bytes, lean_ok);
-  const int t = pl.tile % N_TILES;
-  const bool lean = env_int("BSIG_GEMM_LEAN", 1) && lean_ok && t <= TILE_96x128;
-  return put(lean ? GEMM_PATH_LEAN : GEMM_PATH_MFMA, kTileM[t], kTileN[t], pl.splits, pl.k_chunk,
-             ceil_div<int64_t>(m, kTileM[t]) * ceil_div<int64_t>(n, kTileN[t]) * pl.splits);
+  GemmRoute r;
+  BSIG_TRY(gemm_route(gemm_facts_dense(m, n, k, a_kmajor != 0, b_kmajor != 0, gathered != 0, epilogue,
+                                       workspace_bytes, matmul), &r));
+  out[0] = r.path; out[1] = r.tile_m; out[2] = r.tile_n; out[3] = r.splits; out[4] = r.k_chunk;
+  out[5] = (int32_t)std::min<int64_t>(r.workgroups, INT32_MAX);
+  out[6] = r.declined;
+  return BSIG_OK;
 }

@@ -75,6 +75,29 @@ def test_the_table_reaches_what_it_claims(monkeypatch):
     assert any(c.ws == 0 for c in G.CASES)
 
 
+def test_a_forced_tile_that_is_not_built_is_refused(monkeypatch):
+    """BSIG_GEMM_TILE indexes the tile table: a value beyond it, or (in a build without the whole-width tiles)
+    one of its two empty entries, is an error that names the value -- not a read past the table or another
+    tile's kernel on this tile's slice count."""
+    lib = _lib.load()
+    out = (ctypes.c_int32 * 8)()
+    before = os.environ.get('BSIG_GEMM_TILE')
+    for key in ('BSIG_GEMM_SPLITS', 'BSIG_DEBUG_F64_ACC_MIN_K'):
+        monkeypatch.delenv(key, raising=False)
+    monkeypatch.setenv('BSIG_GEMM_TILE', '7')
+    wide_tiles_built = lib.bsig_debug_gemm_path(300, 260, 530, 0, 0, 0, 0, 0, _lib.MATMUL_FP32, out) == 0
+    for value in ('8', '1000') + (() if wide_tiles_built else ('6', '7')):
+        monkeypatch.setenv('BSIG_GEMM_TILE', value)
+        assert lib.bsig_debug_gemm_path(300, 260, 530, 0, 0, 0, 0, 0, _lib.MATMUL_FP32, out) == _lib.BSIG_EINVAL
+        message = lib.bsig_last_error().decode()
+        assert 'BSIG_GEMM_TILE=%s ' % value in message and ('0..7' if wide_tiles_built else '0..5') in message, message
+        assert list(out) == [0] * 8
+    monkeypatch.setenv('BSIG_GEMM_TILE', '5')
+    assert _path(300, 260, 530)['tile_m'] == 96
+    monkeypatch.undo()
+    assert os.environ.get('BSIG_GEMM_TILE') == before
+
+
 def test_the_table_keeps_the_shapes_the_edges_need():
     shapes = {(c.m, c.n, c.k) for c in G.CASES}
     assert set(G.GENERIC_SHAPES) <= shapes
