@@ -26,10 +26,11 @@
 // via the column-0 threads, the layer's bias), so an update has no optimizer
 // kernel.  Data parallel: gradients go to the flat buffer, the caller
 // all-reduces it, then one flat Adam kernel runs (bsig_fit_grad / _apply).
+//
+// The parameter layout, the workspace carve and the forward / backward sequence of products are
+// shared with the fp64 mode: network_pass.h.
 #include "comm.h"
-#include "gemm.h"
-#include "../../include/bsig_matmul.h"
-#include "head.h"
+#include "network_pass.h"
 #include "persist.h"
 #include "persist_mdnn.h"
 #include "fit_protocol.h"
@@ -43,275 +44,7 @@
 
 namespace bsig {
 
-int adam_launch(float* p, const float* g, float* m, float* v, int64_t n, float lr,
-                float beta1, float beta2, float eps, int64_t t, const float* dyn,
-                hipStream_t st);
-int colsum_launch(const float* x, int64_t ld, int64_t rows, int64_t cols, float* out,
-                  void* workspace, size_t workspace_bytes, hipStream_t st);
-
-constexpr int64_t kAlign = 4;  // floats: every tensor starts 16-B aligned
-
-struct Layout {
-  int n_layers;                        // trunk layers
-  int64_t in_dim[BSIG_MAX_HIDDEN + 1]; // input width of trunk layer l / of the heads
-  int64_t w_off[BSIG_MAX_HIDDEN], b_off[BSIG_MAX_HIDDEN];
-  int64_t feat_dim;                    // F: width of the heads' input
-  int64_t nh;                          // Nh
-  int64_t head_w_off, head_b_off;
-  int64_t total;
-};
-
-static int make_layout(const bsig_mdn_cfg* c, Layout* L) {
-  BSIG_REQUIRE(c, "cfg is null");
-  BSIG_REQUIRE(c->input_dim >= 1, "cfg: input_dim must be >= 1");
-  BSIG_REQUIRE(c->n_hidden >= 0 && c->n_hidden <= BSIG_MAX_HIDDEN, "cfg: bad n_hidden");
-  BSIG_REQUIRE(!(c->rff_feats > 0 && c->n_hidden > 0), "cfg: MDRFF has no trunk (mdrff.py:18)");
-  BSIG_REQUIRE(c->rff_feats >= 0 && (c->rff_cos_only || c->rff_feats % 2 == 0),
-               "cfg: n_feat must be even (rff.py:105)");
-  L->n_layers = c->n_hidden;
-  int64_t off = 0, width = c->rff_feats > 0 ? c->rff_feats : c->input_dim;
-  for (int l = 0; l < c->n_hidden; ++l) {
-    BSIG_REQUIRE(c->hidden[l] >= 1, "cfg: hidden layer width must be >= 1");
-    L->in_dim[l] = width;
-    L->w_off[l] = off; off = round_up<int64_t>(off + (int64_t)c->hidden[l] * width, kAlign);
-    L->b_off[l] = off; off = round_up<int64_t>(off + c->hidden[l], kAlign);
-    width = c->hidden[l];
-  }
-  L->in_dim[c->n_hidden] = width;
-  L->feat_dim = width;
-  L->nh = bsig_head_width(&c->head);
-  BSIG_REQUIRE(L->nh >= 1, "cfg: bad head dims");
-  L->head_w_off = off; off = round_up<int64_t>(off + L->nh * width, kAlign);
-  L->head_b_off = off; off = round_up<int64_t>(off + L->nh, kAlign);
-  L->total = off;
-  return BSIG_OK;
-}
-
-// ---- workspace carve ------------------------------------------------------
-struct Scratch {
-  float* feat;                      // [B, F] RFF features (MDRFF, not hoisted)
-  float* h[BSIG_MAX_HIDDEN];        // trunk activations [B, hidden_l]
-  float* dz[2];                     // ping-pong [B, max hidden]
-  float* o;                         // [B, ld_o] raw head outputs
-  float* d_o;                       // [B, ld_o]
-  int64_t ld_o;                     // Nh -- or ceil16(Nh) where the whole-width products take these buffers (gemm_wide.h)
-  int32_t* tickets;                 // kWideTickets zeroed words: in-launch combine of the head product's K slices
-  float* head_ws; size_t head_ws_bytes;
-  float* gemm_ws; size_t gemm_ws_bytes;
-  float* colsum_ws; size_t colsum_ws_bytes;
-  size_t total_bytes;
-  int math;                         // matmul precision of every product issued on this scratch (gemm.h; a plan's: plan_mem)
-};
-
-constexpr int kWideTickets = 1024;
-
-static size_t gemm_ws_need(const bsig_mdn_cfg* c, const Layout& L, int64_t B) {
-  size_t need = 0;
-  auto upd = [&](int64_t m, int64_t n, int64_t k) {
-    need = std::max(need, bsig_gemm_workspace_bytes(m, n, k));
-  };
-  if (c->rff_feats > 0) upd(B, c->rff_cos_only ? c->rff_feats : c->rff_feats / 2, c->input_dim);
-  for (int l = 0; l < L.n_layers; ++l) {
-    upd(B, c->hidden[l], L.in_dim[l]);       // forward
-    upd(c->hidden[l], L.in_dim[l], B);       // dW
-    if (l > 0) upd(B, L.in_dim[l], c->hidden[l]);  // dX
-  }
-  upd(B, L.nh, L.feat_dim);
-  upd(L.nh, L.feat_dim, B);
-  if (L.n_layers > 0) upd(B, L.feat_dim, L.nh);
-  return need;
-}
-
-static void carve(const bsig_mdn_cfg* c, const Layout& L, int64_t B, void* base, Scratch* s) {
-  size_t off = 0;
-  s->math = BSIG_MATMUL_FP32;
-  auto take = [&](size_t floats) {
-    float* p = base ? reinterpret_cast<float*>(reinterpret_cast<char*>(base) + off) : nullptr;
-    off += round_up<size_t>(floats * sizeof(float), 256);
-    return p;
-  };
-  s->feat = c->rff_feats > 0 ? take((size_t)B * c->rff_feats) : nullptr;
-  int64_t hmax = 0;
-  for (int l = 0; l < L.n_layers; ++l) {
-    s->h[l] = take((size_t)B * c->hidden[l]);
-    hmax = std::max<int64_t>(hmax, c->hidden[l]);
-  }
-  s->dz[0] = hmax ? take((size_t)B * hmax) : nullptr;
-  s->dz[1] = hmax ? take((size_t)B * hmax) : nullptr;
-  // large minibatches of a head the whole-width kernels cover: pitch ceil16(Nh) (dO is their k-major
-  // operand at exactly that pitch; the forward product stores the padded width)
-  s->ld_o = (B >= 2048 && gemm_wide_covers((int)L.nh) && B <= 64 * (int64_t)kWideTickets) ? round_up<int64_t>(L.nh, 16) : L.nh;
-  s->o = take((size_t)B * s->ld_o);
-  s->d_o = take((size_t)B * s->ld_o);
-  s->tickets = reinterpret_cast<int32_t*>(take(kWideTickets));
-  s->head_ws_bytes = bsig_head_workspace_bytes(&c->head, B);
-  s->head_ws = take(s->head_ws_bytes / sizeof(float) + 1);
-  s->gemm_ws_bytes = gemm_ws_need(c, L, B);
-  s->gemm_ws = take(s->gemm_ws_bytes / sizeof(float) + 1);
-  s->colsum_ws_bytes = (size_t)64 * std::max<int64_t>(L.nh, std::max<int64_t>(hmax, 1)) * sizeof(float);
-  s->colsum_ws = take(s->colsum_ws_bytes / sizeof(float));
-  s->total_bytes = off;
-}
-
-// ---- passes ---------------------------------------------------------------
-// Where the estimator's input rows come from.  Logical minibatch row i reads
-// source index i + (dyn[0] + delta) * dyn_stride + dyn_base, looked up in
-// `rows` when that is given.  With `is_feat` the source already holds RFF
-// features (hoisted projection) and `rows` must be null.
-struct Inputs {
-  const float* x = nullptr; int64_t ldx = 0;
-  const int32_t* rows = nullptr;
-  const int32_t* dyn = nullptr; int64_t dyn_stride = 0, dyn_base = 0;
-  bool is_feat = false;
-  const float* rff_coeff = nullptr; int64_t ld_coeff = 0; const float* rff_offset = nullptr;
-};
-
-// Adam fused into the dW GEMMs (single rank)
-struct AdamFuse {
-  float* m; float* v; const float* dyn; float beta1, beta2, eps;
-};
-
-static void set_src_a(GemmParams& g, const float* x, int64_t ld, const Inputs* in, int delta) {
-  g.a = x; g.lda = ld; g.a_kmajor = 0;
-  if (in) {
-    g.a_rows = in->rows; g.dyn = in->dyn; g.dyn_delta = delta;
-    g.a_dyn_stride = in->dyn_stride; g.a_dyn_base = in->dyn_base;
-  }
-}
-static void set_src_b_kmajor(GemmParams& g, const float* x, int64_t ld, const Inputs* in,
-                             int delta) {
-  g.b = x; g.ldb = ld; g.b_kmajor = 1;
-  if (in) {
-    g.b_rows = in->rows; g.dyn = in->dyn; g.dyn_delta = delta;
-    g.b_dyn_stride = in->dyn_stride; g.b_dyn_base = in->dyn_base;
-  }
-}
-
-static int rff_project(const bsig_mdn_cfg* c, const Inputs& in, int64_t rows, float* feats,
-                       void* ws, size_t ws_bytes, int math, hipStream_t st) {
-  BSIG_REQUIRE(in.rff_coeff, "MDRFF needs rff_coeff");
-  BSIG_REQUIRE(!(c->rff_cos_only && !in.rff_offset), "cos-only RFF needs an offset");
-  GemmParams g;
-  set_src_a(g, in.x, in.ldx, &in, 0);
-  g.b = in.rff_coeff; g.ldb = in.ld_coeff;
-  g.c = feats; g.ldc = c->rff_feats;
-  g.m = (int)rows; g.n = c->rff_cos_only ? c->rff_feats : c->rff_feats / 2; g.k = c->input_dim;
-  g.epilogue = c->rff_cos_only ? BSIG_EPI_COS_OFF : BSIG_EPI_COS_SIN;
-  g.bias = in.rff_offset; g.alpha = c->rff_scale; g.math = math;
-  return gemm_run(g, ws, ws_bytes, st);
-}
-
-// trunk (or RFF) + heads -> o ; leaves activations in s.h / s.feat
-static int forward_pass(const bsig_mdn_cfg* c, const Layout& L, const float* params,
-                        const Inputs& in, int64_t B, const Scratch& s, float* o, int64_t ldo,
-                        hipStream_t st, int* n_sig = nullptr) {
-  const float* feat = in.x; int64_t ldf = in.ldx; const Inputs* src = &in;
-  if (c->rff_feats > 0 && !in.is_feat) {
-    BSIG_TRY(rff_project(c, in, B, s.feat, s.gemm_ws, s.gemm_ws_bytes, s.math, st));
-    feat = s.feat; ldf = c->rff_feats; src = nullptr;
-  }
-  for (int l = 0; l < L.n_layers; ++l) {
-    GemmParams g;
-    set_src_a(g, feat, ldf, src, 0);
-    g.b = params + L.w_off[l]; g.ldb = L.in_dim[l];
-    g.c = s.h[l]; g.ldc = c->hidden[l];
-    g.m = (int)B; g.n = c->hidden[l]; g.k = (int)L.in_dim[l];
-    g.epilogue = BSIG_EPI_BIAS_ACT; g.act = c->activation; g.bias = params + L.b_off[l]; g.math = s.math;
-    BSIG_TRY(gemm_run(g, s.gemm_ws, s.gemm_ws_bytes, st));
-    feat = s.h[l]; ldf = c->hidden[l]; src = nullptr;
-  }
-  GemmParams g;
-  set_src_a(g, feat, ldf, src, 0);
-  g.b = params + L.head_w_off; g.ldb = L.feat_dim;
-  g.c = o; g.ldc = ldo;
-  g.m = (int)B; g.n = (int)L.nh; g.k = (int)L.feat_dim;
-  g.epilogue = BSIG_EPI_BIAS; g.bias = params + L.head_b_off; g.math = s.math;
-  if (o == s.o) { g.combine_tickets = s.tickets; g.combine_capacity = kWideTickets; }   // (the scratch buffer has the padded pitch the combine stores)
-  if (n_sig && c->head.eps_noise != 0.f) {   // sum(exp(pre_diag)) partials for the jitter scale
-    g.expsum = s.head_ws;
-    g.expsum_col0 = c->head.n_comp + c->head.out_dim * c->head.n_comp;
-    g.expsum_ncols = c->head.out_dim * c->head.n_comp;
-  }
-  int n = 0;
-  BSIG_TRY(gemm_run(g, s.gemm_ws, s.gemm_ws_bytes, st, &n));
-  if (n_sig) *n_sig = n <= head_sig_capacity() ? n : 0;
-  if (n > head_sig_capacity()) { set_error("head GEMM produced %d exp partials", n); return BSIG_EUNSUPPORTED; }
-  return BSIG_OK;
-}
-
-// dW[nout, nin] = dY^T X (+ fused Adam) for one layer
-static int weight_grad(const float* dy, int64_t nout, int64_t ld_dy, const float* xin, int64_t ldin,
-                       const Inputs* src, int delta, int64_t nin, int64_t B, float* params,
-                       float* grads, int64_t w_off, int64_t b_off, const AdamFuse* fuse,
-                       const Scratch& s, hipStream_t st, const HeadBiasPartials* bias_partials = nullptr) {
-  GemmParams g;
-  g.a = dy; g.lda = ld_dy; g.a_kmajor = 1;
-  set_src_b_kmajor(g, xin, ldin, src, delta);
-  g.m = (int)nout; g.n = (int)nin; g.k = (int)B; g.ldc = nin; g.math = s.math;
-  if (fuse) {
-    g.epilogue = EPI_ADAM;
-    g.c = params + w_off; g.adam_m = fuse->m + w_off; g.adam_v = fuse->v + w_off;
-    g.adam_dyn = fuse->dyn; g.beta1 = fuse->beta1; g.beta2 = fuse->beta2; g.adam_eps = fuse->eps;
-    g.bias_p = params + b_off; g.bias_m = fuse->m + b_off; g.bias_v = fuse->v + b_off;
-    g.bias_g = grads + b_off;
-    if (bias_partials && bias_partials->n > 1) {   // the finishing kernel's slab sums, added up by the reduce + Adam kernel
-      g.bias_g = bias_partials->sums; g.bias_g_n = bias_partials->n; g.bias_g_stride = bias_partials->stride;
-    }
-  } else {
-    g.epilogue = BSIG_EPI_NONE;
-    g.c = grads + w_off;
-  }
-  return gemm_run(g, s.gemm_ws, s.gemm_ws_bytes, st);
-}
-
-// backward from s.d_o.  Every product that READS a weight matrix is issued
-// before the GEMM that updates it (fused Adam).  `delta` = offset of the step
-// counter seen by these kernels relative to the forward half.
-static int backward_pass(const bsig_mdn_cfg* c, const Layout& L, float* params,
-                         const Inputs& in, int delta, int64_t B, const Scratch& s, float* grads,
-                         const AdamFuse* fuse, hipStream_t st, const HeadBiasPartials* bias_partials = nullptr) {
-  // input of the heads
-  const float* feat; int64_t ldf; const Inputs* fsrc = nullptr;
-  if (L.n_layers > 0) { feat = s.h[L.n_layers - 1]; ldf = c->hidden[L.n_layers - 1]; }
-  else if (c->rff_feats > 0 && !in.is_feat) { feat = s.feat; ldf = c->rff_feats; }
-  else { feat = in.x; ldf = in.ldx; fsrc = &in; }
-  int cur = 0;
-  if (L.n_layers > 0) {   // dz_L = (dO W_heads) * act'(h_L)   [reads W_heads]
-    GemmParams g;
-    g.a = s.d_o; g.lda = s.ld_o;
-    g.b = params + L.head_w_off; g.ldb = L.feat_dim; g.b_kmajor = 1;
-    g.c = s.dz[cur]; g.ldc = L.feat_dim;
-    g.m = (int)B; g.n = (int)L.feat_dim; g.k = (int)L.nh;
-    g.epilogue = BSIG_EPI_MUL_DACT; g.act = c->activation; g.aux = feat; g.ldaux = ldf; g.math = s.math;
-    BSIG_TRY(gemm_run(g, s.gemm_ws, s.gemm_ws_bytes, st));
-  }
-  // heads: dW = dO^T feat (bias gradient = column sums of dO, from the finish kernel)
-  BSIG_TRY(weight_grad(s.d_o, L.nh, s.ld_o, feat, ldf, fsrc, delta, L.feat_dim, B, params, grads,
-                       L.head_w_off, L.head_b_off, fuse, s, st, bias_partials));
-  for (int l = L.n_layers - 1; l >= 0; --l) {
-    const int64_t hw = c->hidden[l];
-    const float* xin; int64_t ldin; const Inputs* xsrc = nullptr;
-    if (l > 0) { xin = s.h[l - 1]; ldin = c->hidden[l - 1]; }
-    else { xin = in.x; ldin = in.ldx; xsrc = &in; }
-    BSIG_TRY(colsum_launch(s.dz[cur], hw, B, hw, grads + L.b_off[l], s.colsum_ws,
-                           s.colsum_ws_bytes, st));
-    if (l > 0) {           // dz_{l-1} = (dz_l W_l) * act'(h_{l-1})   [reads W_l]
-      GemmParams g;
-      g.a = s.dz[cur]; g.lda = hw;
-      g.b = params + L.w_off[l]; g.ldb = L.in_dim[l]; g.b_kmajor = 1;
-      g.c = s.dz[cur ^ 1]; g.ldc = L.in_dim[l];
-      g.m = (int)B; g.n = (int)L.in_dim[l]; g.k = (int)hw;
-      g.epilogue = BSIG_EPI_MUL_DACT; g.act = c->activation; g.aux = xin; g.ldaux = ldin; g.math = s.math;
-      BSIG_TRY(gemm_run(g, s.gemm_ws, s.gemm_ws_bytes, st));
-    }
-    BSIG_TRY(weight_grad(s.dz[cur], hw, hw, xin, ldin, xsrc, delta, L.in_dim[l], B, params, grads,
-                         L.w_off[l], L.b_off[l], fuse, s, st));
-    cur ^= 1;
-  }
-  return BSIG_OK;
-}
-
-static int head_nll(const bsig_mdn_cfg* c, const Layout& L, const Scratch& s, const float* y,
+static int head_nll(const bsig_mdn_cfg* c, const Layout& L, const Scratch<float>& s, const float* y,
                     int64_t ldy, const int32_t* y_rows, int64_t B, int64_t norm_batch,
                     const float* noise, uint64_t seed, uint64_t stream_id,
                     const uint64_t* dyn_rng, float* loss, const int32_t* loss_slot, bool bwd,
@@ -422,7 +155,7 @@ static bool feat_cache_applies(const bsig_fit_plan* p, int64_t n_train) {
   return p->hoist && p->feat_cache && n_train <= p->n_updates * p->batch;
 }
 
-struct PlanMem { Scratch tr, te; float* feats; float* big_ws; int32_t* iota; void* persist_ws; };
+struct PlanMem { Scratch<float> tr, te; float* feats; float* big_ws; int32_t* iota; void* persist_ws; };
 
 // fit_begin_kernel clears up to four regions: the persistent kernels' exchange areas (2), the Adam
 // moments (2; not where a single-rank persistent plan starts them in registers) -- and, where that
@@ -531,9 +264,9 @@ static int enqueue_persistent(bsig_fit_plan* p, int n, hipStream_t st, int eval_
   return persist_mdnn_run(persist_mdnn_shape(p), p->mg, pb, n, st);
 }
 
-static Inputs train_inputs(const bsig_fit_plan* p, const PlanMem& m) {
+static Inputs<float> train_inputs(const bsig_fit_plan* p, const PlanMem& m) {
   const bsig_fit_buffers& b = p->buf;
-  Inputs in;
+  Inputs<float> in;
   in.dyn = b.state + ST_STEP; in.dyn_stride = p->batch;
   in.rff_coeff = b.rff_coeff; in.ld_coeff = b.ld_coeff; in.rff_offset = b.rff_offset;
   if (p->hoist) {
@@ -544,9 +277,9 @@ static Inputs train_inputs(const bsig_fit_plan* p, const PlanMem& m) {
   return in;
 }
 
-static Inputs eval_inputs(const bsig_fit_plan* p, const PlanMem& m) {
+static Inputs<float> eval_inputs(const bsig_fit_plan* p, const PlanMem& m) {
   const bsig_fit_buffers& b = p->buf;
-  Inputs in;
+  Inputs<float> in;
   in.rff_coeff = b.rff_coeff; in.ld_coeff = b.ld_coeff; in.rff_offset = b.rff_offset;
   if (p->hoist) {
     in.x = m.feats; in.ldx = p->cfg.rff_feats; in.is_feat = true;
@@ -564,7 +297,7 @@ static int enqueue_grad(bsig_fit_plan* p, hipStream_t st, bool fuse_adam) {
   if (p->buf.x_kind != BSIG_X_ROWS) { set_error("per-phase update on factor rows"); return BSIG_EUNSUPPORTED; }
   PlanMem m; plan_mem(p, &m);
   const bsig_fit_buffers& b = p->buf;
-  const Inputs in = train_inputs(p, m);
+  const Inputs<float> in = train_inputs(p, m);
   HeadDyn hd;
   hd.y_dyn = b.state + ST_STEP; hd.y_dyn_stride = p->batch;
   hd.hook.state = b.state; hd.hook.kind = 1;
@@ -572,7 +305,7 @@ static int enqueue_grad(bsig_fit_plan* p, hipStream_t st, bool fuse_adam) {
   AdamFuse fuse{b.exp_avg, b.exp_avg_sq, st_adam(b.state), p->cfg.beta1, p->cfg.beta2, p->cfg.adam_eps};
   const uint64_t* rng = st_rng(b.state);
   int n_sig = 0;
-  BSIG_TRY(forward_pass(&p->cfg, p->L, b.params, in, p->batch, m.tr, m.tr.o, m.tr.ld_o, st,
+  BSIG_TRY(forward_pass(&p->cfg, p->L, b.params, in, p->cfg.rff_scale, p->batch, m.tr, m.tr.o, m.tr.ld_o, st,
                         &n_sig));
   hd.n_sig_ready = n_sig;
   // a fused Adam step whose weight gradient runs as the whole-width kernel + reduce: the head bias
@@ -604,9 +337,9 @@ static int enqueue_eval(bsig_fit_plan* p, hipStream_t st) {
     BSIG_CHECK_LAUNCH("eval_noop");
     return BSIG_OK;
   }
-  const Inputs in = eval_inputs(p, m);
+  const Inputs<float> in = eval_inputs(p, m);
   int n_sig = 0;
-  BSIG_TRY(forward_pass(&p->cfg, p->L, b.params, in, b.n_test, m.te, m.te.o, m.te.ld_o, st,
+  BSIG_TRY(forward_pass(&p->cfg, p->L, b.params, in, p->cfg.rff_scale, b.n_test, m.te, m.te.o, m.te.ld_o, st,
                         &n_sig));
   hd.n_sig_ready = n_sig;
   return head_nll(&p->cfg, p->L, m.te, b.y_test, b.ldy_test, nullptr, b.n_test, b.n_test,
@@ -620,7 +353,7 @@ static int enqueue_eval(bsig_fit_plan* p, hipStream_t st) {
 static int enqueue_hoisted_rff(bsig_fit_plan* p, hipStream_t st) {
   PlanMem m; plan_mem(p, &m);
   const bsig_fit_buffers& b = p->buf;
-  Inputs in;
+  Inputs<float> in;
   in.x = b.x_train; in.ldx = b.ldx_train;
   in.rff_coeff = b.rff_coeff; in.ld_coeff = b.ld_coeff; in.rff_offset = b.rff_offset;
   // feature cache: each distinct training row once (it is visited ~n_updates*batch/n_train
@@ -632,11 +365,11 @@ static int enqueue_hoisted_rff(bsig_fit_plan* p, hipStream_t st) {
   // 512 workgroups, two per CU, where 800 + 200 rows were 416 + 128 in two launches
   if (p->feat_unique && b.n_test > 0 && b.ldx_test == b.ldx_train &&
       b.x_test == b.x_train + (size_t)b.n_train * b.ldx_train)
-    return rff_project(&p->cfg, in, train_rows + b.n_test, m.feats, m.big_ws, p->big_gemm_ws_bytes, p->matmul, st);
-  BSIG_TRY(rff_project(&p->cfg, in, train_rows, m.feats, m.big_ws, p->big_gemm_ws_bytes, p->matmul, st));
+    return rff_project(&p->cfg, in, p->cfg.rff_scale, train_rows + b.n_test, m.feats, m.big_ws, p->big_gemm_ws_bytes, p->matmul, st);
+  BSIG_TRY(rff_project(&p->cfg, in, p->cfg.rff_scale, train_rows, m.feats, m.big_ws, p->big_gemm_ws_bytes, p->matmul, st));
   if (b.n_test > 0) {
     in.x = b.x_test; in.ldx = b.ldx_test; in.rows = nullptr;
-    BSIG_TRY(rff_project(&p->cfg, in, b.n_test, m.feats + (size_t)train_rows * p->cfg.rff_feats,
+    BSIG_TRY(rff_project(&p->cfg, in, p->cfg.rff_scale, b.n_test, m.feats + (size_t)train_rows * p->cfg.rff_feats,
                          m.big_ws, p->big_gemm_ws_bytes, p->matmul, st));
   }
   return BSIG_OK;
@@ -716,7 +449,7 @@ extern "C" int bsig_mdn_param_offsets(const bsig_mdn_cfg* cfg, int64_t* offsets,
 extern "C" size_t bsig_mdn_workspace_bytes(const bsig_mdn_cfg* cfg, int64_t max_batch) {
   Layout L;
   if (make_layout(cfg, &L) != BSIG_OK) return 0;
-  Scratch s;
+  Scratch<float> s;
   carve(cfg, L, std::max<int64_t>(max_batch, 1), nullptr, &s);
   return s.total_bytes;
 }
@@ -731,16 +464,16 @@ extern "C" int bsig_mdn_head_forward(const bsig_mdn_cfg* cfg, const float* param
   BSIG_TRY(make_layout(cfg, &L));
   BSIG_REQUIRE(params && x && head_out && batch >= 1, "head_forward: bad args");
   BSIG_REQUIRE(ldx >= cfg->input_dim && ld_head >= L.nh, "head_forward: leading dims too small");
-  Scratch s;
+  Scratch<float> s;
   carve(cfg, L, batch, nullptr, &s);
   BSIG_REQUIRE(workspace && workspace_bytes >= s.total_bytes,
                "head_forward: workspace %zu < %zu", workspace_bytes, s.total_bytes);
   carve(cfg, L, batch, workspace, &s);
   s.tickets = nullptr;   // (nobody zeroes a caller's workspace: the head product reduces in its own kernel)
-  Inputs in;
+  Inputs<float> in;
   in.x = x; in.ldx = ldx; in.rows = x_rows;
   in.rff_coeff = rff_coeff; in.ld_coeff = ld_coeff; in.rff_offset = rff_offset;
-  return forward_pass(cfg, L, params, in, batch, s, head_out, ld_head, as_stream(stream));
+  return forward_pass(cfg, L, params, in, cfg->rff_scale, batch, s, head_out, ld_head, as_stream(stream));
 }
 
 extern "C" int bsig_mdn_loss_grad(const bsig_mdn_cfg* cfg, const float* params,
@@ -756,18 +489,18 @@ extern "C" int bsig_mdn_loss_grad(const bsig_mdn_cfg* cfg, const float* params,
   BSIG_REQUIRE(params && x && y && grads && batch >= 1 && norm_batch >= 1,
                "loss_grad: bad args");
   BSIG_REQUIRE(ldx >= cfg->input_dim && ldy >= cfg->head.out_dim, "loss_grad: leading dims");
-  Scratch s;
+  Scratch<float> s;
   carve(cfg, L, batch, nullptr, &s);
   BSIG_REQUIRE(workspace && workspace_bytes >= s.total_bytes, "loss_grad: workspace %zu < %zu",
                workspace_bytes, s.total_bytes);
   carve(cfg, L, batch, workspace, &s);
   s.tickets = nullptr;   // (nobody zeroes a caller's workspace: the head product reduces in its own kernel)
   hipStream_t st = as_stream(stream);
-  Inputs in;
+  Inputs<float> in;
   in.x = x; in.ldx = ldx; in.rows = rows;
   in.rff_coeff = rff_coeff; in.ld_coeff = ld_coeff; in.rff_offset = rff_offset;
   int n_sig = 0;
-  BSIG_TRY(forward_pass(cfg, L, params, in, batch, s, s.o, s.ld_o, st, &n_sig));
+  BSIG_TRY(forward_pass(cfg, L, params, in, cfg->rff_scale, batch, s, s.o, s.ld_o, st, &n_sig));
   HeadDyn hd;
   hd.n_sig_ready = n_sig;
   BSIG_TRY(head_nll(cfg, L, s, y, ldy, rows, batch, norm_batch, noise, seed, stream_id, nullptr,
@@ -800,7 +533,7 @@ extern "C" int bsig_fit_create_ex(const bsig_mdn_cfg* cfg, int64_t batch,
   p->batch = batch; p->max_test = max_test_rows; p->norm_batch = batch;
   p->n_updates = n_updates; p->n_evals = count_logging_points(n_updates);
   p->matmul = (plan_flags & BSIG_PLAN_SPLIT_BF16) ? BSIG_MATMUL_SPLIT_BF16 : BSIG_MATMUL_FP32;
-  Scratch s;
+  Scratch<float> s;
   carve(cfg, p->L, batch, nullptr, &s); p->train_ws_bytes = s.total_bytes;
   carve(cfg, p->L, std::max<int64_t>(max_test_rows, 1), nullptr, &s);
   p->test_ws_bytes = s.total_bytes;

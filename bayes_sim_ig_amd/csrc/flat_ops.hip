@@ -1,7 +1,7 @@
 // Flat-buffer helpers of the fit loop: fused Adam over the flat parameter
 // buffer (torch.optim.Adam defaults, mdnn.py:203,234), column sums for the
 // bias gradients, theta normalisation (mdnn.py:245-248), strided row copies.
-#include "common.h"
+#include "flat_ops.h"
 
 #include <algorithm>
 #include <cmath>

@@ -16,6 +16,7 @@
 // Row sums (loss, jitter terms) are reduced with wavefront shuffles, one
 // partial per workgroup, summed in a fixed order by the finishing kernel
 // (bitwise reproducible, no atomics).
+#include "flat_ops.h"
 #include "head.h"
 #include "head_device.h"
 
@@ -481,9 +482,6 @@ __global__ __launch_bounds__(256) void mdn_outputs_kernel(
 }
 
 // ---------------------------------------------------------------- host side
-int colsum_launch(const float* x, int64_t ld, int64_t rows, int64_t cols, float* out,
-                  void* workspace, size_t workspace_bytes, hipStream_t st);
-
 constexpr int kWavesPerBlock = 8;     // diag kernel: rows per workgroup
 constexpr int kMaxSlabs = 64;         // finish kernel: row slabs for tall batches
 

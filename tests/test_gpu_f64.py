@@ -307,6 +307,41 @@ def test_one_step_grads_and_adam(B, tag):
         np.testing.assert_allclose(v.float().cpu().numpy(), g['w1.' + k], rtol=0, atol=1e-4 * lr, err_msg=k)
 
 
+DEEP_TRUNKS = [((16, 12, 8), act, False) for act in ('Tanh', 'ReLU', 'LeakyReLU', 'Sigmoid', 'Identity')] + \
+    [((16, 12, 8), 'Tanh', True), ((12,) * 8, 'Tanh', False), ((12,) * 8, 'ReLU', False)]
+
+
+@pytest.mark.parametrize('hidden,act,full', DEEP_TRUNKS, ids=lambda v: str(v).replace(' ', ''))
+def test_one_step_grads_on_deeper_trunks(B, hidden, act, full):
+    """The per-phase pass away from the reference's defaults: trunks of three and of eight (the maximum)
+    layers, every activation, both covariance shapes.  fp32-representable weights and data, a given noise;
+    loss and every parameter's gradient within 1e-12 of the fp64 oracle, the rule of the one-step test above
+    (the oracle's own spread over four orders of the input columns at these shapes: <= 6.7e-16)."""
+    from oracle import estimators as oest
+    d, k, b, i = 3, 3, 32, 10
+    B.MDNN.EPS_NOISE = 1e-5
+    kw = dict(input_dim=i, output_dim=d, output_lows=np.zeros(d), output_highs=np.ones(d), n_gaussians=k,
+              full_covariance=full, hidden_layers=hidden, activation=getattr(torch.nn, act), lr=1e-3)
+    torch.manual_seed(11)
+    m = B.MDNN(device=DEV, **kw)
+    w0 = {n: v.detach().cpu().clone() for n, v in m.state_dict().items()}
+    m.double()
+    gen = torch.Generator().manual_seed(12)
+    x, y, noise = torch.randn(b, i, generator=gen), torch.rand(b, d, generator=gen), torch.rand(b, d, k, generator=gen)
+    loss = m.loss_and_grad(x.to(DEV), y.to(DEV), noise=noise.to(DEV))
+    grads = {n: p.grad.cpu().numpy().copy() for n, p in m.named_parameters()}
+    with default_f64():
+        o = oest.OracleMDNN(eps_noise=1e-5, **kw)
+        o.load_state_dict(w0)
+        ref_loss = o.mdn_loss_fn(*o.forward(x.double(), noise=noise.double()), y.double())
+        ref_loss.backward()
+        ref_grads = {n: p.grad.numpy().copy() for n, p in o.named_parameters()}
+    assert len(grads) == 2 * (len(hidden) + (4 if full else 3)) and set(grads) == set(ref_grads)
+    _close(float(loss.item()), float(ref_loss.item()), 1e-12, 'loss')
+    for n in grads:
+        _close(grads[n], ref_grads[n], 1e-12, 'grad ' + n)
+
+
 # ------------------------------------------------------------------ chunks
 CHUNKS = {
     'mdnn_start': dict(cls='MDNN', summarizer='summary_start', d=2, k=10, hidden=(24, 24), full=False),
