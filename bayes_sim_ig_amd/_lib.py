@@ -314,6 +314,15 @@ HEADERS['bsig_sysid.h'] = {
     'bsig_sysid': (C.c_int, [vp, vp, vp, i64] + [C.c_int] * 4 + [f64, i64, vp, vp]),
     'bsig_sysid_f64': (C.c_int, [vp, vp, vp, i64] + [C.c_int] * 4 + [f64, i64, vp, vp]),
 }
+# open-loop rollouts of the two analytic tasks, with episode ends
+SIM_PENDULUM, SIM_CARTPOLE = 0, 1                              # include/bsig_sim.h
+SIM_TASKS = {'pendulum': SIM_PENDULUM, 'cartpole': SIM_CARTPOLE}
+SIM_EPISODES, SIM_STEP_BLOCK, SIM_GRID_CAP = 64, 8, 2048       # include/bsig_sim.h
+HEADERS['bsig_sim.h'] = {
+    'bsig_sim_dims': (C.c_int, [C.c_int] + [C.POINTER(C.c_int)] * 3),
+    'bsig_sim_rollout': (C.c_int, [C.c_int] + [vp] * 6 + [i64] + [C.c_int] * 3 + [vp, vp]),
+    'bsig_sim_rollout_f64': (C.c_int, [C.c_int] + [vp] * 6 + [i64] + [C.c_int] * 3 + [vp, vp]),
+}
 COMM_ID_BYTES = 128
 EXCHANGE_SUM, EXCHANGE_BROADCAST = 0, 1
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int, vp, i64, C.c_int, vp)
@@ -459,6 +468,8 @@ class Precision:
         'kme_ragged': ('bsig_kme_ragged', 'bsig_kme_ragged_f64'),
         'kme_rows_ragged': ('bsig_kme_rows_ragged', 'bsig_kme_rows_ragged_f64'),
         'sysid': ('bsig_sysid', 'bsig_sysid_f64'),
+        # the rollouts of the analytic tasks (include/bsig_sim.h): fp32 data or double data, double arithmetic
+        'sim_rollout': ('bsig_sim_rollout', 'bsig_sim_rollout_f64'),
         # the input-side companions of normalize_rows / copy_rows (the statistics of rows, and the copy that
         # standardises)
         'input_norm_stats': ('bsig_input_norm_stats', 'bsig_input_norm_stats_f64'),

@@ -35,6 +35,9 @@ rm -f "$OUT"/obj/fit_persistent_v1.*      # (retired in round 6: an object of an
 for f in summarizers gemm_f32 gemm_tile_64 gemm_tile_128 gemm_tile_128x32 gemm_tile_128x64 gemm_tile_128x96 gemm_tile_96x128 gemm_lean_64 gemm_lean_128 gemm_lean_128x32 gemm_lean_128x64 gemm_lean_128x96 gemm_lean_96x128 gemm_wide gemm_split_bf16 $WIDE_TILES mdn_head flat_ops estimator fit_persistent fit_deferred_eval fit_persistent_mdnn fit_persistent_mdnn_stream signature_ex logsignature input_norm rff_bandwidth xcorr kme xcorr_ragged kme_ragged sysid; do
   build_one "$f" "$SRC/$f.hip" ""
 done
+# the rollouts state every step as single double operations (include/bsig_sim.h): nothing contracts to an fma
+build_one sim "$SRC/sim.hip" "-ffp-contract=off"
+build_one sim_f64 "$SRC/f64/sim_f64.hip" "-ffp-contract=off"
 for f in api comm; do
   build_one "$f" "$SRC/$f.cpp" "-x hip"
 done
