@@ -1,5 +1,5 @@
-"""GPU checks of the summarizers' fp64 mode (``dtype=torch.float64``: csrc/f64/summarizers_f64.hip,
-include/bsig_f64.h) through the public Python functions, against oracle/summarize.py and
+"""GPU checks of the summarizers' fp64 mode (``dtype=torch.float64``: the double instantiation of csrc/summaries.h,
+csrc/f64/summarizers_f64.hip, include/bsig_f64.h) through the public Python functions, against oracle/summarize.py and
 oracle/signature.py run on the CPU on the same double inputs (torch.randn, fixed seeds).
 
 Bounds -- derived, none of them tuned (U = 2^-53):
@@ -53,6 +53,26 @@ def _check_rows(got, n, width):
     assert got.stride(1) == 1 and (n == 1 or got.stride(0) % 2 == 0) and got.data_ptr() % 16 == 0
 
 
+def _views(n, width):
+    """(flat NaN-filled buffer, its [n, width] view) twice: 16-byte aligned rows at an even pitch -- the 16-byte
+    stores of the shared kernels -- and rows that start one element in at an odd pitch -- their element loops."""
+    even = width + width % 2
+    for off, pitch in ((0, even + 2), (1, even + 3)):
+        buf = torch.full(((n + 1) * pitch + off,), float('nan'), dtype=F64, device=DEV)
+        view = buf[off:off + n * pitch].view(n, pitch)[:, :width]
+        assert view.data_ptr() % 16 == 8 * off and view.stride(0) % 2 == off
+        yield buf, view
+
+
+def _assert_untouched(buf, view):
+    """every element of the buffer outside the view is still NaN"""
+    n, width = view.shape
+    pitch, off = view.stride(0), (view.data_ptr() - buf.data_ptr()) // 8
+    outside = torch.ones_like(buf, dtype=torch.bool)
+    outside[off:off + n * pitch].view(n, pitch)[:, :width] = False
+    assert torch.isnan(buf[outside]).all() and not torch.isnan(view).any()
+
+
 # ------------------------------------------------------------------ 1. summary_start / summary_waypts
 START_SHAPES = [(1, 3, 2, 1, 1), (5, 12, 11, 3, 2), (3, 10, 10, 2, 1)]     # pads both | crops | as long as max_t = 10
 
@@ -78,27 +98,74 @@ def test_start_and_waypts_are_bitwise_the_oracle(B, shape, max_t):
 CC_SHAPES = [(2, 3, 3, 2, 1), (4, 20, 20, 3, 3), (2, 12, 12, 52, 1), (1, 2, 2, 2, 1), (2, 4, 4, 2100, 1)]
 
 
-@pytest.mark.parametrize('use_diff', [False, True])
-@pytest.mark.parametrize('shape', CC_SHAPES)
-def test_cross_correlation_against_the_oracle(B, shape, use_diff):
+@functools.lru_cache(maxsize=None)
+def _crosscorr_ref(shape, use_diff):
+    """(oracle rows, S, A, the bound on mean and std per row) of a shape's trajectories.  Never modified."""
     from oracle import summarize as osum
-    n = shape[0]
     states, actions = _traj(*shape)
-    ref = osum.cross_correlation(states, actions, use_diff)
     sf, af = osum.crosscorr_features(states, actions, use_diff)
-    s_dim, a_dim = sf.shape[1], af.shape[1]
-    got = B.cross_correlation(*_gpu(states, actions), use_state_diff=use_diff, dtype=F64)
-    _check_rows(got, n, s_dim * a_dim + 2)
+    return (osum.cross_correlation(states, actions, use_diff), sf.shape[1], af.shape[1],
+            4 * (sf.shape[1] + 8) * U * sf.abs().max(dim=1).values)
+
+
+def _assert_crosscorr(got, shape, use_diff):
+    """the products bitwise, mean and std within the summation bound"""
+    ref, s_dim, a_dim, tol = _crosscorr_ref(shape, use_diff)
     got = got.cpu()
+    assert tuple(got.shape) == tuple(ref.shape) == (shape[0], s_dim * a_dim + 2)
     assert torch.equal(got[:, :s_dim * a_dim], ref[:, :s_dim * a_dim])
-    tol = 4 * (s_dim + 8) * U * sf.abs().max(dim=1).values
     for col, what in ((-2, 'mean'), (-1, 'std')):
         ratio = ((got[:, col] - ref[:, col]).abs() / tol).max().item()
         print('crosscorr %s diff=%d %s: worst |err| / bound = %.3g' % (shape, use_diff, what, ratio))
         assert ratio <= 1.0, (what, ratio)
+
+
+@pytest.mark.parametrize('use_diff', [False, True])
+@pytest.mark.parametrize('shape', CC_SHAPES)
+def test_cross_correlation_against_the_oracle(B, shape, use_diff):
+    states, actions = _traj(*shape)
+    _, s_dim, a_dim, _ = _crosscorr_ref(shape, use_diff)
+    got = B.cross_correlation(*_gpu(states, actions), use_state_diff=use_diff, dtype=F64)
+    _check_rows(got, shape[0], s_dim * a_dim + 2)
+    _assert_crosscorr(got, shape, use_diff)
     # the named summarizers are the same call
     named = (B.summary_corrdiff if use_diff else B.summary_corr)(*_gpu(states, actions), dtype=F64)
-    assert torch.equal(named.cpu(), got)
+    assert torch.equal(named, got)
+
+
+# The branches of crosscorr_kernel<double> (csrc/summaries.h), each at the smallest shape that reaches it, through
+# both views of _views.  Rows of at most 2048 products (kSmallRow) take the lean variant: features fetched in place,
+# every product checked, element stores into either view.  Longer rows take the fp32 body: into 16-byte aligned rows
+# of even pitch it stores 16-byte words (a word of action features per thread where A is even and A <= 512, else the
+# generic word loop, with an element tail where S A is odd), into the offset view elements.  (N, T, Ta, sd, ad):
+CC_BRANCHES = {
+    'lean': (3, 4, 4, 3, 1),                  # S = 8, A = 4
+    'lean_even': (2, 3, 3, 3, 1),             # S A = 18
+    'lean_odd': (2, 5, 5, 2, 1),              # S A = 25
+    'lean_edge': (2, 8, 8, 33, 1),            # S A = 256 * 8 = 2048: the last lean row
+    'lean_above_cap': ('cap+5', 3, 3, 2, 1),  # five workgroups take a second trajectory
+    'prefetch_word': (2, 8, 8, 34, 1),        # S A = 264 * 8 = 2112: features prefetched in registers; a word per thread
+    'inplace_tail': (2, 3, 3, 258, 1),        # sd - 1 = 257 > 256: fetched in place; S A = 771 * 3 is odd: tail
+    'generic': (2, 5, 5, 85, 1),              # A = 5 is odd, S A = 420 * 5 even: the generic loop, no tail
+    'generic_tail': (2, 5, 5, 84, 1),         # S A = 415 * 5: one element behind the last full word
+    'wide_a': (2, 10, 10, 2, 52),             # A = 520 is even and above 512: the generic loop
+    'above_cap': ('cap+5', 8, 8, 34, 1),      # five workgroups store a second trajectory, fetched by their prefetch
+}
+
+
+@pytest.mark.parametrize('use_diff', [False, True])
+@pytest.mark.parametrize('name', list(CC_BRANCHES))
+def test_cross_correlation_branches_of_the_shared_kernel(B, name, use_diff):
+    shape = CC_BRANCHES[name]
+    if shape[0] == 'cap+5':
+        shape = (_grid_cap() + 5,) + shape[1:]
+    s, a = _gpu(*_traj(*shape))
+    _, s_dim, a_dim, _ = _crosscorr_ref(shape, use_diff)
+    for buf, view in _views(shape[0], s_dim * a_dim + 2):
+        got = B.cross_correlation(s, a, use_state_diff=use_diff, out=view, dtype=F64)
+        assert got.data_ptr() == view.data_ptr()
+        _assert_crosscorr(view, shape, use_diff)
+        _assert_untouched(buf, view)
 
 
 def test_cross_correlation_of_equal_state_features_has_std_zero(B):
@@ -189,6 +256,82 @@ def test_signature_depth_3_refuses_what_does_not_fit(B):
         B.summary_signatory(*_gpu(states, actions), dtype=F64)
     with pytest.raises(NotImplementedError, match='path dim'):
         B.summary_signatory(*_gpu(*_traj(2, 4, 4, 19, 3)), depth=3, dtype=F64)
+
+
+@functools.lru_cache(maxsize=None)
+def _signature_case_refs(n, length, sd, ad, depth):
+    """(signature_brute rows, their bound) of a case's trajectories.  Never modified."""
+    from oracle import summarize as osum
+    ref, sabs = _signature_refs(osum.signature_paths(*_traj(n, length, length, sd, ad)), depth)
+    bound = (length + 6) * 2.0 ** -52 * sabs
+    assert (bound > 0).all()
+    return ref, bound
+
+
+# The branches of signature3_kernel<double, DMAX> and signature12_kernel<double> (csrc/summaries.h), each through
+# both views of _views (aligned rows: head, 16-byte words on whole lines, tail; the offset view: elements).
+# (N, L, sd, ad, depth): d = 3, DMAX 8, odd d | d = 9, DMAX 16 | d = 17, DMAX 24 | d = 22, the widest, even d --
+# all four with L sd <= threads: the next trajectory prefetched | L sd = 160 > 64 threads: fetched in place, even d |
+# depth 2 and depth 1 at d = 23 and d = 111
+SIG_BRANCHES = [(3, 5, 1, 1, 3), (2, 3, 6, 2, 3), (2, 3, 13, 3, 3), (2, 3, 18, 3, 3), (2, 40, 4, 1, 3),
+                (2, 4, 19, 3, 2), (2, 4, 19, 3, 1), (2, 3, 100, 10, 2), (2, 3, 100, 10, 1)]
+
+
+@pytest.mark.parametrize('case', SIG_BRANCHES, ids=[str(c) for c in SIG_BRANCHES])
+def test_signature_branches_of_the_shared_kernels(B, case):
+    n, length, sd, ad, depth = case
+    d = 1 + sd + ad
+    s, a = _gpu(*_traj(n, length, length, sd, ad))
+    ref, bound = _signature_case_refs(*case)
+    for buf, view in _views(n, sum(d ** k for k in range(1, depth + 1))):
+        got = B.summary_signatory(s, a, depth=depth, out=view, dtype=F64)
+        assert got.data_ptr() == view.data_ptr()
+        ratio = (np.abs(view.cpu().numpy() - ref) / bound).max()
+        print('signature %s pitch %d: worst |err| / bound = %.3g' % (case, view.stride(0), ratio))
+        assert ratio <= 1.0, ratio
+        _assert_untouched(buf, view)
+
+
+def _signature_chen_longdouble(path):
+    """Levels 1..3 of one path [L, d] by Chen's identity per segment in numpy's longdouble (x87: 2^-64 against the
+    2^-53 of the values under test), for the one path too long for signature_brute's O(L^3) ordered triples.  The
+    same definition (oracle/signature.py: S <- S (x) exp(delta)); its own rounding is 2^-11 of the bound."""
+    assert np.finfo(np.longdouble).eps <= 2.0 ** -63
+    x = np.asarray(path, dtype=np.longdouble)
+    d = x.shape[1]
+    s1, s2, s3 = np.zeros(d, np.longdouble), np.zeros((d, d), np.longdouble), np.zeros((d, d, d), np.longdouble)
+    for dl in x[1:] - x[:-1]:
+        e2 = np.multiply.outer(dl, dl) / 2
+        e3 = np.multiply.outer(e2, dl) / 3
+        s3 = s3 + np.multiply.outer(s2, dl) + np.multiply.outer(s1, e2) + e3
+        s2 = s2 + np.multiply.outer(s1, dl) + e2
+        s1 = s1 + dl
+    return np.concatenate([s1, s2.reshape(-1), s3.reshape(-1)])
+
+
+def test_signature_depth_3_at_the_edge_of_a_workgroups_lds(B):
+    """d = 22: path, increments and stage are 8 (44 L - 22 + 10648) bytes (profiles/f64_NOTES.md): 163 504 at
+    L = 223, inside the 163 840 of a workgroup, and 163 856 at L = 224, refused with the message it always had.
+    A forced depth 3 at d = 23 is refused as well."""
+    from oracle import summarize as osum
+    states, actions = _traj(1, 223, 223, 18, 3)
+    got = B.summary_signatory(*_gpu(states, actions), dtype=F64)
+    _check_rows(got, 1, 22 + 22 ** 2 + 22 ** 3)
+    x = osum.signature_paths(states, actions)[0].numpy()
+    steps = np.abs(x[1:] - x[:-1])
+    xabs = np.concatenate([np.zeros_like(x[:1]), np.cumsum(steps, axis=0)], axis=0)
+    ref, sabs = _signature_chen_longdouble(x), _signature_chen_longdouble(xabs)
+    bound = (223 + 6) * 2.0 ** -52 * sabs
+    assert (bound > 0).all()
+    ratio = float((np.abs(got.cpu().numpy()[0].astype(np.longdouble) - ref) / bound).max())
+    print('signature d = 22, L = 223: worst |err| / bound = %.3g' % ratio)
+    assert ratio <= 1.0, ratio
+    with pytest.raises(NotImplementedError) as refused:
+        B.summary_signatory(*_gpu(*_traj(1, 224, 224, 18, 3)), dtype=F64)
+    assert str(refused.value) == 'signature_f64: 163856 B of LDS needed (163840 in a workgroup)'
+    with pytest.raises(NotImplementedError) as refused:
+        B.summary_signatory(*_gpu(*_traj(2, 4, 4, 19, 3)), depth=3, dtype=F64)
+    assert str(refused.value) == 'signature_f64: depth 3 needs path dim <= 22 (got 23)'
 
 
 # ------------------------------------------------------------------ 4. out=
