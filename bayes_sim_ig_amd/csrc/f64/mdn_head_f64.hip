@@ -1,12 +1,13 @@
 // Mixture-density head in double (include/bsig_f64.h): forward tuple, NLL and its backward --
 // the closed forms of SURVEY.md Appendix A.1-A.3, derived from mdnn.py:108-178.
 //
-// mdn_nll_f64_kernel<FULL>: one wavefront per row, lane k < K runs component k (forward
-// substitution with T_k = diag(sigma_k) + strict lower, back substitution for the gradients), the
-// logsumexp goes through the wavefront's LDS.  mdn_finish_f64_kernel: loss mean, the
-// non-detached jitter-mean term sum(u dL/dsigma), head bias column sums, engine state advance.
-// Every sum has a fixed order: two runs are bitwise equal.
+// mdn_nll_f64_kernel<FULL>: one wavefront per row, four rows per workgroup; lane k < K runs component k through the
+// phases of the component row (../mdn_row.h, the body the fp32 kernels run), the row read from global memory, the
+// gradients written to its d_out row, the logsumexp through the wavefront's LDS.  mdn_finish_f64_kernel: loss mean,
+// the non-detached jitter-mean term sum(u dL/dsigma), head bias column sums, engine state advance.  The forward()
+// tuple is mdn::mdn_outputs_kernel<double>.  Every sum has a fixed order: two runs are bitwise equal.
 #include "f64.h"
+#include "../mdn_row.h"
 
 #include <algorithm>
 #include <cmath>
@@ -16,7 +17,6 @@ namespace f64 {
 
 constexpr int kRowsPerBlock = 4;   // wavefronts per workgroup
 constexpr int kSigMax = 64;        // partial sums of exp(pre_diag)
-constexpr double kHalfLog2Pi = 0.91893853320467274178;
 
 struct HeadArgs {
   const double* seg_w; int64_t ld_w;
@@ -47,15 +47,6 @@ __device__ inline double block_sum_f64(double v, double* scratch) {
   for (int i = 0; i < nw; ++i) t += scratch[i];
   return t;
 }
-
-// the jitter draw of element e = (row * D + d) * K + k: the uniform of the fp32
-// thread-per-component kernels (24 bits of Philox word 0), widened
-__device__ inline double jitter_u(const double* noise, uint64_t seed, uint64_t sid, int64_t e) {
-  if (noise) return noise[e];
-  return (double)u01(philox4x32_10(seed, sid, (uint64_t)e).v[0]);
-}
-
-__device__ inline double clampd(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }
 
 // partial sums of exp(pre_diag) over [batch, DK] for the jitter scale EPS_NOISE * mean(exp(pre))
 __global__ __launch_bounds__(256) void sigma0_sum_f64_kernel(const double* __restrict__ pre, int64_t ld,
@@ -89,120 +80,40 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void mdn_nll_f64_kernel(HeadArg
     for (int i = 0; i < a.n_sig; ++i) s += a.sig_partials[i];
     eps = a.eps_noise * (s / ((double)a.batch * (double)DK));   // mdnn.py:115, not detached
   }
-  const double* Tw = a.seg_w + (int64_t)row * a.ld_w;
-  const double* Tmu = a.seg_mu + (int64_t)row * a.ld_mu;
-  const double* Tsg = a.seg_sg + (int64_t)row * a.ld_sg;
-  const double* Tlo = FULL ? a.seg_lo + (int64_t)row * a.ld_lo : nullptr;
-  const double* yv = a.y + (int64_t)(a.y_rows ? a.y_rows[row] : row) * a.ldy;
-  const int64_t e0 = (int64_t)row * DK + k;   // jitter element of (row, d = 0, k)
+  // the component row on the four pitched segments of the row; gradients go to the row of d_out
+  const bool bwd = a.d_out != nullptr;
+  double* dT = bwd ? a.d_out + (int64_t)row * a.ld_dout : nullptr;
+  const mdn::RowHyper<double> h{D, K, a.from_tuple != 0, a.min_w, a.ll_limit, a.inv_norm, a.noise, a.seed, a.stream_id};
+  mdn::RowView<double> view{};
+  view.lg = a.seg_w + (int64_t)row * a.ld_w;
+  view.mu = a.seg_mu + (int64_t)row * a.ld_mu + k;
+  view.sg = a.seg_sg + (int64_t)row * a.ld_sg + k;
+  view.lo = FULL ? a.seg_lo + (int64_t)row * a.ld_lo + k : nullptr;
+  if (bwd) { view.d_mu = dT + K + k; view.d_sg = view.d_mu + DK; view.d_lo = view.d_sg + DK; }
+  view.es = K;
+  view.y = a.y + (int64_t)(a.y_rows ? a.y_rows[row] : row) * a.ldy;
+  view.v = v_; view.q = q_; view.vs = K;
+  view.je = (int64_t)row * DK + k;
 
-  double logp = 0.0, w_k = 0.0, s_k = 0.0, csum = 1.0, mx = 0.0, den = 1.0;
-  bool bad = false;
+  mdn::CompState<double> c{};
   if (comp) {
-    if (a.from_tuple) {
-      w_k = Tw[k];
-    } else {   // softmax -> clamp -> renormalise, mdnn.py:109-111
-      mx = Tw[0];
-      for (int j = 1; j < K; ++j) mx = fmax(mx, Tw[j]);
-      den = 0.0;
-      for (int j = 0; j < K; ++j) den += exp(Tw[j] - mx);
-      csum = 0.0;
-      for (int j = 0; j < K; ++j) csum += clampd(exp(Tw[j] - mx) / den, a.min_w, 1.0);
-      s_k = exp(Tw[k] - mx) / den;
-      w_k = clampd(s_k, a.min_w, 1.0) / csum;
-    }
-    bad |= !isfinite(w_k);
-    double quad = 0.0, logdet = 0.0;
-    for (int d = 0; d < D; ++d) {
-      const double mu = Tmu[d * K + k];
-      double sg = a.from_tuple ? Tsg[d * K + k] : exp(Tsg[d * K + k]);
-      if (eps != 0.0) sg += jitter_u(a.noise, a.seed, a.stream_id, e0 + (int64_t)d * K) * eps;
-      bad |= !(isfinite(mu) && isfinite(sg));
-      double res = yv[d] - mu;
-      if (FULL)
-        for (int j = 0; j < d; ++j) {
-          const double lij = Tlo[(d * (d - 1) / 2 + j) * K + k];
-          bad |= !isfinite(lij);
-          res -= lij * v_[j * K];
-        }
-      const double vi = res / sg;
-      v_[d * K] = vi;
-      quad += vi * vi;
-      logdet += log(sg);
-    }
-    logp = -0.5 * quad - logdet - (double)D * kHalfLog2Pi;
-    const double lp = clampd(logp, -a.ll_limit, a.ll_limit);   // mdnn.py:159
-    const double wc = clampd(w_k, a.min_w, 1.0);               // mdnn.py:160
-    const double rv = lp + log(wc);
-    bad |= !(isfinite(logp) && isfinite(rv));
-    rk[k] = rv;
+    mdn::comp_weights(view, h, k, c);
+    rk[k] = mdn::comp_elements<double, FULL, true>(view, h, eps, c);   // (a v plane for diagonal rows too)
   }
   // (rk[] crosses LANES of this wavefront only -- a row never spans wavefronts, and the early
   // return above is row-uniform -- and a wavefront's LDS operations issue in order: a scheduling fence is
   // all that is needed, no __syncthreads().  A row spread over several wavefronts would break this.)
   __builtin_amdgcn_wave_barrier();
-  double m2 = rk[0];
-  for (int j = 1; j < K; ++j) m2 = fmax(m2, rk[j]);
-  double se = 0.0;
-  for (int j = 0; j < K; ++j) se += exp(rk[j] - m2);
-  const double lse = m2 + log(se);
+  const double lse = mdn::row_lse(rk, K);
 
   double uds = 0.0;
-  if (a.d_out != nullptr && comp) {
-    double* dT = a.d_out + (int64_t)row * a.ld_dout;
-    const double sc = -exp(rk[k] - lse) * a.inv_norm;
-    const double g_lp = (logp >= -a.ll_limit && logp <= a.ll_limit) ? sc : 0.0;
-    if (FULL)
-      for (int i = D - 1; i >= 0; --i) {   // q = T^{-T} v by back substitution
-        double acc = v_[i * K];
-        for (int j = i + 1; j < D; ++j) acc -= Tlo[(j * (j - 1) / 2 + i) * K + k] * q_[j * K];
-        double sg = exp(Tsg[i * K + k]);
-        if (eps != 0.0) sg += jitter_u(a.noise, a.seed, a.stream_id, e0 + (int64_t)i * K) * eps;
-        q_[i * K] = acc / sg;
-      }
-    for (int d = 0; d < D; ++d) {
-      const double sg0 = exp(Tsg[d * K + k]);
-      double sg = sg0, u = 0.0;
-      if (eps != 0.0) { u = jitter_u(a.noise, a.seed, a.stream_id, e0 + (int64_t)d * K); sg += u * eps; }
-      const double vi = v_[d * K];
-      const double qi = FULL ? q_[d * K] : vi / sg;
-      const double dsg = FULL ? g_lp * (qi * vi - 1.0 / sg) : g_lp * ((vi * vi - 1.0) / sg);
-      if (FULL)
-        for (int j = 0; j < d; ++j) dT[K + 2 * DK + (d * (d - 1) / 2 + j) * K + k] = g_lp * qi * v_[j * K];
-      uds += u * dsg;
-      dT[K + d * K + k] = g_lp * qi;
-      dT[K + DK + d * K + k] = dsg * sg0;   // (the jitter-mean term is added by the finishing kernel)
-    }
-    // mixture-weight path: second clamp, renormalisation, first clamp, softmax
-    double s1 = 0.0;
-    for (int j = 0; j < K; ++j) {
-      const double sj = exp(Tw[j] - mx) / den;
-      const double wj = clampd(sj, a.min_w, 1.0) / csum;
-      const double wcj = clampd(wj, a.min_w, 1.0);
-      const double scj = -exp(rk[j] - lse) * a.inv_norm;
-      const double gwj = (wj >= a.min_w && wj <= 1.0) ? scj / wcj : 0.0;
-      s1 += gwj * wj;
-    }
-    double s2 = 0.0, gs_k = 0.0;
-    for (int j = 0; j < K; ++j) {
-      const double sj = exp(Tw[j] - mx) / den;
-      const double wj = clampd(sj, a.min_w, 1.0) / csum;
-      const double wcj = clampd(wj, a.min_w, 1.0);
-      const double scj = -exp(rk[j] - lse) * a.inv_norm;
-      const double gwj = (wj >= a.min_w && wj <= 1.0) ? scj / wcj : 0.0;
-      const double gcj = (gwj - s1) / csum;
-      const double gsj = (sj >= a.min_w && sj <= 1.0) ? gcj : 0.0;
-      s2 += gsj * sj;
-      if (j == k) gs_k = gsj;
-    }
-    dT[k] = s_k * (gs_k - s2);
-  }
+  if (bwd && comp) dT[k] = mdn::comp_backward<double, FULL, true>(view, h, k, eps, c, rk, lse, uds);
   uds = wave_sum_f64(comp ? uds : 0.0);
   if (lane == 0) {
     a.row_lse[row] = lse;
     if (a.row_uds) a.row_uds[row] = uds;
   }
-  if (__any(bad) && lane == 0 && a.nonfinite) atomicOr(a.nonfinite, kFlagNonfinite);
+  if (__any(c.bad) && lane == 0 && a.nonfinite) atomicOr(a.nonfinite, kFlagNonfinite);
 }
 
 // Fit-engine state advance (single writer; every reader of these words runs in a later kernel).
@@ -256,52 +167,6 @@ __global__ __launch_bounds__(256) void mdn_finish_f64_kernel(
   part[rl][cl] = acc;
   __syncthreads();
   if (rl == 0 && col < nh) colsum[col] = (part[0][cl] + part[1][cl]) + (part[2][cl] + part[3][cl]);
-}
-
-// forward() tuple, mdnn.py:109-119
-__global__ __launch_bounds__(256) void mdn_outputs_f64_kernel(
-    const double* __restrict__ o, int64_t ld, int batch, int D, int K, int Ls,
-    const double* __restrict__ noise, uint64_t seed, uint64_t stream_id, double eps_noise, double min_w,
-    const double* __restrict__ sig_partials, int n_sig, double* __restrict__ weights,
-    double* __restrict__ mu, double* __restrict__ l_d, double* __restrict__ lower,
-    int32_t* __restrict__ nonfinite) {
-  const int DK = D * K, Nh = K + 2 * DK + Ls * K;
-  double eps = 0.0;
-  if (eps_noise != 0.0) {
-    double s = 0.0;
-    for (int i = 0; i < n_sig; ++i) s += sig_partials[i];
-    eps = eps_noise * (s / ((double)batch * (double)DK));
-  }
-  bool bad = false;
-  for (int row = blockIdx.x; row < batch; row += gridDim.x) {
-    const double* t = o + (int64_t)row * ld;
-    for (int j = threadIdx.x; j < Nh; j += blockDim.x) {
-      double v;
-      if (j < K) {
-        double mx = t[0];
-        for (int q = 1; q < K; ++q) mx = fmax(mx, t[q]);
-        double den = 0.0;
-        for (int q = 0; q < K; ++q) den += exp(t[q] - mx);
-        double csum = 0.0;
-        for (int q = 0; q < K; ++q) csum += clampd(exp(t[q] - mx) / den, min_w, 1.0);
-        v = clampd(exp(t[j] - mx) / den, min_w, 1.0) / csum;
-        weights[(int64_t)row * K + j] = v;
-      } else if (j < K + DK) {
-        v = t[j];
-        mu[(int64_t)row * DK + (j - K)] = v;
-      } else if (j < K + 2 * DK) {
-        const int e = j - K - DK;
-        v = exp(t[j]);
-        if (eps != 0.0) v += jitter_u(noise, seed, stream_id, (int64_t)row * DK + e) * eps;
-        l_d[(int64_t)row * DK + e] = v;
-      } else {
-        v = t[j];
-        lower[(int64_t)row * Ls * K + (j - K - 2 * DK)] = v;
-      }
-      bad |= !isfinite(v);
-    }
-  }
-  if (bad && nonfinite) atomicOr(nonfinite, kFlagNonfinite);
 }
 
 // ---------------------------------------------------------------- host side
@@ -414,7 +279,7 @@ extern "C" int bsig_mdn_head_outputs_f64(const bsig_head_dims* dims, const bsig_
     n_sig = f64::sigma0_sum(head_out + g.K + g.D * g.K, ld, batch, g.D * g.K, sig_partials, st);
     if (n_sig < 0) return n_sig;
   }
-  hipLaunchKernelGGL(f64::mdn_outputs_f64_kernel, dim3((int)std::min<int64_t>(batch, 2048)), dim3(256), 0, st,
+  hipLaunchKernelGGL(mdn::mdn_outputs_kernel<double>, dim3((int)std::min<int64_t>(batch, 2048)), dim3(256), 0, st,
                      head_out, ld, (int)batch, g.D, g.K, g.Ls, noise, seed, stream_id, hy.eps_noise,
                      hy.min_weight, sig_partials, n_sig, weights, mu, l_d, lower, nonfinite);
   BSIG_CHECK_LAUNCH("mdn_outputs_f64");

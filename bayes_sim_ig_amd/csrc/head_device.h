@@ -1,8 +1,11 @@
-// Device-side pieces of the mixture-density head shared by mdn_head.hip and the
-// persistent update kernel (fit_persistent.hip).
+// Device-side pieces of the mixture-density head shared by mdn_head.hip and the persistent update kernels:
+// the wavefront-per-row diagonal rows (diag_row_body, diag_row_fast_core: DPP reductions, their own summation
+// orders), the full-covariance row of the persistent owners (full_row: the component row of mdn_row.h, as
+// in mdn_nll_kernel), and the cross-workgroup flags and granules of one launch.
 #pragma once
 #include "head.h"
 #include "fit_protocol.h"
+#include "mdn_row.h"
 
 namespace bsig {
 
@@ -100,138 +103,6 @@ __device__ __forceinline__ void diag_row_noise(const HeadArgs& a, int groups, in
   }
 }
 
-#ifdef BSIG_DIAG_ROW_V1
-template <typename EpsFn>
-__device__ __forceinline__ void diag_row(const HeadArgs& a, int row, bool active, int lane,
-                                         float* tile, const float* yv, float* rk, float* lpk,
-                                         float* dlg, EpsFn&& eps_fn, RowOut& out,
-                                         const float* eu_pre = nullptr) {
-  const int D = a.D, K = a.K;
-  const int DK = D * K;
-  const int groups = 64 / K;               // d-slots per sweep
-  const int TPR = groups * K;
-  const int k = lane % K, d0 = lane / K;
-  const bool elem = active && lane < TPR;
-  bool bad = false;
-  // per-element values kept for the backward half
-  float ez[kElemsPerLane], esg[kElemsPerLane], eu[kElemsPerLane];
-  float (&esg0)[kElemsPerLane] = out.esg0;
-  float quad = 0.f, logdet = 0.f;
-  Philox4 ph{{0u, 0u, 0u, 0u}};
-  const bool jitter = !a.from_tuple && a.eps_noise != 0.f;
-  const bool draw = jitter && a.noise == nullptr;
-  const uint64_t rng_seed = a.dyn_rng ? a.dyn_rng[0] : a.seed;
-  const uint64_t rng_sid = a.dyn_rng ? a.dyn_rng[1] : a.stream_id;
-#pragma unroll
-  for (int q = 0; q < kElemsPerLane; ++q) {
-    const int d = d0 + q * groups;
-    ez[q] = 0.f; esg[q] = 1.f; esg0[q] = 1.f; eu[q] = 0.f;
-    if (eu_pre == nullptr && (q & 3) == 0 && draw && elem && d < D)
-      ph = philox4x32_10(rng_seed, rng_sid, ((uint64_t)row * 64 + lane) * 2 + (q >> 2));
-    if (elem && d < D && !a.from_tuple) {
-      esg0[q] = expf(tile[K + DK + d * K + k]);
-      if (jitter) eu[q] = eu_pre ? eu_pre[q] : (a.noise ? a.noise[((int64_t)row * D + d) * K + k] : u01(ph.v[q & 3]));
-    }
-  }
-  // mixture weights (mdnn.py:109-111): lane j < K owns component j, the sums over
-  // the components are wavefront reductions
-  const bool comp = active && lane < K;
-  float s_own = 0.f, w_own = 0.f, csum = 1.f;
-  if (active && !a.from_tuple) {
-    float mx = tile[0];
-    for (int j = 1; j < K; ++j) mx = fmaxf(mx, tile[j]);
-    const float e_own = comp ? expf(tile[lane] - mx) : 0.f;
-    s_own = e_own / wave_sum_dpp(e_own);
-    const float c_own = comp ? fminf(fmaxf(s_own, a.min_w), 1.0f) : 0.f;
-    csum = wave_sum_dpp(c_own);
-    w_own = c_own / csum;
-  } else if (comp) {
-    w_own = tile[lane];
-  }
-  const float eps = eps_fn();
-#pragma unroll
-  for (int q = 0; q < kElemsPerLane; ++q) {
-    const int d = d0 + q * groups;
-    if (elem && d < D) {
-      const float mu = tile[K + d * K + k];
-      float sg;
-      if (a.from_tuple) sg = tile[K + DK + d * K + k];
-      else {
-        sg = esg0[q];
-        if (eps != 0.f) sg += eu[q] * eps;
-        else eu[q] = 0.f;
-      }
-      bad |= !(isfinite(mu) && isfinite(sg));
-      const float z = (yv[d] - mu) / sg;
-      quad += z * z;
-      logdet += logf(sg);
-      ez[q] = z; esg[q] = sg;
-    }
-  }
-  // sum over the dimensions of each component: lanes k, k+K, k+2K, ...
-  for (int off = 32; off >= 1; off >>= 1) {
-    if (off < groups || off == 1) {
-      const float tq = __shfl_down(quad, off * K, 64);
-      const float tl = __shfl_down(logdet, off * K, 64);
-      if (d0 + off < groups && lane + off * K < 64) { quad += tq; logdet += tl; }
-    }
-  }
-  if (comp) {
-    const float logp = -0.5f * quad - logdet - (float)D * kHalfLog2Pi;
-    const float w = w_own;
-    const float lp = fminf(fmaxf(logp, -a.ll_limit), a.ll_limit);
-    const float rv = lp + logf(fminf(fmaxf(w, a.min_w), 1.0f));
-    bad |= !(isfinite(w) && isfinite(logp) && isfinite(rv));
-    rk[lane] = rv;
-    lpk[lane] = logp;
-  }
-  __builtin_amdgcn_wave_barrier();
-  float lse = 0.f;
-  if (active) {
-    float m2 = rk[0];
-    for (int j = 1; j < K; ++j) m2 = fmaxf(m2, rk[j]);
-    float se = 0.f;
-    for (int j = 0; j < K; ++j) se += expf(rk[j] - m2);
-    lse = m2 + logf(se);
-  }
-
-  const bool bwd = a.d_out != nullptr;
-  float uds = 0.f;
-  if (bwd && elem) {
-    const float sc = -expf(rk[k] - lse) * a.inv_norm;
-    const float lp0 = lpk[k];
-    const float g_lp = (lp0 >= -a.ll_limit && lp0 <= a.ll_limit) ? sc : 0.f;
-#pragma unroll
-    for (int q = 0; q < kElemsPerLane; ++q) {
-      const int d = d0 + q * groups;
-      if (d < D) {
-        const float dsg = g_lp * (ez[q] * ez[q] - 1.0f) / esg[q];
-        uds += eu[q] * dsg;
-        tile[K + d * K + k] = g_lp * ez[q] / esg[q];
-        tile[K + DK + d * K + k] = dsg * esg0[q];
-      }
-    }
-  }
-  if (bwd && active) {                      // mixture-weight path, lane = component
-    float gw = 0.f;
-    if (comp) {
-      const float sc = -expf(rk[lane] - lse) * a.inv_norm;
-      gw = (w_own >= a.min_w && w_own <= 1.0f) ? sc / fminf(fmaxf(w_own, a.min_w), 1.0f) : 0.f;
-    }
-    float dlogit = gw;
-    if (!a.from_tuple) {                    // through the renormalisation, the clamp, the softmax
-      const float s1 = wave_sum_dpp(gw * w_own);
-      const float gs = (comp && s_own >= a.min_w && s_own <= 1.0f) ? (gw - s1) / csum : 0.f;
-      const float s2 = wave_sum_dpp(gs * s_own);
-      dlogit = s_own * (gs - s2);
-    }
-    if (comp) dlg[lane] = dlogit;           // separate slot: the logits stay readable
-  }
-  __builtin_amdgcn_wave_barrier();
-  out.lse = lse; out.uds = uds; out.bad = bad;
-}
-
-#else
 // Wavefront maximum through the DPP row shifts / broadcasts (cf. wave_sum_dpp, common.h); every
 // lane gets the result.
 __device__ inline float wave_max_dpp(float v) {
@@ -531,7 +402,6 @@ __device__ __forceinline__ void diag_row_capped(const HeadArgs& a, int row, bool
   const RowGeom rg = row_geom(a.D, a.K, lane);
   diag_row_impl<NQCAP>(a, rg, row, active, lane, tile, yv, rk, lpk, dlg, e, out, nullptr);
 }
-#endif
 
 // ---- diagonal covariance: the FAST row of the persistent kernels' owners (round 6) -------------------
 // One row on TWO wavefronts (wavefront h in {0, 1} takes the sweeps h, h + 2, ...), lane = d-slot * KP + k
@@ -651,135 +521,49 @@ __device__ __forceinline__ void diag_row_fast_core(int K, int D, bool active, bo
 
 }
 
-// jitter draw of element (row, d, k) for the thread-per-component kernels (full covariance)
-__device__ inline float jitter_u(const HeadArgs& a, int row, int d, int k) {
-  const int64_t e = ((int64_t)row * a.D + d) * a.K + k;
-  if (a.noise) return a.noise[e];
-  const uint64_t seed = a.dyn_rng ? a.dyn_rng[0] : a.seed;
-  const uint64_t sid = a.dyn_rng ? a.dyn_rng[1] : a.stream_id;
-  return u01(philox4x32_10(seed, sid, (uint64_t)e).v[0]);
+// ---- thread-per-component rows: the component row of mdn_row.h on an LDS tile ------------------
+// the head's scalars and jitter source (a device-side {seed, stream} overrides the launch's)
+__device__ __forceinline__ mdn::RowHyper<float> row_hyper(const HeadArgs& a, bool tuple) {
+  return {a.D, a.K, tuple, a.min_w, a.ll_limit, a.inv_norm, a.noise,
+          a.dyn_rng ? a.dyn_rng[0] : a.seed, a.dyn_rng ? a.dyn_rng[1] : a.stream_id};
+}
+// component k of the row staged in T = [K logits | D*K mu | D*K pre | Ls*K lower]: gradients overwrite the row
+// in place; v / q (/ e0) are the scratch planes at stride vs
+__device__ __forceinline__ mdn::RowView<float> tile_view(const HeadArgs& a, float* T, const float* yv, int row, int k,
+                                                         float* v, float* q, int vs, float* e0) {
+  const int K = a.K, DK = a.D * K;
+  float *mu = T + K + k, *sg = mu + DK, *lo = sg + DK;
+  return {T, mu, sg, lo, mu, sg, lo, K, yv, v, q, vs, e0, (int64_t)row * DK + k};
 }
 
 // ---- full covariance, one wavefront per row (the persistent MDNN kernel's owners) ---------
-// Lane k < K runs component k: forward substitution with T_k = diag(sigma_k) + strict lower
-// (mdnn.py:152-158), back substitution for the gradients -- the same
-// operations in the same order as mdn_nll_kernel<true> (mdn_head.hip), which the per-phase
-// path runs with one thread per (row, component).  In: tile[Nh] raw head outputs, yv[D].  Out:
-// gradients in tile[K..Nh) and dlg[K] (without the jitter-scale term), the row's logsumexp,
-// the lane's sum(u * dL/dsigma); vq [3][D][K] scratch: v, q, and exp(pre) (left for the caller's
-// jitter-scale correction).  `eps_fn()` as in diag_row.
+// Lane k < K runs component k through the phases of mdn_row.h -- the body mdn_nll_kernel<true> (mdn_head.hip)
+// runs with one thread per (row, component).  In: tile[Nh] raw head outputs, yv[D].  Out: gradients in
+// tile[K..Nh) and dlg[K] (without the jitter-scale term), the row's logsumexp, the lane's
+// sum(u * dL/dsigma); vq [3][D][K] scratch: v, q, and exp(pre) (left for the caller's jitter-scale
+// correction).  `eps_fn()` as in diag_row.
 template <typename EpsFn>
 __device__ __forceinline__ void full_row(const HeadArgs& a, int row, bool active, int lane,
                                          float* T, const float* yv, float* rk, float* dlg,
                                          float* vq, EpsFn&& eps_fn, RowOut& out) {
-  const int D = a.D, K = a.K, DK = D * K;
+  const int K = a.K, DK = a.D * K;
   const int k = lane < K ? lane : 0;
   const bool comp = active && lane < K;
-  float* v_ = vq + k;              // v_[i * K]
-  float* q_ = vq + DK + k;         // q_[i * K]
-  float* s0 = vq + 2 * DK + k;     // exp(pre)[i * K]
-  float logp = 0.f, w_k = 0.f, s_k = 0.f, csum = 1.f, mx = 0.f, den = 1.f;
-  bool bad = false;
-  if (comp) {   // softmax -> clamp -> renormalise, mdnn.py:109-111
-    mx = T[0];
-    for (int j = 1; j < K; ++j) mx = fmaxf(mx, T[j]);
-    den = 0.f;
-    for (int j = 0; j < K; ++j) den += expf(T[j] - mx);
-    csum = 0.f;
-    for (int j = 0; j < K; ++j) csum += fminf(fmaxf(expf(T[j] - mx) / den, a.min_w), 1.0f);
-    s_k = expf(T[k] - mx) / den;
-    w_k = fminf(fmaxf(s_k, a.min_w), 1.0f) / csum;
-    bad |= !isfinite(w_k);
-  }
+  const bool bwd = a.d_out != nullptr;
+  const mdn::RowHyper<float> h = row_hyper(a, false);
+  const mdn::RowView<float> view = tile_view(a, T, yv, row, k, vq + k, vq + DK + k, K, vq + 2 * DK + k);
+  mdn::CompState<float> c{};
+  if (comp) mdn::comp_weights(view, h, k, c);
   const float eps = eps_fn();
-  if (comp) {
-    float quad = 0.f, logdet = 0.f;
-    for (int d = 0; d < D; ++d) {
-      const float mu = T[K + d * K + k];
-      const float sg0 = expf(T[K + DK + d * K + k]);
-      s0[d * K] = sg0;
-      float sg = sg0;
-      if (eps != 0.f) sg += jitter_u(a, row, d, k) * eps;
-      bad |= !(isfinite(mu) && isfinite(sg));
-      float res = yv[d] - mu;
-      const int base = K + 2 * DK + (d * (d - 1) / 2) * K + k;
-      for (int j = 0; j < d; ++j) {
-        const float lij = T[base + j * K];
-        bad |= !isfinite(lij);
-        res -= lij * v_[j * K];
-      }
-      const float vi = res / sg;
-      v_[d * K] = vi;
-      quad += vi * vi;
-      logdet += logf(sg);
-    }
-    logp = -0.5f * quad - logdet - (float)D * kHalfLog2Pi;
-    const float lp = fminf(fmaxf(logp, -a.ll_limit), a.ll_limit);   // mdnn.py:159
-    const float wc = fminf(fmaxf(w_k, a.min_w), 1.0f);              // mdnn.py:160
-    const float rv = lp + logf(wc);
-    bad |= !(isfinite(logp) && isfinite(rv));
-    rk[k] = rv;
-  }
+  if (comp) rk[k] = mdn::comp_elements<float, true, true, true>(view, h, eps, c);
   __builtin_amdgcn_wave_barrier();
-  float lse = 0.f;
-  if (active) {
-    float m2 = rk[0];
-    for (int j = 1; j < K; ++j) m2 = fmaxf(m2, rk[j]);
-    float se = 0.f;
-    for (int j = 0; j < K; ++j) se += expf(rk[j] - m2);
-    lse = m2 + logf(se);
-  }
+  const float lse = active ? mdn::row_lse(rk, K) : 0.f;
   float uds = 0.f, dlogit = 0.f;
-  if (a.d_out != nullptr && comp) {
-    const float sc = -expf(rk[k] - lse) * a.inv_norm;
-    const float g_lp = (logp >= -a.ll_limit && logp <= a.ll_limit) ? sc : 0.f;
-    for (int i = D - 1; i >= 0; --i) {   // q = T^{-T} v by back substitution
-      float acc = v_[i * K];
-      for (int j = i + 1; j < D; ++j) acc -= T[K + 2 * DK + (j * (j - 1) / 2 + i) * K + k] * q_[j * K];
-      float sg = s0[i * K];
-      if (eps != 0.f) sg += jitter_u(a, row, i, k) * eps;
-      q_[i * K] = acc / sg;
-    }
-    for (int d = 0; d < D; ++d) {
-      const float sg0 = s0[d * K];
-      float sg = sg0, u = 0.f;
-      if (eps != 0.f) { u = jitter_u(a, row, d, k); sg += u * eps; }
-      const float qi = q_[d * K], vi = v_[d * K];
-      const float dsg = g_lp * (qi * vi - 1.0f / sg);
-      const int base = K + 2 * DK + (d * (d - 1) / 2) * K + k;
-      for (int j = 0; j < d; ++j) T[base + j * K] = g_lp * qi * v_[j * K];
-      uds += u * dsg;
-      T[K + d * K + k] = g_lp * qi;
-      T[K + DK + d * K + k] = dsg * sg0;
-    }
-    // mixture-weight path: second clamp, renormalisation, first clamp, softmax
-    float s1 = 0.f;
-    for (int j = 0; j < K; ++j) {
-      const float sj = expf(T[j] - mx) / den;
-      const float wj = fminf(fmaxf(sj, a.min_w), 1.0f) / csum;
-      const float wcj = fminf(fmaxf(wj, a.min_w), 1.0f);
-      const float scj = -expf(rk[j] - lse) * a.inv_norm;
-      const float gwj = (wj >= a.min_w && wj <= 1.0f) ? scj / wcj : 0.f;
-      s1 += gwj * wj;
-    }
-    float s2 = 0.f, gs_k = 0.f;
-    for (int j = 0; j < K; ++j) {
-      const float sj = expf(T[j] - mx) / den;
-      const float wj = fminf(fmaxf(sj, a.min_w), 1.0f) / csum;
-      const float wcj = fminf(fmaxf(wj, a.min_w), 1.0f);
-      const float scj = -expf(rk[j] - lse) * a.inv_norm;
-      const float gwj = (wj >= a.min_w && wj <= 1.0f) ? scj / wcj : 0.f;
-      const float gcj = (gwj - s1) / csum;
-      const float gsj = (sj >= a.min_w && sj <= 1.0f) ? gcj : 0.f;
-      s2 += gsj * sj;
-      if (j == k) gs_k = gsj;
-    }
-    dlogit = s_k * (gs_k - s2);
-  }
+  if (bwd && comp) dlogit = mdn::comp_backward<float, true, true, true>(view, h, k, eps, c, rk, lse, uds);
   __builtin_amdgcn_wave_barrier();
-  if (a.d_out != nullptr && comp) dlg[k] = dlogit;   // separate slot: the logits stay readable
+  if (bwd && comp) dlg[k] = dlogit;   // separate slot: the logits stay readable
   __builtin_amdgcn_wave_barrier();
-  out.lse = lse; out.uds = uds; out.bad = bad;
+  out.lse = lse; out.uds = uds; out.bad = c.bad;
 }
 
 // ---- cross-workgroup sums inside one launch -----------------------------------

@@ -11,8 +11,11 @@
 // d = l/K + q*(64/K); its per-element values stay in registers between the
 // forward and the backward half; the per-component sums meet in LDS for the
 // logsumexp; gradients overwrite the staged row in place and leave with
-// lane-contiguous stores.  Full covariance: a workgroup owns R rows, thread
-// (r, k) runs the forward / back substitution of component k from LDS.
+// lane-contiguous stores.  Full covariance (and diagonals too wide for a
+// wavefront): a workgroup owns R rows staged in LDS, thread (r, k) runs
+// component k through the phases of the component row (mdn_row.h: the one
+// body full_row and the double kernel run too); the forward() tuple is
+// mdn::mdn_outputs_kernel<float>.
 // Row sums (loss, jitter terms) are reduced with wavefront shuffles, one
 // partial per workgroup, summed in a fixed order by the finishing kernel
 // (bitwise reproducible, no atomics).
@@ -102,148 +105,24 @@ __global__ void mdn_nll_kernel(HeadArgs a) {
   const bool active = r < nrows;
   const int row = row0 + r;
   float* T = tile + r * Nh;
-  const float* yv = ybuf + r * D;
-  float* v_ = vq + tid;                       // v_[i*nt]
-  float* q_ = vq + (size_t)D * nt + tid;      // q_[i*nt]
-
-  float logp = 0.f, w_k = 0.f, s_k = 0.f, csum = 1.f, mx = 0.f, den = 1.f;
-  bool bad = false;
+  // the component row (mdn_row.h) on the tile, gradients in place; FULL: v / q at stride blockDim.x
+  const mdn::RowHyper<float> h = row_hyper(a, a.from_tuple != 0);
+  const mdn::RowView<float> view = tile_view(a, T, ybuf + r * D, row, k, FULL ? vq + tid : nullptr,
+                                             FULL ? vq + (size_t)D * nt + tid : nullptr, nt, nullptr);
+  mdn::CompState<float> c{};
   if (active) {
-    if (a.from_tuple) {
-      w_k = T[k];
-    } else {  // softmax -> clamp -> renormalise, mdnn.py:109-111
-      mx = T[0];
-      for (int j = 1; j < K; ++j) mx = fmaxf(mx, T[j]);
-      den = 0.f;
-      for (int j = 0; j < K; ++j) den += expf(T[j] - mx);
-      csum = 0.f;
-      for (int j = 0; j < K; ++j)
-        csum += fminf(fmaxf(expf(T[j] - mx) / den, a.min_w), 1.0f);
-      s_k = expf(T[k] - mx) / den;
-      w_k = fminf(fmaxf(s_k, a.min_w), 1.0f) / csum;
-    }
-    bad |= !isfinite(w_k);
-    float quad = 0.f, logdet = 0.f;
-    for (int d = 0; d < D; ++d) {
-      const float mu = T[K + d * K + k];
-      const float sraw = T[K + DK + d * K + k];
-      float sg;
-      if (a.from_tuple) sg = sraw;
-      else {
-        sg = expf(sraw);
-        if (eps != 0.f) sg += jitter_u(a, row, d, k) * eps;
-      }
-      bad |= !(isfinite(mu) && isfinite(sg));
-      float res = yv[d] - mu;
-      if (FULL) {  // forward substitution with T = diag(sigma) + strict lower
-        const int base = K + 2 * DK + (d * (d - 1) / 2) * K + k;
-        for (int j = 0; j < d; ++j) {
-          const float lij = T[base + j * K];
-          bad |= !isfinite(lij);
-          res -= lij * v_[j * nt];
-        }
-        const float vi = res / sg;
-        v_[d * nt] = vi;
-        quad += vi * vi;
-      } else {
-        const float z = res / sg;
-        quad += z * z;
-      }
-      logdet += logf(sg);
-    }
-    logp = -0.5f * quad - logdet - (float)D * kHalfLog2Pi;
-    const float lp = fminf(fmaxf(logp, -a.ll_limit), a.ll_limit);   // mdnn.py:159
-    const float wc = fminf(fmaxf(w_k, a.min_w), 1.0f);              // mdnn.py:160
-    const float rv = lp + logf(wc);
-    bad |= !(isfinite(logp) && isfinite(rv));
-    rk[r * K + k] = rv;
+    mdn::comp_weights(view, h, k, c);
+    rk[r * K + k] = mdn::comp_elements<float, FULL>(view, h, eps, c);
   }
   __syncthreads();
 
-  float lse = 0.f;
-  if (active) {
-    const float* rr = rk + r * K;
-    float m2 = rr[0];
-    for (int j = 1; j < K; ++j) m2 = fmaxf(m2, rr[j]);
-    float se = 0.f;
-    for (int j = 0; j < K; ++j) se += expf(rr[j] - m2);
-    lse = m2 + logf(se);
-  }
+  const float lse = active ? mdn::row_lse(rk + r * K, K) : 0.f;
   const float lse_sum = block_sum((active && k == 0) ? lse : 0.f, red);
   if (tid == 0) a.block_lse[blockIdx.x] = lse_sum;
 
   float uds = 0.f, dlogit = 0.f;
   const bool bwd = a.d_out != nullptr;
-  if (bwd && active) {
-    const float* rr = rk + r * K;
-    const float sc = -expf(rr[k] - lse) * a.inv_norm;
-    const float g_lp = (logp >= -a.ll_limit && logp <= a.ll_limit) ? sc : 0.f;
-    if (FULL) {  // q = T^{-T} v by back substitution
-      for (int i = D - 1; i >= 0; --i) {
-        float acc = v_[i * nt];
-        for (int j = i + 1; j < D; ++j)
-          acc -= T[K + 2 * DK + (j * (j - 1) / 2 + i) * K + k] * q_[j * nt];
-        const float sraw = T[K + DK + i * K + k];
-        float sg = a.from_tuple ? sraw : expf(sraw);
-        if (!a.from_tuple && eps != 0.f) sg += jitter_u(a, row, i, k) * eps;
-        q_[i * nt] = acc / sg;
-      }
-    }
-    for (int d = 0; d < D; ++d) {
-      const float mu = T[K + d * K + k];
-      const float sraw = T[K + DK + d * K + k];
-      float sg0 = 1.f, sg, u = 0.f;
-      if (a.from_tuple) sg = sraw;
-      else {
-        sg0 = expf(sraw);
-        sg = sg0;
-        if (eps != 0.f) { u = jitter_u(a, row, d, k); sg += u * eps; }
-      }
-      float dmu, dsg;
-      if (FULL) {
-        const float qi = q_[d * nt], vi = v_[d * nt];
-        dmu = g_lp * qi;
-        dsg = g_lp * (qi * vi - 1.0f / sg);
-        const int base = K + 2 * DK + (d * (d - 1) / 2) * K + k;
-        for (int j = 0; j < d; ++j) T[base + j * K] = g_lp * qi * v_[j * nt];
-      } else {
-        const float z = (yv[d] - mu) / sg;
-        dmu = g_lp * z / sg;
-        dsg = g_lp * (z * z - 1.0f) / sg;
-      }
-      uds += u * dsg;
-      T[K + d * K + k] = dmu;
-      T[K + DK + d * K + k] = dsg * sg0;
-    }
-    // mixture-weight path: second clamp, renormalisation, first clamp, softmax
-    if (a.from_tuple) {
-      const float wc = fminf(fmaxf(w_k, a.min_w), 1.0f);
-      dlogit = (w_k >= a.min_w && w_k <= 1.0f) ? sc / wc : 0.f;   // d/d weights
-    } else {
-      float s1 = 0.f;  // sum_j g_w[j] * w[j]
-      for (int j = 0; j < K; ++j) {
-        const float sj = expf(T[j] - mx) / den;
-        const float wj = fminf(fmaxf(sj, a.min_w), 1.0f) / csum;
-        const float wcj = fminf(fmaxf(wj, a.min_w), 1.0f);
-        const float scj = -expf(rr[j] - lse) * a.inv_norm;
-        const float gwj = (wj >= a.min_w && wj <= 1.0f) ? scj / wcj : 0.f;
-        s1 += gwj * wj;
-      }
-      float s2 = 0.f, gs_k = 0.f;  // sum_j g_s[j] * s[j]
-      for (int j = 0; j < K; ++j) {
-        const float sj = expf(T[j] - mx) / den;
-        const float wj = fminf(fmaxf(sj, a.min_w), 1.0f) / csum;
-        const float wcj = fminf(fmaxf(wj, a.min_w), 1.0f);
-        const float scj = -expf(rr[j] - lse) * a.inv_norm;
-        const float gwj = (wj >= a.min_w && wj <= 1.0f) ? scj / wcj : 0.f;
-        const float gcj = (gwj - s1) / csum;
-        const float gsj = (sj >= a.min_w && sj <= 1.0f) ? gcj : 0.f;
-        s2 += gsj * sj;
-        if (j == k) gs_k = gsj;
-      }
-      dlogit = s_k * (gs_k - s2);
-    }
-  }
+  if (bwd && active) dlogit = mdn::comp_backward<float, FULL>(view, h, k, eps, c, rk + r * K, lse, uds);
   const float uds_sum = block_sum(uds, red);  // also orders logits reads before writes
   if (tid == 0 && a.block_uds) a.block_uds[blockIdx.x] = uds_sum;
   if (bwd) {
@@ -255,7 +134,7 @@ __global__ void mdn_nll_kernel(HeadArgs a) {
       for (int j = tid; j < Nh; j += nt) o[j] = t[j];
     }
   }
-  if (bad && a.nonfinite) atomicOr(a.nonfinite, kFlagNonfinite);
+  if (c.bad && a.nonfinite) atomicOr(a.nonfinite, kFlagNonfinite);
 }
 
 template <int WPB, int NQCAP = kElemsPerLane>
@@ -427,58 +306,6 @@ __global__ __launch_bounds__(64 * kFinishLanes) void mdn_finish_kernel(
     for (int q = 0; q < kFinishLanes; ++q) t += part[q][cl];
     colsum[(int64_t)blockIdx.y * nh + col] = t;
   }
-}
-
-// forward() tuple, mdnn.py:109-119
-__global__ __launch_bounds__(256) void mdn_outputs_kernel(
-    const float* __restrict__ o, int64_t ld, int batch, int D, int K, int Ls,
-    const float* __restrict__ noise, uint64_t seed, uint64_t stream_id, float eps_noise,
-    float min_w, const float* __restrict__ sig_partials, int n_sig, float* __restrict__ weights,
-    float* __restrict__ mu, float* __restrict__ l_d, float* __restrict__ lower,
-    int32_t* __restrict__ nonfinite) {
-  __shared__ float red[8];
-  const int DK = D * K, Nh = K + 2 * DK + Ls * K;
-  float eps = 0.f;
-  if (eps_noise != 0.f) {
-    float s = 0.f;
-    for (int i = threadIdx.x; i < n_sig; i += blockDim.x) s += sig_partials[i];
-    s = block_sum(s, red);
-    eps = eps_noise * (s / ((float)batch * (float)DK));
-  }
-  bool bad = false;
-  for (int row = blockIdx.x; row < batch; row += gridDim.x) {
-    const float* t = o + (int64_t)row * ld;
-    for (int j = threadIdx.x; j < Nh; j += blockDim.x) {
-      float v;
-      if (j < K) {
-        float mx = t[0];
-        for (int q = 1; q < K; ++q) mx = fmaxf(mx, t[q]);
-        float den = 0.f;
-        for (int q = 0; q < K; ++q) den += expf(t[q] - mx);
-        float csum = 0.f;
-        for (int q = 0; q < K; ++q) csum += fminf(fmaxf(expf(t[q] - mx) / den, min_w), 1.f);
-        v = fminf(fmaxf(expf(t[j] - mx) / den, min_w), 1.f) / csum;
-        weights[(int64_t)row * K + j] = v;
-      } else if (j < K + DK) {
-        v = t[j];
-        mu[(int64_t)row * DK + (j - K)] = v;
-      } else if (j < K + 2 * DK) {
-        const int e = j - K - DK;
-        v = expf(t[j]);
-        if (eps != 0.f) {
-          const int64_t ne = (int64_t)row * DK + e;  // [B, D, K] flat == d*K+k
-          const float u = noise ? noise[ne] : u01(philox4x32_10(seed, stream_id, (uint64_t)ne).v[0]);
-          v += u * eps;
-        }
-        l_d[(int64_t)row * DK + e] = v;
-      } else {
-        v = t[j];
-        lower[(int64_t)row * Ls * K + (j - K - 2 * DK)] = v;
-      }
-      bad |= !isfinite(v);
-    }
-  }
-  if (bad && nonfinite) atomicOr(nonfinite, kFlagNonfinite);
 }
 
 // ---------------------------------------------------------------- host side
@@ -682,7 +509,7 @@ extern "C" int bsig_mdn_head_outputs(const bsig_head_dims* dims, const float* he
                        head_out + K + D * K, ld, (int)batch, D * K, sig_partials);
     BSIG_CHECK_LAUNCH("sigma0_sum");
   }
-  hipLaunchKernelGGL(mdn_outputs_kernel, dim3((int)std::min<int64_t>(batch, 2048)), dim3(256),
+  hipLaunchKernelGGL(mdn::mdn_outputs_kernel<float>, dim3((int)std::min<int64_t>(batch, 2048)), dim3(256),
                      0, st, head_out, ld, (int)batch, D, K, Ls, noise, seed, stream_id,
                      dims->eps_noise, dims->min_weight, sig_partials, n_sig, weights, mu, l_d,
                      lower, nonfinite);

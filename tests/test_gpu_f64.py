@@ -236,6 +236,51 @@ def test_head_philox_jitter_is_the_fp32_draw_widened(B):
     _close(d_o.cpu().numpy(), d_ref, 1e-12, 'dO (Philox)')
 
 
+@pytest.mark.parametrize('eps', [0.0, 1e-5])
+@pytest.mark.parametrize('b,d,k,full', [(5, 3, 4, False), (9, 4, 3, True)])
+def test_head_outputs_and_tuple_loss_match_closed_form(B, b, d, k, full, eps):
+    """bsig_mdn_head_outputs_f64 (weights, mu, L_d, lower; injected noise) and bsig_mdn_nll_from_tuple_f64 of that
+    tuple, called directly, against the closed form; the flag word stays clear, and a NaN in one mu raises it."""
+    from oracle.estimators import mdn_head_closed_form
+    L = B._lib
+    lib = L.load()
+    r = np.random.RandomState(b * 100 + d * 10 + k)
+    ls = d * (d - 1) // 2 if full else 0
+    nh = k + 2 * d * k + ls * k
+    o, y, noise = r.randn(b, nh) * 0.5, r.rand(b, d), r.rand(b, d, k)
+    loss_ref, _, aux = mdn_head_closed_form(o, y, d, k, full, eps_noise=eps, noise=noise)
+    dims, hy = _head_dims(B, d, k, full, eps), _hyper(B, eps)
+    to, ty, tn = _dev(o), _dev(y), _dev(noise)
+    outs = [torch.full((b, n), float('nan'), dtype=torch.float64, device=DEV) for n in (k, d * k, d * k, max(ls * k, 1))]
+    loss = torch.full((1,), float('nan'), dtype=torch.float64, device=DEV)
+    flag = torch.zeros(1, dtype=torch.int32, device=DEV)
+    ws = torch.empty(int(lib.bsig_head_workspace_bytes_f64(C.byref(dims), b)) // 8 + 1, dtype=torch.float64,
+                     device=DEV)
+
+    def outputs(src):
+        L.check(lib.bsig_mdn_head_outputs_f64(C.byref(dims), C.byref(hy), L.ptr(src), nh, b, L.ptr(tn), 0, 0,
+                                              L.ptr(outs[0]), L.ptr(outs[1]), L.ptr(outs[2]),
+                                              L.ptr(outs[3]) if full else None, L.ptr(flag), L.ptr(ws), ws.numel() * 8,
+                                              L.stream()))
+
+    def tuple_loss():
+        L.check(lib.bsig_mdn_nll_from_tuple_f64(C.byref(dims), C.byref(hy), L.ptr(outs[0]), L.ptr(outs[1]),
+                                                L.ptr(outs[2]), L.ptr(outs[3]) if full else None, L.ptr(ty), d, b,
+                                                L.ptr(loss), L.ptr(flag), L.ptr(ws), ws.numel() * 8, L.stream()))
+    outputs(to)
+    tuple_loss()
+    assert int(flag.item()) == 0
+    for got, key in zip(outs[:4 if full else 3], ('weights', 'mu', 'l_d', 'lower')):
+        _close(got.cpu().numpy(), np.asarray(aux[key]).reshape(b, -1), 1e-12, key)
+    assert abs(float(loss.item()) - loss_ref) <= 1e-12 * abs(loss_ref)
+    o[b - 1, k + d * k - 1] = np.nan
+    outputs(_dev(o))
+    assert int(flag.item()) == 1
+    flag.zero_()
+    tuple_loss()                      # (the tuple now carries the NaN)
+    assert int(flag.item()) == 1
+
+
 # ------------------------------------------------------------------ one step
 STEP_CFG = {
     'diag': dict(cls='MDNN', input_dim=40, output_dim=2, n_gaussians=10, full_covariance=False,
