@@ -323,6 +323,16 @@ HEADERS['bsig_sim.h'] = {
     'bsig_sim_rollout': (C.c_int, [C.c_int] + [vp] * 6 + [i64] + [C.c_int] * 3 + [vp, vp]),
     'bsig_sim_rollout_f64': (C.c_int, [C.c_int] + [vp] * 6 + [i64] + [C.c_int] * 3 + [vp, vp]),
 }
+# closed-loop rollouts: an MLP policy inside the rollout kernel
+SIM_ACTIVATIONS = {'identity': 0, 'relu': 1, 'tanh': 2}         # include/bsig_sim_policy.h
+SIM_POLICY_MAX_HIDDEN, SIM_POLICY_MAX_WIDTH, SIM_POLICY_UNITS = 2, 64, 4
+HEADERS['bsig_sim_policy.h'] = {
+    'bsig_sim_policy_size': (i64, [C.c_int] * 4),
+    'bsig_sim_rollout_policy': (C.c_int, [C.c_int] + [vp] * 5 + [C.c_int] * 4 + [vp] * 3 + [i64] + [C.c_int] * 3
+                                + [vp, vp]),
+    'bsig_sim_rollout_policy_f64': (C.c_int, [C.c_int] + [vp] * 5 + [C.c_int] * 4 + [vp] * 3 + [i64]
+                                    + [C.c_int] * 3 + [vp, vp]),
+}
 COMM_ID_BYTES = 128
 EXCHANGE_SUM, EXCHANGE_BROADCAST = 0, 1
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int, vp, i64, C.c_int, vp)
@@ -470,6 +480,8 @@ class Precision:
         'sysid': ('bsig_sysid', 'bsig_sysid_f64'),
         # the rollouts of the analytic tasks (include/bsig_sim.h): fp32 data or double data, double arithmetic
         'sim_rollout': ('bsig_sim_rollout', 'bsig_sim_rollout_f64'),
+        # the same under an MLP policy evaluated in the kernel (include/bsig_sim_policy.h)
+        'sim_rollout_policy': ('bsig_sim_rollout_policy', 'bsig_sim_rollout_policy_f64'),
         # the input-side companions of normalize_rows / copy_rows (the statistics of rows, and the copy that
         # standardises)
         'input_norm_stats': ('bsig_input_norm_stats', 'bsig_input_norm_stats_f64'),

@@ -20,6 +20,13 @@
 // phase 2, a row apart, spread over the banks four at a time instead of meeting on one.
 // Nothing here depends on an episode's end but that episode's own thread: the barriers and the loops' trip
 // counts are functions of n and T alone.
+//
+// Policy is the kernel's third parameter.  NoPolicy (bsig_sim_rollout*) is the open-loop launch: every policy
+// line below is behind `if constexpr (Policy::kOn)`, so those instantiations hold nothing of it.  With
+// MlpPolicy (csrc/sim_policy.h, include/bsig_sim_policy.h) the workgroup stages the weights in the dynamic LDS
+// once, phase 1 brings the block's replace marks in beside the exploration terms, and in phase 2 the thread
+// keeps its observation in double (before any rounding to T), forms a_t from it, steps with that double and
+// records its rounding in lds_a[e][j].
 #pragma once
 #include <climits>
 #include <cmath>
@@ -133,14 +140,20 @@ __device__ inline void write_runs(T* __restrict__ dst, const T* lds, int row, in
   }
 }
 
-template <typename T, typename Task>
+// The open-loop launch: no policy.
+struct NoPolicy {
+  static constexpr bool kOn = false;
+  __host__ __device__ int lds_bytes(int) const { return 0; }
+};
+
+template <typename T, typename Task, typename Policy = NoPolicy>
 __global__ __launch_bounds__(kEpisodes) void rollout_kernel(const T* __restrict__ params,
                                                             const T* __restrict__ init,
                                                             const T* __restrict__ actions, T* __restrict__ states,
                                                             T* __restrict__ actions_out,
                                                             int32_t* __restrict__ lengths, int64_t n, int steps,
                                                             int ta, int terminate, int vec_s, int vec_a,
-                                                            int32_t* __restrict__ nonfinite) {
+                                                            int32_t* __restrict__ nonfinite, Policy pol) {
   constexpr int sd = Task::sd;
   constexpr int per = 16 / (int)sizeof(T);
   constexpr int row_s = kBlock * sd + per, row_a = kBlock + per;
@@ -148,6 +161,14 @@ __global__ __launch_bounds__(kEpisodes) void rollout_kernel(const T* __restrict_
   __shared__ __attribute__((aligned(16))) T lds_a[kEpisodes * row_a];
   const int lane = threadIdx.x;
   const int ts = steps + 1;
+  [[maybe_unused]] double* pol_lds = nullptr;       // the staged policy, and the block's replace marks [e][j]
+  [[maybe_unused]] uint8_t* lds_r = nullptr;
+  if constexpr (Policy::kOn) {
+    extern __shared__ __attribute__((aligned(16))) double sim_policy_smem[];
+    pol_lds = sim_policy_smem;
+    lds_r = reinterpret_cast<uint8_t*>(sim_policy_smem + pol.layout(sd).marks);
+    pol.stage(pol_lds, sd, lane);                   // (the first barrier below orders it before its use)
+  }
 
   for (int64_t base = (int64_t)blockIdx.x * kEpisodes; base < n; base += (int64_t)gridDim.x * kEpisodes) {
     const int ne = (int)(n - base < kEpisodes ? n - base : kEpisodes);
@@ -157,6 +178,7 @@ __global__ __launch_bounds__(kEpisodes) void rollout_kernel(const T* __restrict_
     bool ended = false, bad = false;
     int len = ts;
     T held = (T)0;
+    [[maybe_unused]] double od[Policy::kOn ? sd : 1];     // the observation unrounded: the policy's input
     if (active) {
       task.load(params + (base + lane) * Task::pd, init + (base + lane) * Task::id);
       double o[sd];
@@ -165,6 +187,7 @@ __global__ __launch_bounds__(kEpisodes) void rollout_kernel(const T* __restrict_
       for (int c = 0; c < sd; ++c) {
         obs[c] = (T)o[c];
         bad |= !isfinite(obs[c]);
+        if constexpr (Policy::kOn) od[c] = o[c];
       }
     }
     for (int t0 = 0; t0 < ts; t0 += kBlock) {
@@ -174,6 +197,7 @@ __global__ __launch_bounds__(kEpisodes) void rollout_kernel(const T* __restrict_
         const int e = i / nb, j = i - e * nb;
         const int t = min(min(t0 + j, steps - 1), ta - 1);
         lds_a[e * row_a + j] = actions[(base + e) * ta + t];
+        if constexpr (Policy::kOn) lds_r[e * kBlock + j] = pol.replace ? pol.replace[(base + e) * ta + t] : 0;
       }
       __syncthreads();
       if (active) {
@@ -185,20 +209,32 @@ __global__ __launch_bounds__(kEpisodes) void rollout_kernel(const T* __restrict_
           if (ended) {
             ma[j] = held;
           } else if (t0 + j < steps) {
-            const T a = ma[j];
-            task.step((double)a);
+            T a = ma[j];
+            if constexpr (Policy::kOn) {
+              double av = (double)a;                      // e_t; a_t = e_t where replaced, else pi(o_t) + e_t
+              if (!lds_r[lane * kBlock + j]) av = pol.template eval<sd>(od, pol_lds, lane) + av;
+              a = (T)av;
+              ma[j] = a;
+              held = a;                                   // (state T repeats it: what was loaded there is e)
+              task.step(av);
+            } else {
+              task.step((double)a);
+            }
             double o[sd];
             task.observe(o);
 #pragma unroll
             for (int c = 0; c < sd; ++c) {
               obs[c] = (T)o[c];
               bad |= !isfinite(obs[c]);
+              if constexpr (Policy::kOn) od[c] = o[c];
             }
             if (terminate && task.ended()) {
               ended = true;
               len = t0 + j + 2;       // the state just formed is the last valid one
               held = a;
             }
+          } else if constexpr (Policy::kOn) {
+            ma[j] = held;             // state T of an episode that runs on: the action of step T - 1
           }
         }
       }
@@ -224,9 +260,10 @@ inline int dims(int task, int* pd, int* id, int* sd) {
 }
 
 // The entry point of either type: the argument checks, which runs go out in 16-byte pieces, the launch.
-template <typename T>
+template <typename T, typename Policy = NoPolicy>
 int run(const char* what, int task, const T* params, const T* init, const T* actions, T* states, T* actions_out,
-        int32_t* lengths, int64_t n, int steps, int ta, int terminate, int32_t* nonfinite, bsig_stream_t stream) {
+        int32_t* lengths, int64_t n, int steps, int ta, int terminate, int32_t* nonfinite, bsig_stream_t stream,
+        Policy pol = Policy()) {
   if (n == 0) return BSIG_OK;
   BSIG_REQUIRE(n > 0, "%s: bad n=%lld", what, (long long)n);
   BSIG_REQUIRE(task == BSIG_SIM_PENDULUM || task == BSIG_SIM_CARTPOLE, "%s: unknown task %d", what, task);
@@ -239,12 +276,26 @@ int run(const char* what, int task, const T* params, const T* init, const T* act
   const int vec_s = aligned(states, 16) && (ts * sd * (int64_t)sizeof(T)) % 16 == 0;
   const int vec_a = aligned(actions_out, 16) && (ts * (int64_t)sizeof(T)) % 16 == 0;
   const dim3 grid(capped_grid(ceil_div<int64_t>(n, kEpisodes), BSIG_SIM_GRID_CAP)), block(kEpisodes);
+  // (the dynamic LDS is the policy's alone: none without one)
+  const size_t lds = (size_t)pol.lds_bytes(sd);
+  if constexpr (Policy::kOn) {
+    if (lds > kLdsUnraised) {
+      static LdsRaised raised[2];
+      if (task == BSIG_SIM_PENDULUM) {
+        BSIG_TRY(raise_lds_limit(rollout_kernel<T, Pendulum, Policy>, Policy::kMaxLdsBytes, &raised[0]));
+      } else {
+        BSIG_TRY(raise_lds_limit(rollout_kernel<T, CartPole, Policy>, Policy::kMaxLdsBytes, &raised[1]));
+      }
+    }
+  }
   if (task == BSIG_SIM_PENDULUM) {
-    hipLaunchKernelGGL((rollout_kernel<T, Pendulum>), grid, block, 0, as_stream(stream), params, init, actions,
-                       states, actions_out, lengths, n, steps, ta, terminate, vec_s, vec_a, nonfinite);
+    hipLaunchKernelGGL((rollout_kernel<T, Pendulum, Policy>), grid, block, lds, as_stream(stream), params, init,
+                       actions, states, actions_out, lengths, n, steps, ta, terminate, vec_s, vec_a, nonfinite,
+                       pol);
   } else {
-    hipLaunchKernelGGL((rollout_kernel<T, CartPole>), grid, block, 0, as_stream(stream), params, init, actions,
-                       states, actions_out, lengths, n, steps, ta, terminate, vec_s, vec_a, nonfinite);
+    hipLaunchKernelGGL((rollout_kernel<T, CartPole, Policy>), grid, block, lds, as_stream(stream), params, init,
+                       actions, states, actions_out, lengths, n, steps, ta, terminate, vec_s, vec_a, nonfinite,
+                       pol);
   }
   BSIG_CHECK_LAUNCH(what);
   return BSIG_OK;

@@ -15,7 +15,10 @@ This module produces tensors with that contract from
     (collect_trajectories.py:96-101), and
   * open-loop rollouts of the two analytic tasks, Pendulum and CartPole, with real episode ends
     (``rollout``, ``cartpole_pairs``; include/bsig_sim.h): on the device the tensors live on -- the HIP kernel
-    for GPU tensors, its numpy restatement in double for CPU tensors.
+    for GPU tensors, its numpy restatement in double for CPU tensors; and the same rollouts closed loop, under
+    an ``MLPPolicy`` evaluated step by step inside the kernel (``rollout(policy=, replace=)``,
+    ``cartpole_pairs(policy=<MLPPolicy>)``; include/bsig_sim_policy.h): the reference's ``policy_rl`` and
+    ``policy_rl_randomized`` (collect_trajectories.py) for an actor of up to two hidden layers.
 
 The loaders and ``pendulum_pairs`` are host-side data preparation (numpy); not part of the accelerated path.
 """
@@ -154,8 +157,133 @@ _HOST_TASKS = {'pendulum': (_pendulum_step, _pendulum_observe, None),
                'cartpole': (_cartpole_step, lambda state: state, cartpole_ended)}
 
 
-def _host_rollout(task, params, init, actions, n_steps, terminate):
-    """The definition of include/bsig_sim.h in numpy, double: (states, actions_out, lengths)."""
+class MLPPolicy:
+    """The policy of include/bsig_sim_policy.h: an MLP with 0, 1 or 2 hidden layers of 1..64 units, ONE output
+    without an activation, and one activation ('identity', 'relu' or 'tanh') on every hidden layer.
+    ``weights[l]`` is ``[out_l, in_l]`` and ``biases[l]`` ``[out_l]`` (arrays or tensors; kept as doubles, fp32
+    values widened exactly).  The input width is checked against the task by ``rollout``.
+
+    ``policy(obs)`` is the definition in numpy, double, on ``obs [..., in]``: ``z_j = b_j``, then for k ascending
+    ``z_j = z_j + W_jk * x_k`` (two roundings a term); ``relu(z) = where(z < 0, 0, z)``.  ``to(device)`` packs the
+    weights once per device (``W_0, b_0, W_1, b_1, ...``, one double tensor) and keeps them there.
+    ValueError for anything that does not fit; the message names it."""
+    ACTIVATIONS = ('identity', 'relu', 'tanh')
+
+    def __init__(self, weights, biases, activation='tanh'):
+        self._set(weights, biases, activation)
+
+    def _set(self, weights, biases, activation):
+        as_array = lambda a: (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(np.float64)  # noqa: E731
+        weights, biases = [as_array(w) for w in weights], [as_array(b) for b in biases]
+        if len(weights) < 1 or len(weights) != len(biases):
+            raise ValueError('weights and biases must hold one entry per layer, at least one, got %d and %d'
+                             % (len(weights), len(biases)))
+        if len(weights) - 1 > _lib.SIM_POLICY_MAX_HIDDEN:
+            raise ValueError('weights: %d hidden layers, more than %d' % (len(weights) - 1, _lib.SIM_POLICY_MAX_HIDDEN))
+        for l, (w, b) in enumerate(zip(weights, biases)):
+            if w.ndim != 2 or b.shape != (w.shape[0],) or (l == 0 and w.shape[1] < 1):
+                raise ValueError('weights[%d] must be [out, in] and biases[%d] [out], got %r and %r'
+                                 % (l, l, w.shape, b.shape))
+            if l and w.shape[1] != weights[l - 1].shape[0]:
+                raise ValueError('weights[%d] takes %d inputs, the layer before has %d units'
+                                 % (l, w.shape[1], weights[l - 1].shape[0]))
+        for l, w in enumerate(weights[:-1]):
+            if not 1 <= w.shape[0] <= _lib.SIM_POLICY_MAX_WIDTH:
+                raise ValueError('weights[%d]: a hidden width of %d is outside 1..%d'
+                                 % (l, w.shape[0], _lib.SIM_POLICY_MAX_WIDTH))
+        if weights[-1].shape[0] != 1:
+            raise ValueError('weights[%d]: the policy has one output, got %d' % (len(weights) - 1, weights[-1].shape[0]))
+        if activation not in self.ACTIVATIONS:
+            raise ValueError('activation must be one of %r, got %r' % (self.ACTIVATIONS, activation))
+        self.weights, self.biases, self.activation = weights, biases, activation
+        self.in_dim = weights[0].shape[1]
+        self.hidden = tuple(w.shape[0] for w in weights[:-1])
+        self._packed = {}
+
+    @classmethod
+    def from_module(cls, module):
+        """From a ``torch.nn.Sequential`` of ``Linear`` layers with ``Tanh``, ``ReLU`` or ``Identity`` between
+        them (one kind throughout; none behind the last ``Linear``)."""
+        nn = torch.nn
+        kinds = {nn.Tanh: 'tanh', nn.ReLU: 'relu', nn.Identity: 'identity'}
+        weights, biases, behind = [], [], []          # behind[l]: the activation behind Linear l
+        for i, layer in enumerate(module):
+            if isinstance(layer, nn.Linear):
+                if layer.bias is None:
+                    raise ValueError('module[%d]: a Linear without a bias' % i)
+                weights.append(layer.weight), biases.append(layer.bias), behind.append('identity')
+            elif type(layer) is nn.Identity:
+                continue
+            elif type(layer) in kinds and weights and behind[-1] == 'identity':
+                behind[-1] = kinds[type(layer)]
+            else:
+                raise ValueError('module[%d]: %s where a Linear, or one Tanh / ReLU / Identity behind one, belongs'
+                                 % (i, type(layer).__name__))
+        if behind and behind[-1] != 'identity':
+            raise ValueError('module: the last Linear is the output, no %s behind it' % behind[-1])
+        if len(set(behind[:-1])) > 1:
+            raise ValueError('module: one activation for all hidden layers, got %s' % sorted(set(behind[:-1])))
+        return cls(weights, biases, behind[0] if len(behind) > 1 else 'identity')
+
+    def packed(self):
+        """The packed policy: one double array, ``W_0`` (row-major), ``b_0``, ``W_1``, ``b_1``, ..."""
+        return np.concatenate([part.ravel() for w, b in zip(self.weights, self.biases) for part in (w, b)])
+
+    def to(self, device):
+        """Pack the weights on ``device`` (once: kept for later launches); returns ``self``."""
+        self.packed_on(device)
+        return self
+
+    def packed_on(self, device):
+        device = torch.device(device)
+        if device.type == 'cuda' and device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        if device not in self._packed:
+            self._packed[device] = torch.from_numpy(self.packed()).to(device)
+        return self._packed[device]
+
+    def __call__(self, obs):
+        x = np.asarray(obs, dtype=np.float64)
+        if x.shape[-1] != self.in_dim:
+            raise ValueError('obs must be [..., %d], got %r' % (self.in_dim, x.shape))
+        with np.errstate(all='ignore'):
+            for l, (w, b) in enumerate(zip(self.weights, self.biases)):
+                z = np.broadcast_to(b, x.shape[:-1] + b.shape).copy()
+                for k in range(w.shape[1]):
+                    z = z + w[:, k] * x[..., k:k + 1]
+                if l + 1 < len(self.weights):
+                    if self.activation == 'relu':
+                        z = np.where(z < 0, 0.0, z)
+                    elif self.activation == 'tanh':
+                        z = np.tanh(z)
+                x = z
+        return x[..., 0]
+
+    def state_dict(self):
+        return {'weights': [w.copy() for w in self.weights], 'biases': [b.copy() for b in self.biases],
+                'activation': self.activation}
+
+    def load_state_dict(self, state):
+        self._set(state['weights'], state['biases'], state['activation'])
+        return self
+
+
+def linear_feedback(gains, bias=0.0):
+    """``a = gains . o + bias``: the policy without a hidden layer."""
+    return MLPPolicy([np.asarray(gains, dtype=np.float64).reshape(1, -1)], [np.array([float(bias)])], 'identity')
+
+
+# A feedback on (x, xdot, th, thdot) that keeps CartPole up.  Measured by tools/closed_loop_cpu_table.py --shares
+# (host path, cartpole_pairs(4000, T, seed=0, terminate=True): theta in [0.1, 2]^2, cart mass 1, initial state
+# U[-0.05, 0.05)^4): under it 0 of 4000 episodes end in 50 steps and 10 (0.25 %) in 200; under random actions
+# 3069 (76.7 %) and 3999 (99.97 %, mean length 39.4 states); with frac_rnd = 0.1 of the actions replaced by
+# U[-1, 1] 0 and 71 (1.8 %); with frac_rnd = 0.3, 6 (0.15 %) and 459 (11.5 %).
+CARTPOLE_BALANCE_GAINS = (0.2, 0.5, 8.0, 1.5)
+
+
+def _host_rollout(task, params, init, actions, n_steps, terminate, policy=None, replace=None):
+    """The definition of include/bsig_sim.h (and, with a policy, of include/bsig_sim_policy.h) in numpy, double:
+    (states, actions_out, lengths)."""
     step, observe, ended = _HOST_TASKS[task]
     n, ta = params.shape[0], actions.shape[1]
     states = np.empty((n, n_steps + 1, SIM_DIMS[task][2]))
@@ -166,6 +294,9 @@ def _host_rollout(task, params, init, actions, n_steps, terminate):
     with np.errstate(all='ignore'):
         for t in range(n_steps):
             act = actions[:, min(t, ta - 1), 0]
+            if policy is not None:                      # a_t = e_t where replaced, else pi(o_t) + e_t
+                closed = policy(states[:, t]) + act
+                act = closed if replace is None else np.where(replace[:, min(t, ta - 1)] != 0, act, closed)
             state = step(params, state, act)
             acts[:, t, 0] = act
             states[:, t + 1] = observe(state)
@@ -179,8 +310,9 @@ def _host_rollout(task, params, init, actions, n_steps, terminate):
     return states, acts, lengths
 
 
-def rollout(task, params, init, actions, n_steps=None, terminate=False, dtype=None, nonfinite=None):
-    """Open-loop rollouts of ``task`` ('pendulum' or 'cartpole'), the definition of include/bsig_sim.h:
+def rollout(task, params, init, actions, n_steps=None, terminate=False, dtype=None, nonfinite=None, policy=None,
+            replace=None):
+    """Rollouts of ``task`` ('pendulum' or 'cartpole'), the definition of include/bsig_sim.h:
     ``params`` [N, pd], ``init`` [N, id] (the initial INTERNAL state), ``actions`` [N, Ta, 1] ->
     ``(states [N, T + 1, sd], actions_out [N, T + 1, 1], lengths [N] int32)``, T = ``n_steps``.
 
@@ -208,7 +340,15 @@ def rollout(task, params, init, actions, n_steps=None, terminate=False, dtype=No
     their device (csrc/sim.h); CPU tensors run the numpy restatement on the host and never touch a GPU.  The
     two differ by the sine and cosine of their libraries alone.  ``nonfinite``: an optional 1-element int32
     tensor on the same device, set to 1 where a state is not finite (nothing is repaired or read back).
-    ValueError, before any GPU call, for a shape, a device or an argument that does not fit; it names it."""
+    ValueError, before any GPU call, for a shape, a device or an argument that does not fit; it names it.
+
+    Closed loop (include/bsig_sim_policy.h).  With ``policy`` (an ``MLPPolicy`` whose input width is the task's
+    sd) ``actions`` holds the exploration terms e and the action of step t is ``pi(o_t) + e_t``, one add, with
+    ``o_t`` the observation in double before any rounding; where ``replace`` (optional, uint8 or bool ``[N, Ta]``
+    on the same device, indexed like the actions) is not 0 it is ``e_t`` alone.  That action is what the step
+    takes and what ``actions_out`` records; ends and fills are as above.  The policy is evaluated inside the
+    kernel for GPU tensors and by ``policy(obs)`` on the host for CPU tensors; the two differ by their libraries'
+    sine, cosine and tanh alone.  ``policy=None, replace=None`` is the open-loop call, unchanged."""
     if task not in SIM_DIMS:
         raise ValueError("task must be 'pendulum' or 'cartpole', got %r" % (task,))
     pd, idim, sd = SIM_DIMS[task]
@@ -249,10 +389,29 @@ def rollout(task, params, init, actions, n_steps=None, terminate=False, dtype=No
     if nonfinite is not None and not (torch.is_tensor(nonfinite) and nonfinite.dtype == torch.int32
                                       and nonfinite.numel() == 1 and nonfinite.device == dev):
         raise ValueError('nonfinite must be a 1-element int32 tensor on %s' % (dev,))
+    if policy is None:
+        if replace is not None:
+            raise ValueError('replace marks the steps that do not follow the policy: it needs policy=')
+    else:
+        if not isinstance(policy, MLPPolicy):
+            raise ValueError('policy must be an MLPPolicy, got %r' % (type(policy).__name__,))
+        if policy.in_dim != sd:
+            raise ValueError('policy takes %d inputs, %s observes %d' % (policy.in_dim, task, sd))
+        if replace is not None:
+            if not torch.is_tensor(replace) or replace.dtype not in (torch.uint8, torch.bool) \
+                    or tuple(replace.shape) != (n, ta):
+                raise ValueError('replace must be a uint8 or bool tensor [%d, %d], got %s'
+                                 % (n, ta, (replace.dtype, tuple(replace.shape)) if torch.is_tensor(replace)
+                                    else type(replace).__name__))
+            if replace.device != dev:
+                raise ValueError('replace must live on %s with params, init and actions, got %s'
+                                 % (dev, replace.device))
+            replace = replace.detach().to(torch.uint8).contiguous()
     p, s0, a = (t.detach().to(prec.dtype).contiguous() for t in (params, init, actions))
     if not dev.type == 'cuda':
         states, acts, lengths = _host_rollout(task, p.double().numpy(), s0.double().numpy(), a.double().numpy(),
-                                              n_steps, bool(terminate))
+                                              n_steps, bool(terminate), policy,
+                                              None if replace is None else replace.numpy())
         if nonfinite is not None and not np.isfinite(states).all():
             nonfinite.fill_(1)
         return (torch.from_numpy(states).to(prec.dtype), torch.from_numpy(acts).to(prec.dtype),
@@ -262,6 +421,14 @@ def rollout(task, params, init, actions, n_steps=None, terminate=False, dtype=No
         states = torch.empty((n, n_steps + 1, sd), dtype=prec.dtype, device=dev)
         acts = torch.empty((n, n_steps + 1, 1), dtype=prec.dtype, device=dev)
         lengths = torch.empty((n,), dtype=torch.int32, device=dev)
+        if policy is not None:
+            hidden = policy.hidden + (0, 0)
+            prec.sim_rollout_policy(_lib.SIM_TASKS[task], _lib.ptr(p), _lib.ptr(s0), _lib.ptr(a), _lib.ptr(replace),
+                                    _lib.ptr(policy.packed_on(dev)), len(policy.hidden), hidden[0], hidden[1],
+                                    _lib.SIM_ACTIVATIONS[policy.activation], _lib.ptr(states), _lib.ptr(acts),
+                                    _lib.ptr(lengths), n, n_steps, ta, int(bool(terminate)), _lib.ptr(nonfinite),
+                                    stream)
+            return states, acts, lengths
         prec.sim_rollout(_lib.SIM_TASKS[task], _lib.ptr(p), _lib.ptr(s0), _lib.ptr(a), _lib.ptr(states),
                          _lib.ptr(acts), _lib.ptr(lengths), n, n_steps, ta, int(bool(terminate)),
                          _lib.ptr(nonfinite), stream)
@@ -269,7 +436,7 @@ def rollout(task, params, init, actions, n_steps=None, terminate=False, dtype=No
 
 
 def cartpole_pairs(n, traj_len, policy='random', lows=(0.1, 0.1), highs=(2.0, 2.0), cart_mass=1.0,
-                   params=None, seed=None, device='cpu', terminate=False):
+                   params=None, seed=None, device='cpu', terminate=False, frac_rnd=0.0, noise_std=0.0):
     """n CartPole episodes of ``traj_len`` actions in ``pendulum_pairs``' contract: theta [n, 2] = (pole mass,
     pole half-length) with the cart's mass the constant ``cart_mass``, or, with three bounds, theta [n, 3] with
     the cart's mass drawn as well; states [n, traj_len + 1, 4] = (x, xdot, th, thdot); actions
@@ -280,7 +447,15 @@ def cartpole_pairs(n, traj_len, policy='random', lows=(0.1, 0.1), highs=(2.0, 2.
     ``uniform(lows, highs, (n, 2 or 3))`` (none with ``params=``, which is broadcast to that shape), the initial
     state ``uniform(-0.05, 0.05, (n, 4))``, the actions ``uniform(-1, 1, (n, traj_len))`` for ``'random'`` (none
     for ``'ones'``: every action is 1).  The rollout then runs on ``device`` in double --
-    ``rollout('cartpole', ..., dtype=torch.float64)`` on the draws as they are -- and is rounded once."""
+    ``rollout('cartpole', ..., dtype=torch.float64)`` on the draws as they are -- and is rounded once.
+
+    With ``policy`` an ``MLPPolicy`` (4 inputs) the episodes run closed loop, as ``rollout(policy=, replace=)``
+    states it, and the returned actions are the ones taken.  After theta and the initial state the draws are, in
+    this order and each only if it is used: ``replace = uniform(size=(n, traj_len)) < frac_rnd`` (only if
+    ``frac_rnd > 0``), ``uniform(-1, 1, (n, traj_len))`` (only if ``frac_rnd > 0``: the actions where replaced)
+    and ``standard_normal((n, traj_len))`` (only if ``noise_std > 0``: times ``noise_std``, the exploration term
+    elsewhere).  ``frac_rnd = noise_std = 0`` is the policy alone (the reference's policy_rl), ``frac_rnd > 0``
+    its policy_rl_randomized.  Both must be 0 with ``'random'`` / ``'ones'``, whose draws are unchanged."""
     rs = np.random.RandomState(seed) if seed is not None else np.random
     lows, highs = np.asarray(lows, dtype=np.float64), np.asarray(highs, dtype=np.float64)
     if lows.shape != highs.shape or lows.shape not in ((2,), (3,)):
@@ -292,7 +467,19 @@ def cartpole_pairs(n, traj_len, policy='random', lows=(0.1, 0.1), highs=(2.0, 2.
     else:
         theta = np.broadcast_to(np.asarray(params, dtype=np.float64), (n, k)).copy()
     init = rs.uniform(-0.05, 0.05, size=(n, 4))
-    if policy in ('random', 'policy_random'):
+    closed, replace = isinstance(policy, MLPPolicy), None
+    if not 0.0 <= frac_rnd <= 1.0 or not noise_std >= 0.0:
+        raise ValueError('frac_rnd must lie in [0, 1] and noise_std be >= 0, got %r and %r' % (frac_rnd, noise_std))
+    if not closed and (frac_rnd or noise_std) and policy in ('random', 'policy_random', 'ones', 'policy_ones'):
+        raise ValueError('frac_rnd and noise_std belong to an MLPPolicy, not to policy=%r' % (policy,))
+    if closed:
+        if frac_rnd > 0:
+            replace = rs.uniform(size=(n, traj_len)) < frac_rnd
+            instead = rs.uniform(-1.0, 1.0, size=(n, traj_len))
+        acts = noise_std * rs.standard_normal((n, traj_len)) if noise_std > 0 else np.zeros((n, traj_len))
+        if frac_rnd > 0:
+            acts = np.where(replace, instead, acts)
+    elif policy in ('random', 'policy_random'):
         acts = rs.uniform(-1.0, 1.0, size=(n, traj_len))
     elif policy in ('ones', 'policy_ones'):
         acts = np.ones((n, traj_len))
@@ -301,6 +488,8 @@ def cartpole_pairs(n, traj_len, policy='random', lows=(0.1, 0.1), highs=(2.0, 2.
     full = theta if k == 3 else np.column_stack([theta, np.full(n, float(cart_mass))])
     to = lambda arr: torch.from_numpy(np.ascontiguousarray(arr)).to(device)      # noqa: E731
     states, actions, lengths = rollout('cartpole', to(full), to(init), to(acts[:, :, None]), n_steps=traj_len,
-                                       terminate=terminate, dtype=torch.float64)
+                                       terminate=terminate, dtype=torch.float64,
+                                       policy=policy if closed else None,
+                                       replace=None if replace is None else to(replace))
     out = (to(theta).float(), states.float(), actions.float())
     return out + (lengths,) if terminate else out
