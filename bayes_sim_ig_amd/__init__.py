@@ -11,6 +11,7 @@ from .bayes_sim import BayesSim               # noqa: F401
 from .kme import KernelMeanEmbedding          # noqa: F401
 from .mdnn import MDNN                        # noqa: F401
 from .mdrff import MDRFF                      # noqa: F401
+from .pairs import EpisodeDraws, draw_pairs, rollout_drawn   # noqa: F401
 from .rff import RFF                          # noqa: F401
 from .summarizers import (pad_states_actions, summary_start, summary_waypts,  # noqa: F401
                           summary_corr, summary_corrdiff, summary_signatory,

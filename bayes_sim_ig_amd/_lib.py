@@ -333,6 +333,15 @@ HEADERS['bsig_sim_policy.h'] = {
     'bsig_sim_rollout_policy_f64': (C.c_int, [C.c_int] + [vp] * 5 + [C.c_int] * 4 + [vp] * 3 + [i64]
                                     + [C.c_int] * 3 + [vp, vp]),
 }
+# rollouts whose numbers are drawn inside the kernel by a counter-based generator
+SIM_DRAW_STEP, SIM_DRAW_THETA, SIM_DRAW_INIT = 0, 1, 2         # include/bsig_sim_draws.h: the counter's purpose word
+_DRAWN = [C.c_int, vp, vp] + [vp] * 4 + [f64] * 4 + [u64, u64] + [vp] + [C.c_int] * 4 + [vp] * 7 \
+    + [i64, C.c_int, C.c_int, vp, vp]
+HEADERS['bsig_sim_draws.h'] = {
+    'bsig_philox4x32_10': (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, i64, vp]),
+    'bsig_sim_rollout_drawn': (C.c_int, _DRAWN),
+    'bsig_sim_rollout_drawn_f64': (C.c_int, list(_DRAWN)),
+}
 COMM_ID_BYTES = 128
 EXCHANGE_SUM, EXCHANGE_BROADCAST = 0, 1
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int, vp, i64, C.c_int, vp)
@@ -482,6 +491,8 @@ class Precision:
         'sim_rollout': ('bsig_sim_rollout', 'bsig_sim_rollout_f64'),
         # the same under an MLP policy evaluated in the kernel (include/bsig_sim_policy.h)
         'sim_rollout_policy': ('bsig_sim_rollout_policy', 'bsig_sim_rollout_policy_f64'),
+        # the same with every number drawn inside the kernel (include/bsig_sim_draws.h)
+        'sim_rollout_drawn': ('bsig_sim_rollout_drawn', 'bsig_sim_rollout_drawn_f64'),
         # the input-side companions of normalize_rows / copy_rows (the statistics of rows, and the copy that
         # standardises)
         'input_norm_stats': ('bsig_input_norm_stats', 'bsig_input_norm_stats_f64'),

@@ -27,6 +27,12 @@
 // once, phase 1 brings the block's replace marks in beside the exploration terms, and in phase 2 the thread
 // keeps its observation in double (before any rounding to T), forms a_t from it, steps with that double and
 // records its rounding in lds_a[e][j].
+//
+// Draws is the fourth parameter.  NoDraws is every launch above: each draw line below is behind
+// `if constexpr (Draws::kOn)`.  With EpisodeDraws (csrc/sim_draws.h, include/bsig_sim_draws.h) phase 1 goes away
+// -- the launch reads no [N, Ta] array: the thread makes theta and the initial state of its own episode before
+// step 0 (they leave through lds_s and lds_a, an episode's run at a time), and e_t and r_t at step t, in
+// registers; the recordings of a block are staged in lds_e and lds_m beside lds_a and leave the same way.
 #pragma once
 #include <climits>
 #include <cmath>
@@ -146,14 +152,20 @@ struct NoPolicy {
   __host__ __device__ int lds_bytes(int) const { return 0; }
 };
 
-template <typename T, typename Task, typename Policy = NoPolicy>
+// Every launch whose numbers are the caller's: no draws.
+struct NoDraws {
+  static constexpr bool kOn = false;
+};
+
+template <typename T, typename Task, typename Policy = NoPolicy, typename Draws = NoDraws>
 __global__ __launch_bounds__(kEpisodes) void rollout_kernel(const T* __restrict__ params,
                                                             const T* __restrict__ init,
                                                             const T* __restrict__ actions, T* __restrict__ states,
                                                             T* __restrict__ actions_out,
                                                             int32_t* __restrict__ lengths, int64_t n, int steps,
                                                             int ta, int terminate, int vec_s, int vec_a,
-                                                            int32_t* __restrict__ nonfinite, Policy pol) {
+                                                            int32_t* __restrict__ nonfinite, Policy pol,
+                                                            Draws drw) {
   constexpr int sd = Task::sd;
   constexpr int per = 16 / (int)sizeof(T);
   constexpr int row_s = kBlock * sd + per, row_a = kBlock + per;
@@ -169,6 +181,14 @@ __global__ __launch_bounds__(kEpisodes) void rollout_kernel(const T* __restrict_
     lds_r = reinterpret_cast<uint8_t*>(sim_policy_smem + pol.layout(sd).marks);
     pol.stage(pol_lds, sd, lane);                   // (the first barrier below orders it before its use)
   }
+  [[maybe_unused]] T* lds_e = nullptr;              // the block's recordings: e_t [e][j] and r_t [e][j]
+  [[maybe_unused]] uint8_t* lds_m = nullptr;
+  if constexpr (Draws::kOn) {
+    __shared__ __attribute__((aligned(16))) T sim_draws_e[kEpisodes * row_a];
+    __shared__ __attribute__((aligned(16))) uint8_t sim_draws_m[kEpisodes * kBlock];
+    lds_e = sim_draws_e;
+    lds_m = sim_draws_m;
+  }
 
   for (int64_t base = (int64_t)blockIdx.x * kEpisodes; base < n; base += (int64_t)gridDim.x * kEpisodes) {
     const int ne = (int)(n - base < kEpisodes ? n - base : kEpisodes);
@@ -179,8 +199,21 @@ __global__ __launch_bounds__(kEpisodes) void rollout_kernel(const T* __restrict_
     int len = ts;
     T held = (T)0;
     [[maybe_unused]] double od[Policy::kOn ? sd : 1];     // the observation unrounded: the policy's input
+    [[maybe_unused]] uint64_t g = 0;                      // the episode's global index: its draws' counter
+    if constexpr (Draws::kOn) __syncthreads();            // the batch before has left the LDS
     if (active) {
-      task.load(params + (base + lane) * Task::pd, init + (base + lane) * Task::id);
+      if constexpr (Draws::kOn) {
+        g = drw.first + (uint64_t)(base + lane);
+        T p[Task::pd], s0[Task::id];
+        drw.template episode<Task::pd, Task::id>(g, params, init, base + lane, p, s0);
+        task.load(p, s0);
+#pragma unroll
+        for (int c = 0; c < Task::pd; ++c) lds_s[lane * row_s + c] = p[c];
+#pragma unroll
+        for (int c = 0; c < Task::id; ++c) lds_a[lane * row_a + c] = s0[c];
+      } else {
+        task.load(params + (base + lane) * Task::pd, init + (base + lane) * Task::id);
+      }
       double o[sd];
       task.observe(o);
 #pragma unroll
@@ -190,16 +223,24 @@ __global__ __launch_bounds__(kEpisodes) void rollout_kernel(const T* __restrict_
         if constexpr (Policy::kOn) od[c] = o[c];
       }
     }
+    if constexpr (Draws::kOn) {       // what the episodes run with: a row of pd and of id elements each
+      static_assert(Task::pd <= row_s && Task::id <= row_a, "theta and the initial state fit the staging rows");
+      __syncthreads();
+      write_runs(drw.params_out, lds_s, row_s, base, (int64_t)Task::pd, ne, Task::pd, false, lane);
+      write_runs(drw.init_out, lds_a, row_a, base, (int64_t)Task::id, ne, Task::id, false, lane);
+    }
     for (int t0 = 0; t0 < ts; t0 += kBlock) {
       const int nb = ts - t0 < kBlock ? ts - t0 : kBlock;
       __syncthreads();          // the block before has left the LDS
-      for (int i = lane; i < ne * nb; i += kEpisodes) {
-        const int e = i / nb, j = i - e * nb;
-        const int t = min(min(t0 + j, steps - 1), ta - 1);
-        lds_a[e * row_a + j] = actions[(base + e) * ta + t];
-        if constexpr (Policy::kOn) lds_r[e * kBlock + j] = pol.replace ? pol.replace[(base + e) * ta + t] : 0;
+      if constexpr (!Draws::kOn) {
+        for (int i = lane; i < ne * nb; i += kEpisodes) {
+          const int e = i / nb, j = i - e * nb;
+          const int t = min(min(t0 + j, steps - 1), ta - 1);
+          lds_a[e * row_a + j] = actions[(base + e) * ta + t];
+          if constexpr (Policy::kOn) lds_r[e * kBlock + j] = pol.replace ? pol.replace[(base + e) * ta + t] : 0;
+        }
+        __syncthreads();
       }
-      __syncthreads();
       if (active) {
         T* ms = lds_s + lane * row_s;
         T* ma = lds_a + lane * row_a;
@@ -208,16 +249,33 @@ __global__ __launch_bounds__(kEpisodes) void rollout_kernel(const T* __restrict_
           for (int c = 0; c < sd; ++c) ms[j * sd + c] = obs[c];
           if (ended) {
             ma[j] = held;
+            if constexpr (Draws::kOn) {                   // an ended episode draws nothing more
+              lds_e[lane * row_a + j] = (T)0;
+              lds_m[lane * kBlock + j] = 0;
+            }
           } else if (t0 + j < steps) {
-            T a = ma[j];
+            T a;
+            [[maybe_unused]] bool mark = false;
+            if constexpr (Draws::kOn) {
+              a = drw.template step<Policy::kOn>(g, t0 + j, &mark);      // e_t (v_t without a policy) and r_t
+              lds_e[lane * row_a + j] = a;
+              lds_m[lane * kBlock + j] = mark;
+            } else {
+              a = ma[j];
+            }
             if constexpr (Policy::kOn) {
               double av = (double)a;                      // e_t; a_t = e_t where replaced, else pi(o_t) + e_t
-              if (!lds_r[lane * kBlock + j]) av = pol.template eval<sd>(od, pol_lds, lane) + av;
+              if constexpr (!Draws::kOn) mark = lds_r[lane * kBlock + j];
+              if (!mark) av = pol.template eval<sd>(od, pol_lds, lane) + av;
               a = (T)av;
               ma[j] = a;
               held = a;                                   // (state T repeats it: what was loaded there is e)
               task.step(av);
             } else {
+              if constexpr (Draws::kOn) {
+                ma[j] = a;
+                held = a;                                 // (state T repeats it: nothing was loaded there)
+              }
               task.step((double)a);
             }
             double o[sd];
@@ -233,7 +291,7 @@ __global__ __launch_bounds__(kEpisodes) void rollout_kernel(const T* __restrict_
               len = t0 + j + 2;       // the state just formed is the last valid one
               held = a;
             }
-          } else if constexpr (Policy::kOn) {
+          } else if constexpr (Policy::kOn || Draws::kOn) {
             ma[j] = held;             // state T of an episode that runs on: the action of step T - 1
           }
         }
@@ -242,6 +300,16 @@ __global__ __launch_bounds__(kEpisodes) void rollout_kernel(const T* __restrict_
       write_runs(states + (int64_t)t0 * sd, lds_s, row_s, base, (int64_t)ts * sd, ne, nb * sd,
                  vec_s && (nb * sd) % per == 0, lane);
       write_runs(actions_out + t0, lds_a, row_a, base, (int64_t)ts, ne, nb, vec_a && nb % per == 0, lane);
+      if constexpr (Draws::kOn) {       // the recordings hold T steps, not T + 1 states
+        const int nbe = steps - t0 < nb ? steps - t0 : nb;
+        if (drw.explore_out && nbe > 0) {
+          write_runs(drw.explore_out + t0, lds_e, row_a, base, (int64_t)steps, ne, nbe,
+                     drw.vec_e && nbe % per == 0, lane);
+        }
+        if (drw.replace_out && nbe > 0) {
+          write_runs(drw.replace_out + t0, lds_m, kBlock, base, (int64_t)steps, ne, nbe, false, lane);
+        }
+      }
     }
     if (active) {
       lengths[base + lane] = len;
@@ -260,17 +328,19 @@ inline int dims(int task, int* pd, int* id, int* sd) {
 }
 
 // The entry point of either type: the argument checks, which runs go out in 16-byte pieces, the launch.
-template <typename T, typename Policy = NoPolicy>
+template <typename T, typename Policy = NoPolicy, typename Draws = NoDraws>
 int run(const char* what, int task, const T* params, const T* init, const T* actions, T* states, T* actions_out,
         int32_t* lengths, int64_t n, int steps, int ta, int terminate, int32_t* nonfinite, bsig_stream_t stream,
-        Policy pol = Policy()) {
+        Policy pol = Policy(), Draws drw = Draws()) {
   if (n == 0) return BSIG_OK;
   BSIG_REQUIRE(n > 0, "%s: bad n=%lld", what, (long long)n);
   BSIG_REQUIRE(task == BSIG_SIM_PENDULUM || task == BSIG_SIM_CARTPOLE, "%s: unknown task %d", what, task);
   BSIG_REQUIRE(steps >= 1 && steps < INT_MAX / 8, "%s: T %d outside 1..%d", what, steps, INT_MAX / 8 - 1);
   BSIG_REQUIRE(ta >= 1, "%s: Ta %d below 1", what, ta);
   BSIG_REQUIRE(terminate == 0 || terminate == 1, "%s: terminate %d is not 0 or 1", what, terminate);
-  BSIG_REQUIRE(params && init && actions && states && actions_out && lengths, "%s: null pointer", what);
+  if constexpr (!Draws::kOn) {      // (run_drawn has checked its own pointers, each by name)
+    BSIG_REQUIRE(params && init && actions && states && actions_out && lengths, "%s: null pointer", what);
+  }
   const int sd = task == BSIG_SIM_PENDULUM ? Pendulum::sd : CartPole::sd;
   const int64_t ts = (int64_t)steps + 1;
   const int vec_s = aligned(states, 16) && (ts * sd * (int64_t)sizeof(T)) % 16 == 0;
@@ -282,20 +352,20 @@ int run(const char* what, int task, const T* params, const T* init, const T* act
     if (lds > kLdsUnraised) {
       static LdsRaised raised[2];
       if (task == BSIG_SIM_PENDULUM) {
-        BSIG_TRY(raise_lds_limit(rollout_kernel<T, Pendulum, Policy>, Policy::kMaxLdsBytes, &raised[0]));
+        BSIG_TRY(raise_lds_limit(rollout_kernel<T, Pendulum, Policy, Draws>, Policy::kMaxLdsBytes, &raised[0]));
       } else {
-        BSIG_TRY(raise_lds_limit(rollout_kernel<T, CartPole, Policy>, Policy::kMaxLdsBytes, &raised[1]));
+        BSIG_TRY(raise_lds_limit(rollout_kernel<T, CartPole, Policy, Draws>, Policy::kMaxLdsBytes, &raised[1]));
       }
     }
   }
   if (task == BSIG_SIM_PENDULUM) {
-    hipLaunchKernelGGL((rollout_kernel<T, Pendulum, Policy>), grid, block, lds, as_stream(stream), params, init,
-                       actions, states, actions_out, lengths, n, steps, ta, terminate, vec_s, vec_a, nonfinite,
-                       pol);
+    hipLaunchKernelGGL((rollout_kernel<T, Pendulum, Policy, Draws>), grid, block, lds, as_stream(stream), params,
+                       init, actions, states, actions_out, lengths, n, steps, ta, terminate, vec_s, vec_a,
+                       nonfinite, pol, drw);
   } else {
-    hipLaunchKernelGGL((rollout_kernel<T, CartPole, Policy>), grid, block, lds, as_stream(stream), params, init,
-                       actions, states, actions_out, lengths, n, steps, ta, terminate, vec_s, vec_a, nonfinite,
-                       pol);
+    hipLaunchKernelGGL((rollout_kernel<T, CartPole, Policy, Draws>), grid, block, lds, as_stream(stream), params,
+                       init, actions, states, actions_out, lengths, n, steps, ta, terminate, vec_s, vec_a,
+                       nonfinite, pol, drw);
   }
   BSIG_CHECK_LAUNCH(what);
   return BSIG_OK;

@@ -18,7 +18,11 @@ This module produces tensors with that contract from
     for GPU tensors, its numpy restatement in double for CPU tensors; and the same rollouts closed loop, under
     an ``MLPPolicy`` evaluated step by step inside the kernel (``rollout(policy=, replace=)``,
     ``cartpole_pairs(policy=<MLPPolicy>)``; include/bsig_sim_policy.h): the reference's ``policy_rl`` and
-    ``policy_rl_randomized`` (collect_trajectories.py) for an actor of up to two hidden layers.
+    ``policy_rl_randomized`` (collect_trajectories.py) for an actor of up to two hidden layers; and
+  * the same rollouts with every number -- theta, the initial state, the marks, the replacement actions, the
+    exploration noise -- drawn inside the kernel by a counter-based generator (``rollout_drawn``, ``draw_pairs``;
+    include/bsig_sim_draws.h): an episode is a function of (seed, global episode index) alone, and nothing is
+    drawn on the host or copied.
 
 The loaders and ``pendulum_pairs`` are host-side data preparation (numpy); not part of the accelerated path.
 """
@@ -492,4 +496,329 @@ def cartpole_pairs(n, traj_len, policy='random', lows=(0.1, 0.1), highs=(2.0, 2.
                                        policy=policy if closed else None,
                                        replace=None if replace is None else to(replace))
     out = (to(theta).float(), states.float(), actions.float())
+    return out + (lengths,) if terminate else out
+
+
+# ---------------------------------------------------------------- draws on the device (include/bsig_sim_draws.h)
+PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_TWO_PI = 6.283185307179586
+_MASK32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32(counters, key):
+    """Philox4x32-10 (Salmon et al., SC 2011) in numpy: ``counters`` ``[..., 4]`` and ``key = (k0, k1)`` (integers
+    below 2^32, the key's words scalars or arrays that broadcast against ``[...]``) -> uint32 ``[..., 4]``.  Ten
+    rounds of ``c' = (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0))``, the key bumped by
+    (0x9E3779B9, 0xBB67AE85) after each."""
+    c = np.asarray(counters)
+    if c.ndim < 1 or c.shape[-1] != 4 or c.dtype.kind not in 'iu':
+        raise ValueError('counters must be an integer array [..., 4], got %s %r' % (c.dtype, c.shape))
+    c = c.astype(np.uint64)
+    if (c > _MASK32).any():
+        raise ValueError('counters must be below 2^32')
+    if len(key) != 2:
+        raise ValueError('key must be (k0, k1), got %r' % (key,))
+    k0, k1 = (np.asarray(k).astype(np.uint64) & _MASK32 for k in key)
+    c0, c1, c2, c3 = (c[..., i] for i in range(4))
+    m0, m1 = np.uint64(PHILOX_M0), np.uint64(PHILOX_M1)
+    shift = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = m0 * c0, m1 * c2              # 32 x 32 -> 64 bits: no overflow
+        c0, c1, c2, c3 = (p1 >> shift) ^ c1 ^ k0, p1 & _MASK32, (p0 >> shift) ^ c3 ^ k1, p0 & _MASK32
+        k0, k1 = (k0 + np.uint64(PHILOX_W0)) & _MASK32, (k1 + np.uint64(PHILOX_W1)) & _MASK32
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+class EpisodeDraws:
+    """What the draws of include/bsig_sim_draws.h are made from: ``seed`` and ``first_episode`` (integers in
+    0..2^64 - 1; episode n of a call is the global episode ``first_episode + n``), theta's bounds ``lows`` /
+    ``highs`` (pd entries; ``low == high`` is a constant), the initial internal state's ``init_lows`` /
+    ``init_highs`` (id entries), the replacement action's ``act_low`` / ``act_high``, the share ``frac_rnd`` of
+    the steps that take it instead of the policy's action, and the standard deviation ``noise_std`` of the
+    Gaussian exploration term of the others.  A pair of bounds may be left ``None`` when ``rollout_drawn`` is given
+    that array.  Everything is checked here, before any GPU call; a ValueError names its argument."""
+
+    def __init__(self, seed, first_episode=0, lows=None, highs=None, init_lows=None, init_highs=None,
+                 act_low=-1.0, act_high=1.0, frac_rnd=0.0, noise_std=0.0):
+        self.seed = self._word64('seed', seed)
+        self.first_episode = self._word64('first_episode', first_episode)
+        self.lows, self.highs = self._bounds('lows', 'highs', lows, highs, 3)
+        self.init_lows, self.init_highs = self._bounds('init_lows', 'init_highs', init_lows, init_highs, 4)
+        (self.act_low,), (self.act_high,) = self._bounds('act_low', 'act_high', [act_low], [act_high], 1)
+        self.frac_rnd, self.noise_std = self._real('frac_rnd', frac_rnd), self._real('noise_std', noise_std)
+        if not 0.0 <= self.frac_rnd <= 1.0:
+            raise ValueError('frac_rnd must lie in [0, 1], got %r' % (frac_rnd,))
+        if not (np.isfinite(self.noise_std) and self.noise_std >= 0.0):
+            raise ValueError('noise_std must be finite and >= 0, got %r' % (noise_std,))
+
+    @staticmethod
+    def _word64(name, value):
+        try:
+            word = None if isinstance(value, (bool, np.bool_)) else operator.index(value)
+        except TypeError:
+            word = None
+        if word is None or not 0 <= word < 2 ** 64:
+            raise ValueError('%s must be an int in 0..2^64 - 1, got %r' % (name, value))
+        return word
+
+    @staticmethod
+    def _real(name, value):
+        try:
+            return float(value)
+        except (TypeError, ValueError):
+            raise ValueError('%s must be a number, got %r' % (name, value)) from None
+
+    @staticmethod
+    def _bounds(lo_name, hi_name, lo, hi, most):
+        if lo is None and hi is None:
+            return None, None
+        if lo is None or hi is None:
+            raise ValueError('%s and %s come together, got %r and %r' % (lo_name, hi_name, lo, hi))
+        try:
+            lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError('%s and %s must be numbers, got %r and %r' % (lo_name, hi_name, lo, hi)) from None
+        if lo.ndim != 1 or lo.shape != hi.shape or not 1 <= lo.shape[0] <= most:
+            raise ValueError('%s and %s must both hold 1..%d bounds, got %r and %r'
+                             % (lo_name, hi_name, most, tuple(lo.shape), tuple(hi.shape)))
+        if not np.isfinite(lo).all():
+            raise ValueError('%s must be finite, got %r' % (lo_name, lo.tolist()))
+        if not np.isfinite(hi).all():
+            raise ValueError('%s must be finite, got %r' % (hi_name, hi.tolist()))
+        if (lo > hi).any():
+            raise ValueError('%s must not exceed %s, got %r and %r' % (lo_name, hi_name, lo.tolist(), hi.tolist()))
+        return lo, hi
+
+    @property
+    def thresh(self):
+        """``floor(frac_rnd * 2^32)``, in 0..2^32: step t is marked where ``x0 < thresh``."""
+        return int(np.floor(self.frac_rnd * 4294967296.0))
+
+    def key(self):
+        return self.seed & 0xFFFFFFFF, self.seed >> 32
+
+    def for_task(self, task, need_theta=True, need_init=True):
+        """ValueError unless the bounds that will be used hold ``task``'s pd and id entries."""
+        pd, idim, _ = SIM_DIMS[task]
+        for names, lo, width, need in ((('lows', 'highs', 'params'), self.lows, pd, need_theta),
+                                       (('init_lows', 'init_highs', 'init'), self.init_lows, idim, need_init)):
+            if need and lo is None:
+                raise ValueError('%s and %s are needed where no %s is given' % names)
+            names = names[:2]
+            if need and lo.shape[0] != width:
+                raise ValueError('%s and %s must hold %d bounds for %s, got %d' % (names + (width, task, lo.shape[0])))
+        return self
+
+
+def _np_dtype(dtype):
+    if dtype is None or dtype in (torch.float32, np.float32):
+        return np.float32
+    if dtype in (torch.float64, np.float64):
+        return np.float64
+    raise ValueError('the draws are stored as float32 or float64, got dtype=%r' % (dtype,))
+
+
+def _philox_words(draws, n, t, purpose):
+    """The words of global episodes first_episode .. + n - 1 at the steps ``t`` ([T] or a scalar): [n, (T,) 4]."""
+    g = np.uint64(draws.first_episode) + np.arange(n, dtype=np.uint64)          # (mod 2^64)
+    t = np.asarray(t, dtype=np.uint64)
+    shape = (n,) + t.shape
+    counters = np.empty(shape + (4,), dtype=np.uint64)
+    lead = (slice(None),) + (None,) * t.ndim
+    counters[..., 0] = (g & _MASK32)[lead]
+    counters[..., 1] = (g >> np.uint64(32))[lead]
+    counters[..., 2] = t
+    counters[..., 3] = purpose
+    return philox4x32(counters, draws.key())
+
+
+def episode_draws(task, draws, n, n_steps, policy_on=False, dtype=np.float64):
+    """The definition of include/bsig_sim_draws.h in numpy: the draws of episodes ``draws.first_episode`` ..
+    ``+ n - 1`` -> ``(theta [n, pd], init [n, id], explore [n, T], replace [n, T] uint8)``, every real formed in
+    double by the header's operations and rounded once to ``dtype`` (float32 or float64).  ``theta`` / ``init`` is
+    ``None`` where ``draws`` holds no bounds for it.  ``explore`` is ``e_t = r_t ? v_t : noise_std z_t`` and
+    ``replace`` ``r_t`` with ``policy_on``; without it every step counts as marked: ``v_t`` and 1.  The ends of
+    episodes are not known here: every step is drawn."""
+    if task not in SIM_DIMS:
+        raise ValueError("task must be 'pendulum' or 'cartpole', got %r" % (task,))
+    if not isinstance(draws, EpisodeDraws):
+        raise ValueError('draws must be an EpisodeDraws, got %r' % (type(draws).__name__,))
+    draws.for_task(task, draws.lows is not None, draws.init_lows is not None)
+    pd, idim, _ = SIM_DIMS[task]
+    store = _np_dtype(dtype)
+    unit = lambda x: x.astype(np.float64) * 2.0 ** -32      # noqa: E731  (exact)
+    theta = init = None
+    if draws.lows is not None:
+        x = unit(_philox_words(draws, n, 0, _lib.SIM_DRAW_THETA)[:, :pd])
+        theta = (draws.lows + ((draws.highs - draws.lows) * x)).astype(store)
+    if draws.init_lows is not None:
+        x = unit(_philox_words(draws, n, 0, _lib.SIM_DRAW_INIT)[:, :idim])
+        init = (draws.init_lows + ((draws.init_highs - draws.init_lows) * x)).astype(store)
+    w = _philox_words(draws, n, np.arange(n_steps), _lib.SIM_DRAW_STEP)
+    v = draws.act_low + ((draws.act_high - draws.act_low) * unit(w[..., 1]))
+    if not policy_on:
+        return theta, init, v.astype(store), np.ones((n, n_steps), dtype=np.uint8)
+    replace = w[..., 0].astype(np.uint64) < np.uint64(draws.thresh)
+    if draws.noise_std != 0.0:
+        u1, u2 = (w[..., 2].astype(np.float64) + 1.0) * 2.0 ** -32, unit(w[..., 3])
+        z = np.sqrt(-2.0 * np.log(u1)) * np.cos(_TWO_PI * u2)
+        e = np.where(replace, v, draws.noise_std * z)
+    else:
+        e = np.where(replace, v, 0.0)
+    return theta, init, e.astype(store), replace.astype(np.uint8)
+
+
+def rollout_drawn(task, n, n_steps, draws, policy=None, params=None, init=None, terminate=False, dtype=None,
+                  device='cpu', nonfinite=None, record=False):
+    """``n`` episodes of ``task`` over ``n_steps`` steps with every number drawn by the counter-based generator of
+    include/bsig_sim_draws.h from ``draws`` (an ``EpisodeDraws``): episode i is the global episode
+    ``draws.first_episode + i`` of ``draws.seed``, the same bits whatever ``n``, the launch or the device's
+    neighbours.  -> ``(theta [n, pd], init [n, id], states [n, T + 1, sd], actions_out [n, T + 1, 1],
+    lengths [n] int32)``, and with ``record`` also ``explore [n, T]`` and ``replace [n, T]`` uint8.
+
+    ``policy=None``: every action is the uniform draw ``v_t`` in ``[act_low, act_high)``.  With an ``MLPPolicy``
+    the action is ``v_t`` where the step is marked (a share ``frac_rnd``) and ``pi(o_t) + noise_std z_t``
+    elsewhere: the rule of ``rollout(policy=, replace=)``.  ``params`` / ``init`` (tensors ``[n, pd]`` / ``[n, id]``
+    on ``device``) are used as given instead of a draw.  Ends, fills, ``lengths``, ``dtype`` and ``nonfinite`` are
+    ``rollout``'s; every draw is rounded once to ``dtype`` before it is used, so ``rollout`` fed the returned
+    ``theta``, ``init``, ``explore`` and ``replace`` gives the same states bit for bit.  An ended episode draws
+    nothing more: its ``explore`` and ``replace`` from step ``lengths - 1`` on are 0.
+
+    On a CUDA ``device`` this is ONE launch of the HIP kernel, which reads no ``[n, T]`` array at all; on the CPU
+    it is ``episode_draws`` followed by the numpy rollout, and never touches a GPU.  The two differ by their
+    libraries' sine, cosine, tanh, logarithm alone.  ValueError, before any GPU call, for what does not fit."""
+    if task not in SIM_DIMS:
+        raise ValueError("task must be 'pendulum' or 'cartpole', got %r" % (task,))
+    pd, idim, sd = SIM_DIMS[task]
+    if dtype is None or dtype == torch.float32:
+        prec = _lib.F32
+    elif dtype == torch.float64:
+        prec = _lib.F64
+    else:
+        raise ValueError('rollout_drawn stores torch.float32 or torch.float64, got dtype=%r' % (dtype,))
+    counts = []
+    for name, value, top in (('n', n, 2 ** 62), ('n_steps', n_steps, 2 ** 28)):
+        try:
+            count = None if isinstance(value, (bool, np.bool_)) else operator.index(value)
+        except TypeError:
+            count = None
+        if count is None or not (name == 'n' or count >= 1) or not 0 <= count < top:
+            raise ValueError('%s must be an int >= %d, got %r' % (name, name != 'n', value))
+        counts.append(count)
+    n, n_steps = counts
+    if not isinstance(draws, EpisodeDraws):
+        raise ValueError('draws must be an EpisodeDraws, got %r' % (type(draws).__name__,))
+    if not isinstance(terminate, (bool, np.bool_)):
+        raise ValueError('terminate must be a bool, got %r' % (terminate,))
+    if policy is not None:
+        if not isinstance(policy, MLPPolicy):
+            raise ValueError('policy must be an MLPPolicy, got %r' % (type(policy).__name__,))
+        if policy.in_dim != sd:
+            raise ValueError('policy takes %d inputs, %s observes %d' % (policy.in_dim, task, sd))
+    dev = torch.device(device)
+    if dev.type == 'cuda' and dev.index is None and torch.cuda.is_available():
+        dev = torch.device('cuda', torch.cuda.current_device())
+    given = {}
+    for name, t, width in (('params', params, pd), ('init', init, idim)):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or not t.dtype.is_floating_point or tuple(t.shape) != (n, width):
+            raise ValueError('%s must be a floating-point tensor [%d, %d] for %s' % (name, n, width, task))
+        if t.device != dev:
+            raise ValueError('%s must live on %s, got %s' % (name, dev, t.device))
+        given[name] = t.detach().to(prec.dtype).contiguous()
+    draws.for_task(task, 'params' not in given, 'init' not in given)
+    if nonfinite is not None and not (torch.is_tensor(nonfinite) and nonfinite.dtype == torch.int32
+                                      and nonfinite.numel() == 1 and nonfinite.device == dev):
+        raise ValueError('nonfinite must be a 1-element int32 tensor on %s' % (dev,))
+    if dev.type != 'cuda':
+        theta, s0, explore, replace = episode_draws(task, draws, n, n_steps, policy is not None, prec.np_dtype)
+        theta = given['params'].numpy() if 'params' in given else theta
+        s0 = given['init'].numpy() if 'init' in given else s0
+        states, acts, lengths = _host_rollout(task, theta.astype(np.float64), s0.astype(np.float64),
+                                              explore.astype(np.float64)[:, :, None], n_steps, bool(terminate),
+                                              policy, replace if policy is not None else None)
+        if nonfinite is not None and not np.isfinite(states).all():
+            nonfinite.fill_(1)
+        over = np.arange(n_steps)[None, :] >= lengths[:, None] - 1          # an ended episode draws nothing more
+        explore, replace = np.where(over, 0, explore).astype(explore.dtype), np.where(over, 0, replace).astype(np.uint8)
+        out = (torch.from_numpy(np.ascontiguousarray(theta)), torch.from_numpy(np.ascontiguousarray(s0)),
+               torch.from_numpy(states).to(prec.dtype), torch.from_numpy(acts).to(prec.dtype),
+               torch.from_numpy(lengths))
+        return out + (torch.from_numpy(explore), torch.from_numpy(replace)) if record else out
+    _lib.require_gpu()
+    as_doubles = lambda b: None if b is None else (_lib.f64 * len(b))(*b.tolist())      # noqa: E731
+    bounds = [as_doubles(b) for b in (draws.lows, draws.highs, draws.init_lows, draws.init_highs)]
+    hidden = (policy.hidden if policy is not None else ()) + (0, 0)
+    with _lib.device_stream(dev) as stream:
+        theta = torch.empty((n, pd), dtype=prec.dtype, device=dev)
+        s0 = torch.empty((n, idim), dtype=prec.dtype, device=dev)
+        states = torch.empty((n, n_steps + 1, sd), dtype=prec.dtype, device=dev)
+        acts = torch.empty((n, n_steps + 1, 1), dtype=prec.dtype, device=dev)
+        lengths = torch.empty((n,), dtype=torch.int32, device=dev)
+        explore = torch.empty((n, n_steps), dtype=prec.dtype, device=dev) if record else None
+        replace = torch.empty((n, n_steps), dtype=torch.uint8, device=dev) if record else None
+        prec.sim_rollout_drawn(_lib.SIM_TASKS[task], _lib.ptr(given.get('params')), _lib.ptr(given.get('init')),
+                               bounds[0], bounds[1], bounds[2], bounds[3], draws.act_low, draws.act_high,
+                               draws.frac_rnd, draws.noise_std, draws.seed, draws.first_episode,
+                               None if policy is None else _lib.ptr(policy.packed_on(dev)),
+                               len(hidden) - 2, hidden[0], hidden[1],
+                               _lib.SIM_ACTIVATIONS[policy.activation] if policy is not None else 0,
+                               _lib.ptr(theta), _lib.ptr(s0), _lib.ptr(states), _lib.ptr(acts), _lib.ptr(lengths),
+                               _lib.ptr(explore), _lib.ptr(replace), n, n_steps, int(bool(terminate)),
+                               _lib.ptr(nonfinite), stream)
+    out = (theta, s0, states, acts, lengths)
+    return out + (explore, replace) if record else out
+
+
+_DRAW_PAIRS = {     # task -> theta's default bounds, the initial state's bounds, the actions' (pendulum_pairs, cartpole_pairs)
+    'pendulum': ((0.01, 0.01), (2.0, 2.0), (-np.pi, -1.0), (np.pi, 1.0), 0.0, 1.0),
+    'cartpole': ((0.1, 0.1), (2.0, 2.0), (-0.05,) * 4, (0.05,) * 4, -1.0, 1.0),
+}
+
+
+def draw_pairs(task, n, traj_len, seed, policy='random', lows=None, highs=None, cart_mass=1.0, frac_rnd=0.0,
+               noise_std=0.0, terminate=False, first_episode=0, device='cpu'):
+    """``n`` episodes of ``task`` with ``traj_len`` actions in the contract of ``pendulum_pairs`` and
+    ``cartpole_pairs`` -- fp32 ``(theta, states [n, traj_len + 1, sd], actions [n, traj_len + 1, 1])`` on
+    ``device``, and ``lengths`` [n] int32 with ``terminate=True`` -- with every number drawn by
+    ``rollout_drawn``: on a CUDA device one launch and no host draw or copy at all.  Episode i is the global
+    episode ``first_episode + i`` of ``seed``, so shards, ranks and later rounds make disjoint or identical
+    episodes by their indices alone.
+
+    The defaults follow those functions.  Pendulum: theta = (length, mass) ~ U[0.01, 2)^2, th ~ U[-pi, pi),
+    thdot ~ U[-1, 1), actions ~ U[0, 1).  CartPole: theta = (pole mass, pole half-length) ~ U[0.1, 2)^2 with the
+    cart's mass the constant ``cart_mass`` (or three bounds: drawn as well, theta [n, 3]), the initial state
+    ~ U[-0.05, 0.05)^4, actions ~ U[-1, 1).  ``policy='random'`` draws every action; an ``MLPPolicy`` runs closed
+    loop with ``frac_rnd`` and ``noise_std`` as in ``cartpole_pairs``, and the returned actions are the ones
+    taken.  The launch is the fp32 one: the returned theta is exactly what each episode ran with.  These are not
+    the ``RandomState`` draws of ``pendulum_pairs`` / ``cartpole_pairs``, which are unchanged."""
+    if task not in _DRAW_PAIRS:
+        raise ValueError("task must be 'pendulum' or 'cartpole', got %r" % (task,))
+    d_lows, d_highs, init_lows, init_highs, act_low, act_high = _DRAW_PAIRS[task]
+    lows = np.asarray(d_lows if lows is None else lows, dtype=np.float64)
+    highs = np.asarray(d_highs if highs is None else highs, dtype=np.float64)
+    widths = ((2,), (3,)) if task == 'cartpole' else ((2,),)
+    if lows.shape != highs.shape or lows.shape not in widths:
+        raise ValueError('lows and highs must both hold %s bounds for %s, got %r and %r'
+                         % (' or '.join(str(w[0]) for w in widths), task, tuple(lows.shape), tuple(highs.shape)))
+    k = lows.shape[0]
+    if task == 'cartpole' and k == 2:
+        try:
+            mass = float(cart_mass)
+        except (TypeError, ValueError):
+            raise ValueError('cart_mass must be a number, got %r' % (cart_mass,)) from None
+        lows, highs = np.append(lows, mass), np.append(highs, mass)
+    closed = isinstance(policy, MLPPolicy)
+    if not closed:
+        if policy not in ('random', 'policy_random'):
+            raise ValueError("policy must be 'random' or an MLPPolicy, got %r" % (policy,))
+        if frac_rnd or noise_std:
+            raise ValueError('frac_rnd and noise_std belong to an MLPPolicy, not to policy=%r' % (policy,))
+    draws = EpisodeDraws(seed, first_episode, lows, highs, init_lows, init_highs, act_low, act_high, frac_rnd,
+                         noise_std)
+    theta, _, states, actions, lengths = rollout_drawn(task, n, traj_len, draws, policy=policy if closed else None,
+                                                       terminate=terminate, dtype=torch.float32, device=device)
+    out = (theta[:, :k].contiguous(), states, actions)
     return out + (lengths,) if terminate else out

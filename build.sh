@@ -40,6 +40,8 @@ build_one sim "$SRC/sim.hip" "-ffp-contract=off"
 build_one sim_f64 "$SRC/f64/sim_f64.hip" "-ffp-contract=off"
 build_one sim_policy "$SRC/sim_policy.hip" "-ffp-contract=off"
 build_one sim_policy_f64 "$SRC/f64/sim_policy_f64.hip" "-ffp-contract=off"
+build_one sim_draws "$SRC/sim_draws.hip" "-ffp-contract=off"
+build_one sim_draws_f64 "$SRC/f64/sim_draws_f64.hip" "-ffp-contract=off"
 for f in api comm; do
   build_one "$f" "$SRC/$f.cpp" "-x hip"
 done
